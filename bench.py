@@ -10,6 +10,10 @@ decoder GRU_RNN passes, reference train_gru_cyclevae_gauss_batch.py:1326-1338 in
 device) on x[B=64 per GPU, T=80, 54].  Inputs and weights are resident in HBM before the timed region.  Utterance
 rows are independent, so N GPUs shard the batch with no data-path collective (weak scaling).
 Rank 0 prints ONE JSON line; `roofline` and `cpu_baseline` are described in DESIGN.md section "Measurement".
+
+A plain run times the headline chain only (set-up, W warm-up steps, K timed steps, the JSON line).  `--full` adds what the headline
+figure does not need: the two other forms of the recurrent kernel, the stage-4 training-step leg, the sub-paths, the MCD check against
+the stock-torch CPU path and the CPU baseline.  `--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -39,6 +43,12 @@ def main():
                     help="eval: the headline cyc2 eval chain (BASELINE configs[1]); train: one stage-4 step (configs[2])")
     ap.add_argument("--batch-per-gpu", type=int, default=None, help="utterance rows per GPU (default 64 eval, 8 train)")
     ap.add_argument("--frames", type=int, default=80)
+    ap.add_argument("--full", action="store_true",
+                    help="eval mode: also time the split2 / fp32 kernel forms, the stage-4 training-step leg and the sub-paths, check the "
+                         "chain against the stock-torch CPU path (MCD) and time the CPU baseline; the --no-* switches trim this")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="eval mode, headline config: write the arrays the last timed chain returned (lat, rec, cv, latcv, reccyc) as "
+                         "DIR/<name>.npy (float32; with N > 1 ranks DIR/<name>.rank<r>.npy)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sub-paths", action="store_true", help="skip the conversion-only / single-utterance extras (profiling runs)")
     ap.add_argument("--no-persistent", action="store_true")
@@ -64,6 +74,8 @@ def main():
     ap.add_argument("--lib-option", action="append", default=[], metavar="NAME=VALUE",
                     help="library tuning / diagnostic switch (cvae_set_option), e.g. exp=2; measurement runs only")
     args = ap.parse_args()
+    if args.dump_outputs and (args.mode != "eval" or args.config != "headline"):
+        ap.error("--dump-outputs: the eval chain of --config headline only")
 
     import shard
     if args.gpus > 1 and "RANK" not in os.environ:

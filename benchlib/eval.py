@@ -1,5 +1,5 @@
-"""The headline leg: mcep frames/s of the hu1024 / ld32 / cyc2 eval chain (BASELINE configs[1]), its roofline, the CPU baseline, the
-sub-paths and -- appended as `train_step` -- the stage-4 training step (configs[2])."""
+"""The headline leg: mcep frames/s of the hu1024 / ld32 / cyc2 eval chain (BASELINE configs[1]) and its roofline; with --full also the
+other kernel forms, the CPU baseline and MCD check, the sub-paths and -- appended as `train_step` -- the stage-4 training step (configs[2])."""
 import json
 import os
 import time
@@ -9,7 +9,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-from .report import MAC_DEC, MAC_ENC, MAC_KERN_DEC, MAC_KERN_ENC, PEAK_F32_MFMA_TFLOPS, emit, log
+from .report import MAC_DEC, MAC_ENC, MAC_KERN_DEC, MAC_KERN_ENC, PEAK_F32_MFMA_TFLOPS, dump_outputs, emit, log
 
 
 
@@ -23,6 +23,7 @@ def eval_leg(args, world, rank, dev, use_dist):
         import torch.distributed as dist
     B, T, L, NCYC = args.batch_per_gpu, args.frames, 32, 2
     emu = getattr(args, "emu", False)
+    full = args.full
     kw = {}
     cin_e, cout_e, cin_d, cout_d, HID = 54, 64, 34, 50, 1024
     if emu:      # (tests/emu_bench_backend.py: a small model on the host-fiber build, only to run this file's N > 1 path without GPUs)
@@ -55,6 +56,7 @@ def eval_leg(args, world, rank, dev, use_dist):
 
     per_launch = {}
     per_rank_ms = {}
+    last_out = {}
 
     def timed_leg(kernel, warm):
         """W warm-up chains, then EXACTLY K timed chains on the named recurrent kernel; HIP events recorded by the library on
@@ -65,12 +67,13 @@ def eval_leg(args, world, rank, dev, use_dist):
                 chain(*inputs, seed=1234)
             sync_all()
             lib.profile_collect()
+            out = None
             t0 = time.perf_counter()
             for k in range(args.steps):
                 # the event pairs bracket the kernel's launches of every `--profile-every`-th timed step: an event record costs
                 # ~6 us of idle stream on either side of a launch (rocprofv3 trace), 2.3 % of the step when every launch carries one
                 gru_vae._flags_extra = _cabi.FLAG_PROFILE if flags_env and k % max(1, args.profile_every) == 0 else 0
-                chain(*inputs, seed=1000 + k)
+                out = chain(*inputs, seed=1000 + k)
             sync_all()
             dt_ = time.perf_counter() - t0
             gru_vae._flags_extra = 0
@@ -79,6 +82,7 @@ def eval_leg(args, world, rank, dev, use_dist):
         per_launch[kernel] = launches
         assert chain.status()[0] == 0, "a hand-off spin timed out during the bench (%s)" % kernel
         gru_vae._force_kernel = None
+        last_out[kernel] = out          # what a caller received from the last timed chain (--dump-outputs)
         if use_dist:
             import shard
             # every rank's own time next to the MAX the value is computed from (which rank was the slow one)
@@ -89,16 +93,18 @@ def eval_leg(args, world, rank, dev, use_dist):
     # headline: the exact-operand kernel (k_gru_steps_v6).  The two other forms of the same kernel are timed in the same run
     # and reported as co-equal lines: split2 (22-bit fp16 pairs, k_gru_steps_v5) and fp32 (v_mfma_f32_16x16x4_f32, v4).
     dt, kern_ms, kern_n = timed_leg("exact3", args.warmup)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_out["exact3"], "" if world == 1 else ".rank%d" % rank)
     legs = {}
-    if not args.headline_only:
+    if full and not args.headline_only:
         for name in ("split2", "fp32"):
             legs[name] = timed_leg(name, max(1, args.warmup))
     frames_per_step = B * T * world
     value = frames_per_step * args.steps / dt
 
-    # ---- second leg of the default run: the stage-4 training step (BASELINE configs[2]), every rank takes part (gradient all-reduce)
+    # ---- second leg of a --full run: the stage-4 training step (BASELINE configs[2]), every rank takes part (gradient all-reduce)
     train_res = None
-    if not args.no_train_leg and not args.no_persistent:
+    if full and not args.no_train_leg and not args.no_persistent:
         try:
             train_res = train_leg(args, world, rank, dev, args.train_batch, args.train_steps, args.train_warmup)
         except Exception as e:      # the headline line must survive a failure of the second leg
@@ -217,7 +223,7 @@ def eval_leg(args, world, rank, dev, use_dist):
                                       "ms_per_step": 1e3 * dt_k / args.steps, "roofline": roof(name, dt_k, ms_k, n_k)}
 
     # ---- sub-paths SURVEY 8(d) asks to report next to config 2 (rank 0, N=1 only; not part of `value`)
-    if world == 1 and not args.no_sub_paths:
+    if world == 1 and full and not args.no_sub_paths:
         def timed(fn, n):
             with torch.no_grad():
                 for _ in range(2):
@@ -331,7 +337,7 @@ def eval_leg(args, world, rank, dev, use_dist):
                     "k_gru_steps_v6's launches over the fp32-input MFMA peak (the headline's roofline.frac at B=64)" % T, **sweep}
 
     # ---- parity in the same run + CPU baseline (rank 0, N=1 only)
-    if world == 1:
+    if world == 1 and full:
         from oracle import torch_stock as ts
         from oracle import cyclevae_oracle as orc
         ncpu = os.cpu_count() or 1
