@@ -30,7 +30,7 @@ thread_local char g_err[512] = "";
 // Tuning / diagnostic switches (cvae_set_option): the library reads NO environment variable.
 enum OptId {
     OPT_V6_LIMBS_H64, OPT_NO_LL, OPT_MAX_RT, OPT_LL_BACKOFF, OPT_EXP, OPT_OLD_OUTPROJ, OPT_GEMM_FORCE, OPT_GEMM_LOG, OPT_TRAIN_OLD_GEMM,
-    OPT_GEMM_TRACE, OPT_TRAIN_PER_STEP, OPT_TRAIN_PROF, OPT_TRAIN_BACKOFF, OPT_TRAIN_FP32_MFMA, OPT_TRAIN_BWD_PER_STEP, OPT_TRAIN_KERNEL, OPT_X3_TILE, OPT_BWD_OVERFLOW_AT, OPT_GEMM_MAX_SPLIT, OPT_BWD_KS, OPT_BWD_WIDE, OPT_COOP_LAUNCH, OPT_V6_LIMBS_H2048, OPT_V6_W2S_H64, OPT_STEP_COL_TILES, OPT_T0_IN_KERNEL, OPT_TRAIN_PROFILE, OPT_TRAIN_XMAP, OPT_LL_WIDE_ROWS, OPT_TRAIN_BP16, OPT_BWD_SPLIT_LAUNCH, OPT_WGRAD_ORDER, OPT_SIDE_TILE_CAP, OPT_MASKS_ON_SIDE, OPT_V6_BACKOFF, OPT_TRAIN_BWD_BACKOFF, OPT_LL_ROW_PAD, OPT_GEMM_MIN_DEPTH, OPT_GEMM_OCC_MODEL, OPT_GEMM_NT_FIT, OPT_TRAIN_BWD_GEOM, OPT_BWD_W3_L1_H64, OPT_TRAIN_FWD_GEOM, OPT_BWD_W3_TWO_TILES, OPT_TRAIN_FWD_BACKOFF, OPT_COUNT
+    OPT_GEMM_TRACE, OPT_TRAIN_PER_STEP, OPT_TRAIN_PROF, OPT_TRAIN_BACKOFF, OPT_TRAIN_FP32_MFMA, OPT_TRAIN_BWD_PER_STEP, OPT_TRAIN_KERNEL, OPT_X3_TILE, OPT_BWD_OVERFLOW_AT, OPT_GEMM_MAX_SPLIT, OPT_BWD_KS, OPT_COOP_LAUNCH, OPT_V6_LIMBS_H2048, OPT_V6_W2S_H64, OPT_STEP_COL_TILES, OPT_T0_IN_KERNEL, OPT_TRAIN_PROFILE, OPT_TRAIN_XMAP, OPT_MASKS_ON_SIDE, OPT_V6_BACKOFF, OPT_TRAIN_BWD_BACKOFF, OPT_LL_ROW_PAD, OPT_GEMM_MIN_DEPTH, OPT_TRAIN_BWD_GEOM, OPT_BWD_W3_L1_H64, OPT_TRAIN_FWD_GEOM, OPT_TRAIN_FWD_BACKOFF, OPT_COUNT
 };
 struct OptEntry { const char* name; long dflt; };
 const OptEntry g_opt[OPT_COUNT] = {      // names and DEFAULTS (immutable); the values live in the context
@@ -49,12 +49,11 @@ const OptEntry g_opt[OPT_COUNT] = {      // names and DEFAULTS (immutable); the 
     {"train_backoff", 32},       // s_sleep units before the first poll of a step, pair-form forward training recurrence
     {"train_fp32_mfma", 0},       // 1: forward training recurrence on v_mfma_f32_16x16x4_f32
     {"train_bwd_per_step", 0},    // 1: reverse training recurrence as 2T launches (fp32 products)
-    {"train_kernel", 0},          // training recurrences: 0 exact fp32 operands (fp16 triples), 1 fp16 pairs, 2 fp32-input MFMA
+    {"train_kernel", 0},          // training recurrences: 0 exact fp32 operands (fp16 triples), non-zero fp16 pairs (fp32-input MFMA: train_fp32_mfma)
     {"x3_tile", 0},               // exact-operand forward training recurrence: 0 pick by tiles per block, 16 / 32 force that row tile
     {"bwd_overflow_at", 60000},   // |gate gradient * 2^8| that raises status 5 in the persistent reverse recurrences (tests lower it)
     {"gemm_max_split", 16},      // cap on the contraction split of the training GEMMs (1: never split)
     {"bwd_ks", 8},                // K slices of the per-step backward product k_bwd_step_gemm (1..32)
-    {"bwd_wide", 0},              // 1: four column tiles per block in k_bwd_step_gemm where the shape allows (measured: no gain)
     {"coop_launch", 0},           // 1: the all-resident recurrent kernels go through hipLaunchCooperativeKernel (cvae_launch_coop)
     {"v6_limbs_h2048", 3},        // 2: k_gru_steps_v6 at H = 2048 on fp16 PAIRS (faster, 22-23 bit operands) instead of exact triples
     {"v6_w2s_h64", 0},            // 1: the streamed-third-limb form of k_gru_steps_v6 (what runs at H = 2048) at H = 64, for the emulator tests
@@ -62,23 +61,15 @@ const OptEntry g_opt[OPT_COUNT] = {      // names and DEFAULTS (immutable); the 
     {"t0_in_kernel", 0},          // 1: k_gru_steps_v6 forms the frame-0 feedback correction itself (cvae_t0_fix) instead of reading the prologue's gx0
     {"train_profile", 0},         // 1: HIP events around the training recurrences and GEMMs, summed per class (cvae_train_profile_collect)
     {"train_xmap", 0},            // bit 0 / 1: XCD-aware block placement in the exact forward / reverse training recurrences
-    {"ll_wide_rows", 0},          // 1: word-exchange training passes keep the 32-row padding of the tile kernels (round 3's layout, for A/B)
-    {"train_bp16", 1},            // training passes of 4..16 rows pad to ONE 16-row tile (B = 8: 16.5 -> 13.7 ms per step); 0: 32 rows = two 16-row tiles, one dead (round 3)
-    {"bwd_split_launch", 1},      // exact reverse recurrence: a pass with more than two row tiles per block runs as one launch per two tiles per block (0: one launch)
-    {"wgrad_order", -1},          // side-stream weight-gradient GEMMs of a backward pass: 0 all start right behind its reverse recurrence (beside the dgrad chain), 1 all behind the dgrad chain (under the NEXT recurrence), 2 the light ones at once and the two big contractions behind the chain; -1: 2 for passes of >= 64 rows, else 0
-    {"side_tile_cap", 2},         // > 0: GEMMs on the side stream use tiles of at most 32*cap x 32*cap (several 64 x 64 workgroups fit on a CU beside a block of the reverse recurrence: B=64 24.07-24.13 -> 23.94-24.05 ms; 0: no cap)
     {"masks_on_side", 1},         // train-mode forward with a side stream set: the recurrence's dropout mask is drawn on it, beside the front-end GEMMs (0: on the launch stream)
     {"v6_backoff", -1},           // >= 0: x 64 cycles before the first flag poll of a step in k_gru_steps_v6 blocks with one row tile (-1: swept per front-end width)
     {"train_bwd_backoff", -1},    // x 64 cycles before the first flag poll of a task of the exact reverse training recurrences; -1: 32 when a block has ONE tile (B = 8: reverse recurrences 5.3 -> 4.35 ms per step, round 6), 0 with two or more (swept in round 5: slower)
     {"ll_row_pad", 0},            // rows per frame of the time-major buffers of a word-exchange training pass (<= 3 rows): 0 = exactly B (every GEMM of a one-utterance pass over T rows; round 5: 5.28 -> 4.87 ms per step), 4 = round 4's layout
     {"gemm_min_depth", 128},      // a split contraction keeps at least this many k per slice (256 until round 5: one utterance 4.86 -> 4.76 ms)
-    {"gemm_occ_model", 1},        // tile picker of the training GEMMs: workgroups per CU from the kernels' register use (0: at most four)
-    {"gemm_nt_fit", 1},           // tile picker: constants fitted to the round-5 sweep for the launch stream's k_gemm_nt2 GEMMs (0: the shared ones)
-    {"train_bwd_geom", -1},       // exact reverse training recurrence: 1 = 16 units x 16-row tiles, zero rows of [W_hh^T | F^T] dropped (k_train_bwd_steps_w3, round 6), 0 = 8 units x 16-row tiles (k_train_bwd_steps_x3); -1: the 16-unit form for passes of at least four 16-row tiles (two tiles per block: 128 rows at hu1024 29.0K instead of 2 x 23.3K cycles per step; 64 rows on half the chip, see bwd_w3_two_tiles), else the 8-unit form (ONE tile per 16-unit block leaves the hand-off exposed: 22.1K vs 23.2K cycles per 64 rows alone, and no room for a co-resident GEMM)
+    {"train_bwd_geom", -1},       // exact reverse training recurrence: 1 = 16 units x 16-row tiles, zero rows of [W_hh^T | F^T] dropped (k_train_bwd_steps_w3, round 6), 0 = 8 units x 16-row tiles (k_train_bwd_steps_x3); -1: the 16-unit form for passes of at least four 16-row tiles (two tiles per block: 128 rows at hu1024 29.0K instead of 2 x 23.3K cycles per step; 64 rows on half the chip, two tiles per block), else the 8-unit form (ONE tile per 16-unit block leaves the hand-off exposed: 22.1K vs 23.2K cycles per 64 rows alone, and no room for a co-resident GEMM)
     {"bwd_w3_l1_h64", 0},         // 1: k_train_bwd_steps_w3 at H = 64 keeps the second limbs of two fragments per wave in LDS (what runs at H = 1024), for the emulator tests
     {"train_fwd_geom", -1},       // exact forward training recurrence: 1 = 16 units x 16-row tiles with the zero column tiles of [W_hh | F] dropped (k_train_fwd_steps_w3, round 6), 0 = the 8-unit kernels (k_train_fwd_steps_x3 / x3h); -1: the 16-unit form for passes of at least four 16-row tiles (64 rows: one tile per block behind a first-poll back-off, 128 rows: two tiles per block), else the 8-unit form
-    {"bwd_w3_two_tiles", 1},      // the 16-unit reverse recurrence gives a block two tiles whenever the pass has them: a 64-row pass then runs on 128 blocks = HALF the chip (1.12 instead of 0.84 ms), and the side stream's weight-gradient GEMMs -- which cannot share a CU with a 16-unit block -- get the other 128 CUs to themselves, uncapped tiles: B=64 step 23.2-23.3 -> 22.65-22.86 ms same box; 0: one tile per block on every CU
-    {"train_fwd_backoff", -1},    // x 64 cycles before the first flag poll of a task of the exact forward training recurrences (16-row-tile kernels); -1: swept value when a block has ONE tile (nothing else covers the hand-off and early polls slow the publishes they wait for), 0 with two or more
+    {"train_fwd_backoff", -1},    // x 64 cycles before the first flag poll of a task of the exact forward training recurrences (16-row-tile kernels); -1: 24 when a block has ONE tile (nothing else covers the hand-off and early polls slow the publishes they wait for), 0 with two or more
 };
 
 // hipEvent pairs recorded around the recurrent kernel when CVAE_FLAG_PROFILE is set

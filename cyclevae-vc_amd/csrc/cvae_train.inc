@@ -1,7 +1,7 @@
 // Training entry points of libcyclevae_hip.so (included by cvae_lib.hip): train-mode forward with a tape, BPTT backward,
 // Adam.  The recurrences are persistent cooperative launches where the size allows (H = 1024, 64: exact-operand kernels of
-// cvae_train_x3.h by default, fp16-pair kernels with train_kernel = 1) and per-step launches otherwise; everything batched is an MFMA GEMM
-// over time-major buffers (cvae_train_kernels.h).
+// cvae_train_w3.h / cvae_train_x3.h by default, fp16-pair kernels with train_kernel = 1) and per-step launches otherwise, in the
+// forms plan_train_pass chooses; everything batched is an MFMA GEMM over time-major buffers (cvae_train_kernels.h).
 namespace {
 
 struct TDims {
@@ -22,29 +22,132 @@ TDims make_tdims(const Dims& m, int T) {
     return t;
 }
 
-inline bool bwd_persist_ok(const Dims& m) { return m.H == 1024 || m.H == 64; }
-// the exact-operand recurrences (cvae_train_x3.h) are built for these sizes; their 32-row tiles set the batch padding
-inline bool x3_ok(const Dims& m) { return m.H == 1024 || m.H == 64; }
+// the persistent training recurrences (all-resident grids, weights in registers / LDS) are built for these sizes
+inline bool persist_ok(const Dims& m) { return m.H == 1024 || m.H == 64; }
 inline int x3_kpw(const Dims& m) { return m.H / 64; }
-#ifndef CVAE_FWD_BACKOFF_1TILE
-#define CVAE_FWD_BACKOFF_1TILE 24      // x 64 cycles, forward training recurrences with one tile per block (option train_fwd_backoff)
-#endif
 inline int w3_gpw(const Dims& m) { return m.H >= 128 ? m.H / 128 : 1; }      // 32-unit producer groups per wave (k_train_bwd_steps_w3)
-// Passes of at most three rows whose forward AND reverse recurrence run the word-exchange kernels (cvae_train_ll.h): those kernels
-// address rows by stride only, so the time-major buffers hold exactly B rows per frame instead of a 32-row tile -- every GEMM
-// of such a pass then contracts / produces T*B rows instead of T*32 (the recipe's batch_size_utt = 1: 80 instead of 2,560; round 4
-// padded to four rows per frame, option ll_row_pad: 5.28 -> 4.87 ms per one-utterance step).
-// Must give the same answer in forward and backward of a pass (the tape layout depends on it): options are not to be switched
-// between the two.
-inline bool ll_rows(const Dims& m, int B, int T) {
-    return B <= 3 && T > 1 && T < 65536 && x3_ok(m) && opt(OPT_TRAIN_KERNEL) == 0 && !opt(OPT_TRAIN_FP32_MFMA) && !opt(OPT_TRAIN_PER_STEP) &&
-           !opt(OPT_TRAIN_BWD_PER_STEP) && !opt(OPT_NO_LL) && !opt(OPT_LL_WIDE_ROWS) && cu_count() >= m.H / 4;
-}
-inline int train_bp(const Dims& m, int B, int T) {
-    if (ll_rows(m, B, T)) return opt(OPT_LL_ROW_PAD) > 0 ? (int)opt(OPT_LL_ROW_PAD) : B;
-    // 4..16 rows (option train_bp16): ONE 16-row tile instead of a 32-row padding whose second 16-row tile is all dead rows
-    if (B <= 16 && x3_ok(m) && opt(OPT_TRAIN_BP16) && opt(OPT_X3_TILE) != 32) return 16;
-    return (int)up(B, x3_ok(m) ? 32 : 16);
+
+// Which MFMA-order weight images a train image holds (cvae_net_prepare_train_v): bit 0 the exact-operand tile kernels (w3f, w3h,
+// wbk3, wfw3, wbw3), bit 1 the fp16-pair kernels (wrec_t8, wrec_t8h, wbk), bit 2 the fp32-MFMA persistent forward (wrec_t8).  The
+// GEMM-form weights, the per-step images (wrec_t, wbp) and the fp32 image the word-exchange kernels read are always built.
+enum { TV_EXACT = 1, TV_PAIR = 2, TV_FP32 = 4, TV_ALL = 7 };
+
+// The recurrence forms of a training pass.  Forward: word exchange (<= 3 rows, cvae_train_ll.h), exact operands in 16-unit blocks
+// (cvae_train_w3.h), in 8-unit blocks with 32- or 16-row tiles (cvae_train_x3.h), the fp16-pair or fp32-MFMA persistent kernel
+// (cvae_train_kernels.h), T per-step launches.  Reverse: word exchange, exact operands in 16- or 8-unit blocks, fp16 pairs
+// (cvae_train_bwd.h), 2T per-step launches.
+enum FwdForm { FWD_LL, FWD_W3, FWD_X3, FWD_X3H, FWD_PAIR, FWD_FP32, FWD_STEPS };
+enum BwdForm { BWD_LL, BWD_W3, BWD_X3, BWD_PAIR, BWD_STEPS };
+
+struct TrainPlan {
+    int Bp;                  // rows per frame of the time-major tape and scratch
+    FwdForm fwd;
+    int fwd_rts;             // row tiles side by side: (H / units per block) x rts blocks, a block takes tiles i, i + rts, ...
+    int fwd_col_tiles;       // 16-column tiles per block of FWD_STEPS (and of the run-time fall-back to it)
+    int fwd_backoff;         // before the first flag poll of a step / task (FWD_LL: its own units)
+    int fwd_need;            // image variant without which the pass is refused (-4)
+    bool fwd_full_writes;    // the gate tape and the state copies need no memset
+    BwdForm bwd;
+    int bwd_rts, bwd_backoff;
+    int bwd_per_launch;      // row tiles per launch of BWD_W3 / BWD_X3 (0: the whole pass in one)
+    bool bwd_writes_gates;   // every row of dgi / dgh written by the reverse recurrence (dead rows as zeros): no memset
+    int variants;            // the weight images the forms of this shape may need, their fall-backs included
+};
+
+// THE place where a training pass's recurrence forms are chosen: forward and backward of a pass call it with the same shape and
+// must see the same options (the tape layout depends on it).  Today's rule, as a table: DESIGN.md section 4.2.
+TrainPlan plan_train_pass(const Dims& m, int B, int T) {
+    const bool ok = persist_ok(m), fp32 = opt(OPT_TRAIN_FP32_MFMA) != 0, per_step = opt(OPT_TRAIN_PER_STEP) != 0,
+               bwd_per_step = opt(OPT_TRAIN_BWD_PER_STEP) != 0, no_ll = opt(OPT_NO_LL) != 0, exact = opt(OPT_TRAIN_KERNEL) == 0;
+    const long x3_tile = opt(OPT_X3_TILE), max_rt = opt(OPT_MAX_RT), fwd_geom = opt(OPT_TRAIN_FWD_GEOM), bwd_geom = opt(OPT_TRAIN_BWD_GEOM);
+    const int cus = cu_count();
+    // as many of the pass's `tiles` row tiles side by side as leave every block of `units` units a CU of its own (option max_rt caps it)
+    auto fit = [&](int units, int tiles) {
+        int r = cus / (m.H / units);
+        r = r > tiles ? tiles : r;
+        r = r < 1 ? 1 : r;
+        return max_rt >= 1 && max_rt < r ? (int)max_rt : r;
+    };
+    // blocks with ONE tile sleep before their first poll (nothing else covers the hand-off; early polls slow the publishes)
+    auto backoff = [](long o, int tiles, int rts, int one_tile) { return o >= 0 ? (int)o : (tiles + rts - 1) / rts == 1 ? one_tile : 0; };
+    const int ll_backoff = opt(OPT_LL_BACKOFF) >= 0 ? (int)opt(OPT_LL_BACKOFF) : (B == 1 ? 18 : 16);
+    TrainPlan p = {};
+
+    // at most three rows: the word-exchange kernels.  They address rows by stride only, so when both directions run them the
+    // time-major buffers hold exactly B rows per frame (option ll_row_pad): every GEMM of a one-utterance pass runs over T rows.
+    // (the forward's choice does not look at train_bwd_per_step: with it, a pass of <= 3 rows runs the forward on 16 rows per frame)
+    const bool ll_fwd = exact && !fp32 && !per_step && !no_ll && B <= 3 && T > 1 && T < 65536 && ok && cus >= m.H / 4;
+    const bool ll_rows = ll_fwd && !bwd_per_step;
+    // 4..16 rows: ONE 16-row tile; else the exact kernels' 32-row tiles
+    p.Bp = ll_rows ? (opt(OPT_LL_ROW_PAD) > 0 ? (int)opt(OPT_LL_ROW_PAD) : B) : B <= 16 && ok && x3_tile != 32 ? 16 : (int)up(B, ok ? 32 : 16);
+    const int nt16 = p.Bp / 16, nrt32 = p.Bp / 32;
+    const long mtot = (long)(T + 1) * p.Bp;
+
+    // ---- forward
+    p.fwd = FWD_STEPS;
+    if (ll_fwd) {
+        p.fwd = FWD_LL;
+        p.fwd_backoff = ll_backoff;
+    } else if (exact && !fp32 && !per_step && ok && T > 1) {
+        p.fwd_need = TV_EXACT;
+        const long fbo = opt(OPT_TRAIN_FWD_BACKOFF);
+        const int rt32 = fit(8, nrt32), ntile32 = (nrt32 + rt32 - 1) / rt32;
+        const bool fits8 = cus >= m.H / 8 && (long)m.nch * mtot * 80 < (1L << 31);
+        if (cus >= m.H / 16 && (long)(T + 1) * (m.H / 32) * nt16 * 2560 < (1L << 32) &&
+            (fwd_geom == 1 || (fwd_geom < 0 && x3_tile == 0 && nt16 >= 4))) {
+            p.fwd = FWD_W3;                  // 64 rows on: 16-unit blocks (64 rows: one tile per block behind the back-off)
+            p.fwd_rts = fit(16, nt16);
+            p.fwd_backoff = backoff(fbo, nt16, p.fwd_rts, 24);
+        } else if (fits8 && ntile32 <= 4 && (x3_tile == 32 || (x3_tile != 16 && ntile32 >= 2))) {
+            p.fwd = FWD_X3;                  // 32-row tiles where a block gets at least two (h kept in registers: at most four)
+            p.fwd_rts = rt32;
+        } else if (fits8) {
+            p.fwd = FWD_X3H;                 // 16-row tiles
+            p.fwd_rts = fit(8, nt16);
+            p.fwd_backoff = backoff(fbo, nt16, p.fwd_rts, 24);
+        }
+    }
+    if (p.fwd == FWD_STEPS && !per_step && T > 1 && ok && cus >= m.H / 8 && (long)m.nch * mtot * 64 < (1L << 31)) {
+        p.fwd = fp32 ? FWD_FP32 : FWD_PAIR;  // (also where the exact forms do not fit)
+        p.fwd_rts = fit(8, nt16);
+        p.fwd_backoff = (int)opt(OPT_TRAIN_BACKOFF);
+    }
+    // per-step launches: two 16-column tiles per block where that still gives every CU a block (hu2048: 256 blocks)
+    const long ct = opt(OPT_STEP_COL_TILES);
+    p.fwd_col_tiles = (m.H / 4) % 2 == 0 && ct != 1 && (ct == 2 || m.H / 8 >= cus) ? 2 : 1;
+    p.fwd_full_writes = T > 1 && !per_step && ok && p.fwd != FWD_LL;
+
+    // ---- reverse
+    p.bwd = BWD_STEPS;
+    if (ok && !bwd_per_step && T > 1 && cus >= m.H / 8 && (long)T * (m.H / 8) * nt16 * 2560 < (1L << 32)) {
+        if (exact && !no_ll && B <= 3 && T < 65536 && cus >= m.H / 4) {
+            p.bwd = BWD_LL;
+            p.bwd_backoff = ll_backoff;
+        } else {
+            p.bwd_rts = fit(8, nt16);
+            if (exact && cus >= m.H / 16 && (bwd_geom == 1 || (bwd_geom < 0 && nt16 >= 4))) {
+                // 16-unit blocks with two tiles each wherever the pass has two: a 64-row pass runs on half the chip, the side
+                // stream's weight-gradient GEMMs (which cannot share a CU with such a block) get the other half
+                p.bwd = BWD_W3;
+                p.bwd_rts = fit(16, nt16);
+                if (nt16 >= 2 && p.bwd_rts > nt16 / 2) p.bwd_rts = nt16 / 2;
+            } else {
+                p.bwd = exact ? BWD_X3 : BWD_PAIR;
+            }
+            p.bwd_backoff = backoff(opt(OPT_TRAIN_BWD_BACKOFF), nt16, p.bwd_rts, 32);
+            // at most two tiles per block and launch (the carried z-path gradient stays in registers; rows are independent)
+            if (p.bwd != BWD_PAIR && nt16 > 2 * p.bwd_rts) p.bwd_per_launch = 2 * p.bwd_rts;
+        }
+    }
+    // (a pass of <= 3 rows whose reverse recurrence is not the word-exchange one still zeroes its gate gradients)
+    p.bwd_writes_gates = p.bwd != BWD_LL && p.bwd != BWD_STEPS && !(B <= 3 && exact && !no_ll);
+
+    // ---- weight images: the forward's include what it falls back to when its grid or exchange buffer does not fit
+    if (!ll_rows) {
+        if (!per_step && T > 1) p.variants |= fp32 ? TV_FP32 : exact && ok ? TV_EXACT | TV_PAIR : TV_PAIR;
+        if (!bwd_per_step && T > 1 && ok) p.variants |= exact ? TV_EXACT : TV_PAIR;
+    }
+    return p;
 }
 
 struct TPrep {
@@ -69,7 +172,7 @@ TPrep tprep_layout(const Dims& m, bool sin, bool sout) {
     p.wyT = take((long)m.Co * m.H3);
     p.wbp = take((long)(m.H + m.Cop) * m.H3);   // [whhT ; wyT] as 1 KiB MFMA fragments: [col tile][K chunk][16][16]
     // persistent reverse recurrence (k_train_bwd_steps): [W_hh^T | F^T] as fp16 pairs in MFMA operand order, and out_1.w^T
-    p.wbk = bwd_persist_ok(m) ? take((long)(m.H / 8) * 4 * (m.H / 32) * 2 * 256) : -1;
+    p.wbk = persist_ok(m) ? take((long)(m.H / 8) * 4 * (m.H / 32) * 2 * 256) : -1;
     p.wo = take((long)m.Cop * m.H);
     p.woT = take((long)m.H * m.Cop);
     p.bo = take(m.Cop);
@@ -84,11 +187,11 @@ TPrep tprep_layout(const Dims& m, bool sin, bool sout) {
     p.sout_b = sout ? take(m.Co) : -1;
     p.ffold = take((long)m.H3 * m.H);        // F = W_ih[:, C9:] . out_1.w  [3H][H], fp64-accumulated once (k_prep_ffold)
     // exact-operand forward recurrence (k_train_fwd_steps_x3): [W_hh | F] as fp16 triples in MFMA operand order
-    p.w3f = x3_ok(m) ? take((long)(m.H / 8) * 4 * 2 * x3_kpw(m) * 3 * 256) : -1;
-    p.w3h = x3_ok(m) ? take((long)(m.H / 8) * 2 * 2 * (m.H / 32) * 3 * 256) : -1;   // the same for the 16-row-tile kernel
-    p.wbk3 = x3_ok(m) ? take((long)(m.H / 8) * 4 * (m.H / 32) * 640) : -1;       // [W_hh^T | F^T] as triples (k_train_bwd_steps_x3)
-    p.wbw3 = x3_ok(m) ? take((long)(m.H / 16) * 4 * w3_gpw(m) * 6 * 640) : -1;    // the same without its zero rows, 16-unit blocks (k_train_bwd_steps_w3)
-    p.wfw3 = x3_ok(m) ? take((long)(m.H / 16) * 4 * w3_gpw(m) * 6 * 640) : -1;    // [W_hh | F] without its zero column tiles, 16-unit blocks (k_train_fwd_steps_w3)
+    p.w3f = persist_ok(m) ? take((long)(m.H / 8) * 4 * 2 * x3_kpw(m) * 3 * 256) : -1;
+    p.w3h = persist_ok(m) ? take((long)(m.H / 8) * 2 * 2 * (m.H / 32) * 3 * 256) : -1;   // the same for the 16-row-tile kernel
+    p.wbk3 = persist_ok(m) ? take((long)(m.H / 8) * 4 * (m.H / 32) * 640) : -1;       // [W_hh^T | F^T] as triples (k_train_bwd_steps_x3)
+    p.wbw3 = persist_ok(m) ? take((long)(m.H / 16) * 4 * w3_gpw(m) * 6 * 640) : -1;    // the same without its zero rows, 16-unit blocks (k_train_bwd_steps_w3)
+    p.wfw3 = persist_ok(m) ? take((long)(m.H / 16) * 4 * w3_gpw(m) * 6 * 640) : -1;    // [W_hh | F] without its zero column tiles, 16-unit blocks (k_train_fwd_steps_w3)
     p.total = o;
     return p;
 }
@@ -98,10 +201,10 @@ struct TTape {   // per pass, lives from forward to backward
     int Bp;
 };
 
-TTape ttape_layout(const Dims& m, int B, int T) {
+TTape ttape_layout(const Dims& m, int B, int T, int Bp) {
     const TDims t = make_tdims(m, T);
     TTape p;
-    p.Bp = train_bp(m, B, T);
+    p.Bp = Bp;
     long o = 0;
     auto take = [&](long n) { long r = o; o += up(n, 64); return r; };
     // first what relies on being zeroed (input padding frames, batch padding rows, K padding columns) ...
@@ -130,9 +233,9 @@ struct TScratch {   // shared by all passes, contents need not survive a call
         hx3, ox3, dgic, dghc, fcnt, bcnt, bcnt2, llx, total;
 };
 
-TScratch tscratch_layout(const Dims& m, int B, int T) {
+TScratch tscratch_layout(const Dims& m, int T, long Bp) {
     const TDims t = make_tdims(m, T);
-    const long Bp = train_bp(m, B, T), mtot = (long)(T + 1) * Bp;
+    const long mtot = (long)(T + 1) * Bp;
     TScratch p;
     long o = 0;
     auto take = [&](long n) { long r = o; o += up(n, 64); return r; };
@@ -145,8 +248,8 @@ TScratch tscratch_layout(const Dims& m, int B, int T) {
     p.llx = take(2L * 4 * m.H * 4);   // exchange words of the word-exchange recurrences: [2 slots][<= 3 rows (+1)][H][4 floats]
     p.tprof = take(64);   // long long[8]: phase cycle sums of block 0 (forward 0..3, backward 4..7) with the option train_prof
     // exchanged h and o of k_train_fwd_steps_x3: limb triples, 5 bytes per value, tile-planar (2560 B per 16 units x 32 rows)
-    p.hx3 = x3_ok(m) ? take((long)m.nch * nblk(mtot, 32) * 640) : -1;
-    p.ox3 = x3_ok(m) ? take((long)T * nblk(Bp, 32) * 1024) : -1;        // dropout bits of the feedback operand (k_train_x3_maskbits)
+    p.hx3 = persist_ok(m) ? take((long)m.nch * nblk(mtot, 32) * 640) : -1;
+    p.ox3 = persist_ok(m) ? take((long)T * nblk(Bp, 32) * 1024) : -1;        // dropout bits of the feedback operand (k_train_x3_maskbits)
     // partial-sum areas: always written before they are read, so they sit in front of the zeroed backward scratch
     p.bpart = take((long)BWD_KS_MAX * Bp * (m.H + m.Cop));
     p.dgic = take((long)Bp * m.H3);      // one step's gate gradients, chunk-major, for the per-step reverse product
@@ -155,8 +258,8 @@ TScratch tscratch_layout(const Dims& m, int B, int T) {
     p.gpart2 = take(GEMM_PART_FLOATS);   // partial tiles of the GEMMs that run on the side stream (cvae_set_side_stream)
     // persistent reverse recurrence: exchanged gate gradients (one 2 KiB tile per step, producer octet and 16-row tile) and
     // W_o^T dyl_t for every step
-    p.gx = bwd_persist_ok(m) ? take((long)T * (m.H / 8) * (Bp / 16) * 640) : -1;   // (640: the 2.5 KiB pieces of the triple form)
-    p.dovl = bwd_persist_ok(m) ? take((long)T * Bp * m.H) : -1;
+    p.gx = persist_ok(m) ? take((long)T * (m.H / 8) * (Bp / 16) * 640) : -1;   // (640: the 2.5 KiB pieces of the triple form)
+    p.dovl = persist_ok(m) ? take((long)T * Bp * m.H) : -1;
     // gate gradients: the persistent reverse recurrence writes every row of them (dead rows as zeros); the per-step path relies
     // on a memset of its own
     p.dgi = take((long)T * Bp * m.H3);
@@ -187,14 +290,13 @@ static void pick_tile(int n_rows, int n_cols, long depth, long part_cap, int& TM
     static const int cand[][2] = {{4, 4}, {3, 4}, {2, 4}, {3, 2}, {2, 2}, {1, 2}, {1, 1}};
     static const double tile_rate[] = {1.0, 1.0, 0.95, 0.93, 0.9, 0.7, 0.6};
     static const double conc_rate[] = {0.0, 0.75, 0.9, 0.97, 1.0, 1.0, 1.0, 1.0, 1.0};
-    // workgroups a CU holds by registers (kernel resource usage of the build; <4,4>: k_gemm_tn2 three, k_gemm_nt2 four); option
-    // gemm_occ_model 0: round 4's model (at most four per CU whatever the tile)
+    // workgroups a CU holds by registers (kernel resource usage of the build; <4,4>: k_gemm_tn2 three, k_gemm_nt2 four)
     static const int occ_cap[] = {3, 4, 5, 6, 8, 8, 8};
     // k_gemm_nt2 (the launch stream's GEMMs): constants fitted to a sweep of every (tile, split) over every shape of an encoder and a
-    // decoder pass at 64 x 80 (tools/gemm_sweep.sh, round 5; option gemm_nt_fit 0: the shared constants above)
+    // decoder pass at 64 x 80 (tools/gemm_sweep.sh, round 5)
     static const double tile_rate_nt[] = {1.0, 1.02, 0.61, 0.71, 0.87, 0.78, 0.68};
     static const double conc_rate_nt[] = {0.0, 0.59, 0.71, 0.76, 0.92, 1.0, 1.0, 1.0, 1.0};
-    const bool fit = nt && main_stream && opt(OPT_GEMM_NT_FIT);
+    const bool fit = nt && main_stream;
     const double* trate = fit ? tile_rate_nt : tile_rate;
     const double* crate = fit ? conc_rate_nt : conc_rate;
     const double comb = fit ? 0.38 : 0.3, launch = fit ? 6.8e5 : 2.0e5;
@@ -205,7 +307,7 @@ static void pick_tile(int n_rows, int n_cols, long depth, long part_cap, int& TM
         if (cap > 0 && (c[0] > cap || c[1] > cap)) { ++ci; continue; }
         const long blocks = (long)nblk(n_rows, 32 * c[0]) * nblk(n_cols, 32 * c[1]);
         const long lds = 2L * 16 * (32 * c[0] + 32 * c[1] + 8) * 4;
-        const long occ = opt(OPT_GEMM_OCC_MODEL) ? (ci == 0 && nt ? 4 : occ_cap[ci]) : 4;
+        const long occ = ci == 0 && nt ? 4 : occ_cap[ci];
         const long kres = 150000 / lds < occ ? 150000 / lds : occ;
         for (long k = 1; k <= 16 && k <= opt(OPT_GEMM_MAX_SPLIT); k *= 2) {
             if (k > 1 && (part_cap <= 0 || k * n_rows * n_cols > part_cap || depth / k < opt(OPT_GEMM_MIN_DEPTH))) break;
@@ -254,12 +356,8 @@ static void launch_nt2(dim3 g, hipStream_t st, Args... args) {
 // to a second stream, where they overlap the NEXT pass's reverse recurrence -- a latency-bound kernel with one wave per SIMD that
 // leaves registers, LDS and most matrix-pipe slots of every CU free.  the context's side_done table remembers, per scratch buffer, the event after
 // which its dgi / dgh / gpart2 may be overwritten again.
-// Which MFMA-order weight images a train image holds (cvae_net_prepare_train_v): bit 0 the exact-operand tile kernels (w3f, w3h,
-// wbk3), bit 1 the fp16-pair kernels (wrec_t8, wrec_t8h, wbk), bit 2 the fp32-MFMA persistent forward (wrec_t8).  The GEMM-form
-// weights, the per-step images (wrec_t, wbp) and the fp32 image the word-exchange kernels read are always built.  Per-context
-// registry keyed by the image address: a pass that needs an image the caller left out (or an image this context did not prepare) is
-// refused, never run on garbage.
-enum { TV_EXACT = 1, TV_PAIR = 2, TV_FP32 = 4, TV_ALL = 7 };
+// The weight images (TV_*) each train image holds: a per-context registry keyed by the image address.  A pass that needs an image
+// the caller left out (or an image this context did not prepare) is refused, never run on garbage.
 static int image_variants(const void* image) {
     auto it = cx().train_var.find(image);
     if (it == cx().train_var.end()) return 0;       // (an image this context did not prepare holds none of them: refused with -4)
@@ -397,7 +495,7 @@ struct WgradWork {
     // persistent reverse recurrence: d loss / d y_t = dyl_t + W_ih[:, C9:]^T dgi_{t+1} is formed here (one GEMM over all steps); only
     // the out_1 weight / bias gradients read it, so it belongs to the work that may run on the side stream
     const float* wyT = nullptr;
-    int cap = 0;          // tile cap of the GEMMs when they run on the side stream (option side_tile_cap; persistent reverse recurrence only)
+    int cap = 0;          // tile cap of the GEMMs when they run on the side stream (0: none)
 };
 
 static void colsum_launch(hipStream_t cs, SplitWs ws, const float* A, long lda, float* out, int rows, int n, int acc) {
@@ -478,18 +576,7 @@ int cvae_train_variants_needed(cvae_ctx* ctx, const cvae_net_desc* d, int B, int
     CVAE_ENTER(ctx);
     Dims m;
     if (make_dims(d, &m) || B < 1 || T < 1) return TV_ALL;
-    if (ll_rows(m, B, T)) return 0;                     // forward and reverse on the word-exchange kernels
-    int v = 0;
-    const bool per_step_fwd = opt(OPT_TRAIN_PER_STEP) || T < 2;
-    const bool per_step_bwd = opt(OPT_TRAIN_BWD_PER_STEP) || T < 2 || !bwd_persist_ok(m);
-    const bool exact = opt(OPT_TRAIN_KERNEL) == 0 && x3_ok(m);
-    if (!per_step_fwd) {
-        if (opt(OPT_TRAIN_FP32_MFMA)) v |= TV_FP32;
-        else if (exact) v |= TV_EXACT | TV_PAIR;       // (pair: what an exact pass falls back to when its grid or exchange buffer does not fit)
-        else v |= TV_PAIR;
-    }
-    if (!per_step_bwd) v |= exact ? TV_EXACT : TV_PAIR;
-    return v;
+    return plan_train_pass(m, B, T).variants;
 }
 
 int cvae_net_prepare_train_v(cvae_ctx* ctx, const cvae_net_desc* d, const cvae_net_weights* w, void* image, size_t image_bytes, float gru_drop_p,
@@ -534,10 +621,10 @@ int cvae_net_prepare_train_v(cvae_ctx* ctx, const cvae_net_desc* d, const cvae_n
     if (m.H % 32 == 0 && v_pair)
         hipLaunchKernelGGL((k_prep_wrec_t8h), dim3(nblk((long)(m.H / 8) * 2 * m.nch * 512, 256)), dim3(256), 0, st,
                            (const float*)(P + pl.wrec_t8), P + pl.wrec_t8h, m.H);
-    if (x3_ok(m) && v_exact)
+    if (persist_ok(m) && v_exact)
         hipLaunchKernelGGL((k_prep_wrec_x3), dim3(nblk((long)(m.H / 8) * 4 * 2 * x3_kpw(m) * 512, 256)), dim3(256), 0, st,
                            (const float*)(P + pl.ffold), w->w_hh, P + pl.w3f, m.H, x3_kpw(m), 1.0f / (1.0f - gru_drop_p));
-    if (x3_ok(m) && v_exact)
+    if (persist_ok(m) && v_exact)
         hipLaunchKernelGGL((k_prep_wrec_x3h), dim3(nblk((long)(m.H / 8) * 2 * 2 * (m.H / 32) * 512, 256)), dim3(256), 0, st,
                            (const float*)(P + pl.ffold), w->w_hh, P + pl.w3h, m.H, 1.0f / (1.0f - gru_drop_p));
     auto copy2d = [&](float* dst, long dld, const float* src, long sld, int rows, int cols) {
@@ -553,16 +640,16 @@ int cvae_net_prepare_train_v(cvae_ctx* ctx, const cvae_net_desc* d, const cvae_n
                        (const float*)(P + pl.wyT), P + pl.wbp, m.H, m.Co, m.Cop);
     copy2d(P + pl.wo, m.H, w->out_w, m.H, m.Co, m.H);
     copy2d_t(P + pl.woT, P + pl.wo, (long)m.H, m.Cop, m.H);          // woT[k][c] = out_1.w[c][k], ld Cop (columns >= Co are zero)
-    if (bwd_persist_ok(m) && v_pair)
+    if (persist_ok(m) && v_pair)
         hipLaunchKernelGGL((k_prep_wbk), dim3(nblk((long)(m.H / 8) * 4 * (m.H / 32) * 512, 256)), dim3(256), 0, st,
                            (const float*)(P + pl.ffold), w->w_hh, P + pl.wbk, m.H, m.H / 32);
-    if (x3_ok(m) && v_exact)
+    if (persist_ok(m) && v_exact)
         hipLaunchKernelGGL((k_prep_wbk3), dim3(nblk((long)(m.H / 8) * 4 * (m.H / 32) * 512, 256)), dim3(256), 0, st,
                            (const float*)(P + pl.ffold), w->w_hh, P + pl.wbk3, m.H, m.H / 32);
-    if (x3_ok(m) && v_exact)
+    if (persist_ok(m) && v_exact)
         hipLaunchKernelGGL((k_prep_wfw3), dim3(nblk((long)(m.H / 16) * 4 * w3_gpw(m) * 6 * 512, 256)), dim3(256), 0, st,
                            (const float*)(P + pl.ffold), w->w_hh, P + pl.wfw3, m.H, w3_gpw(m), 1.0f / (1.0f - gru_drop_p));
-    if (x3_ok(m) && v_exact)
+    if (persist_ok(m) && v_exact)
         hipLaunchKernelGGL((k_prep_wbw3), dim3(nblk((long)(m.H / 16) * 4 * w3_gpw(m) * 6 * 512, 256)), dim3(256), 0, st,
                            (const float*)(P + pl.ffold), w->w_hh, P + pl.wbw3, m.H, w3_gpw(m));
     copy2d(P + pl.bo, m.Co, w->out_b, m.Co, 1, m.Co);
@@ -585,14 +672,14 @@ size_t cvae_train_tape_bytes(cvae_ctx* ctx, const cvae_net_desc* d, int B, int T
     CVAE_ENTER_SZ(ctx);
     Dims m;
     if (make_dims(d, &m) || B < 1 || T < 1) return 0;
-    return (size_t)ttape_layout(m, B, T).total * sizeof(float);
+    return (size_t)ttape_layout(m, B, T, plan_train_pass(m, B, T).Bp).total * sizeof(float);
 }
 
 size_t cvae_train_scratch_bytes(cvae_ctx* ctx, const cvae_net_desc* d, int B, int T) {
     CVAE_ENTER_SZ(ctx);
     Dims m;
     if (make_dims(d, &m) || B < 1 || T < 1) return 0;
-    return (size_t)tscratch_layout(m, B, T).total * sizeof(float);
+    return (size_t)tscratch_layout(m, T, plan_train_pass(m, B, T).Bp).total * sizeof(float);
 }
 
 int cvae_gru_rnn_forward_train(cvae_ctx* ctx, const cvae_net_desc* d, const void* image, const float* x, const float* y_in, const float* h_in,
@@ -610,8 +697,9 @@ int cvae_gru_rnn_forward_train(cvae_ctx* ctx, const cvae_net_desc* d, const void
     hipStream_t st = (hipStream_t)stream;
     const TDims t = make_tdims(m, T);
     const TPrep pl = tprep_layout(m, d->has_scale_in != 0, d->has_scale_out != 0);
-    const TTape tl = ttape_layout(m, B, T);
-    const TScratch sl = tscratch_layout(m, B, T);
+    const TrainPlan pn = plan_train_pass(m, B, T);
+    const TTape tl = ttape_layout(m, B, T, pn.Bp);
+    const TScratch sl = tscratch_layout(m, T, pn.Bp);
     const float* P = (const float*)image;
     float* TP = (float*)tape;
     float* S = (float*)scratch;
@@ -619,11 +707,7 @@ int cvae_gru_rnn_forward_train(cvae_ctx* ctx, const cvae_net_desc* d, const void
     const long mtot = (long)(T + 1) * Bp;
     // zero: input padding frames / batch padding rows / K padding columns all rely on it.  The state copies and the gate tape (90 %
     // of the tape's 170 MB at B = 64) are written in full by the persistent recurrences and need no memset then.
-    // at most three rows: the word-exchange kernels (cvae_train_ll.h) -- they write the live rows only
-    const bool ll_train = opt(OPT_TRAIN_KERNEL) == 0 && !opt(OPT_TRAIN_FP32_MFMA) && !opt(OPT_TRAIN_PER_STEP) && !opt(OPT_NO_LL) && B <= 3 &&
-                          T > 1 && T < 65536 && x3_ok(m) && cu_count() >= m.H / 4;
-    const bool full_writes = T > 1 && !opt(OPT_TRAIN_PER_STEP) && (m.H == 1024 || m.H == 64) && !ll_train;
-    CVAE_HIP_OK(hipMemsetAsync(TP, 0, (size_t)(full_writes ? tl.zero_end : tl.total) * sizeof(float), st));
+    CVAE_HIP_OK(hipMemsetAsync(TP, 0, (size_t)(pn.fwd_full_writes ? tl.zero_end : tl.total) * sizeof(float), st));
     // (the flags / status words of the recurrence and the arrival counters of this pass's split GEMMs are cleared by the prologue)
     const SplitWs fws{S + sl.gpart, (unsigned*)(S + sl.fcnt)};
     // dropout masks: supplied (parity tests inject the reference's) or drawn with Philox; the tape keeps them for backward
@@ -680,170 +764,129 @@ int cvae_gru_rnn_forward_train(cvae_ctx* ctx, const cvae_net_desc* d, const void
     gemm_nt(st, TP + tl.xcm, t.C9p, t.C9p, 0, P + pl.wix, t.C9p, P + pl.cfold_t, S + sl.gi, m.H3, T * Bp, m.H3, t.C9p, 0, fws);
 
     if (gmask_on_side) CVAE_HIP_OK(hipStreamWaitEvent(st, cx().mask_join, 0));
-    TrainStepParams sp;
-    sp.hbuf = S + sl.hbuf; sp.obuf = S + sl.obuf; sp.mtot = mtot; sp.hrow = TP + tl.hrow; sp.orow = TP + tl.orow;
-    sp.wrec_t = P + pl.wrec_t; sp.gi = S + sl.gi; sp.bhn = P + pl.bhn; sp.gmask = TP + tl.gmask; sp.tape = TP + tl.gates;
-    sp.wyT = P + pl.wyT; sp.dy = S + sl.dy; sp.Co = m.Co; sp.B = B; sp.Bp = Bp; sp.H = m.H;
-    bool fwd_done = false;
-    {   // ---- the T dependent steps (bracketed by HIP events with the option train_profile)
+    {   // ---- the T dependent steps, in the form the plan chose (bracketed by HIP events with the option train_profile)
     TrainProf tprof(st, TPROF_FWD, 0.0);
-    if (ll_train) {
-        unsigned* tfl = (unsigned*)(S + sl.tflags);
+    const int iv = image_variants(image);
+    if (pn.fwd_need & ~iv)
+        return fail(-4, "the train image was prepared without the exact-operand kernels' weight images (cvae_net_prepare_train_v "
+                        "variants %d) and this pass (B=%d, T=%d) needs them", iv, B, T);
+    unsigned* tfl = (unsigned*)(S + sl.tflags);
+    int* stat = cx().status_sink ? cx().status_sink : (int*)(tfl + (size_t)(Bp / 16) * (m.H / 8));
+    long long* prof = opt(OPT_TRAIN_PROF) ? (long long*)(S + sl.tprof) : nullptr;
+    const int xmap = (int)(opt(OPT_TRAIN_XMAP) & 1), c32w = m.H == 1024 ? 8 : 1;
+    hipError_t e = hipSuccess;
+    const char* what = nullptr;
+    // the 16-row-tile exact forms (16- and 8-unit blocks): exchanged h in limb triples, the feedback mask as bits
+    auto fwd3h = [&](const float* w3) {
+        hipLaunchKernelGGL((k_train_x3h_slot0), dim3(nblk((long)Bp * m.H, 256)), dim3(256), 0, st, (const float*)(TP + tl.hrow),
+                           S + sl.hx3, Bp, m.H);
+        hipLaunchKernelGGL((k_train_x3h_maskbits), dim3(nblk((long)T * (Bp / 16) * 2048, 256)), dim3(256), 0, st,
+                           (const float*)(TP + tl.gmask), (unsigned char*)(S + sl.ox3), T, B, Bp, m.H, c32w);
+        TrainFwd3hParams q;
+        q.hx = S + sl.hx3; q.mbits = (const unsigned char*)(S + sl.ox3); q.w3 = w3; q.gi = S + sl.gi; q.bhn = P + pl.bhn;
+        q.gmask = TP + tl.gmask; q.tape = TP + tl.gates; q.hrow = TP + tl.hrow; q.orow = TP + tl.orow; q.wyT = P + pl.wyT;
+        q.dy = S + sl.dy; q.Co = m.Co; q.B = B; q.Bp = Bp; q.H = m.H; q.T = T; q.rts = pn.fwd_rts; q.flags = tfl; q.status = stat;
+        q.backoff = pn.fwd_backoff; q.xmap = xmap; q.prof = prof;
+        return q;
+    };
+    FwdForm form = pn.fwd;
+    if ((form == FWD_PAIR && !(iv & TV_PAIR)) || (form == FWD_FP32 && !(iv & TV_FP32))) form = FWD_STEPS;   // (image without them)
+    switch (form) {
+    case FWD_LL: {           // at most three rows: fp32 FMAs, one word per unit and row exchanged (cvae_train_ll.h)
         TrainFwdLLParams q;
         q.xbuf = S + sl.llx;
         q.nonce = (cx().ll_train_launch.fetch_add(1u) & 0xffffu) << 16;
-        q.backoff = opt(OPT_LL_BACKOFF) >= 0 ? (int)opt(OPT_LL_BACKOFF) : (B == 1 ? 18 : 16);
+        q.backoff = pn.fwd_backoff;
         q.wrec_t = P + pl.wrec_t; q.gi = S + sl.gi; q.bhn = P + pl.bhn; q.gmask = TP + tl.gmask; q.tape = TP + tl.gates;
         q.hrow = TP + tl.hrow; q.orow = TP + tl.orow; q.wyT = P + pl.wyT; q.dy = S + sl.dy; q.Co = m.Co; q.B = B; q.Bp = Bp;
         q.H = m.H; q.T = T;
         q.status = cx().status_sink ? cx().status_sink : (int*)tfl;
         const dim3 gl(m.H / 4);
         const size_t ldsl = (size_t)(2 * 64 * 49 + 4 * 48) * sizeof(float);
-        hipError_t e = B == 1 ? cvae_launch_coop(k_train_fwd_steps_ll<1>, gl, dim3(256), ldsl, st, q)
-                     : B == 2 ? cvae_launch_coop(k_train_fwd_steps_ll<2>, gl, dim3(256), ldsl, st, q)
-                              : cvae_launch_coop(k_train_fwd_steps_ll<3>, gl, dim3(256), ldsl, st, q);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(-3, "small-batch forward training recurrence failed to launch: %s", hipGetErrorString(e));
-        }
-        fwd_done = true;
+        e = B == 1 ? cvae_launch_coop(k_train_fwd_steps_ll<1>, gl, dim3(256), ldsl, st, q)
+          : B == 2 ? cvae_launch_coop(k_train_fwd_steps_ll<2>, gl, dim3(256), ldsl, st, q)
+                   : cvae_launch_coop(k_train_fwd_steps_ll<3>, gl, dim3(256), ldsl, st, q);
+        what = "small-batch forward training recurrence";
+        break;
     }
-    const int iv = image_variants(image);
-    if (!fwd_done && opt(OPT_TRAIN_KERNEL) == 0 && !opt(OPT_TRAIN_FP32_MFMA) && !opt(OPT_TRAIN_PER_STEP) && x3_ok(m) && T > 1) {
-        if (!(iv & TV_EXACT))
-            return fail(-4, "the train image was prepared without the exact-operand kernels' weight images (cvae_net_prepare_train_v "
-                            "variants %d) and this pass (B=%d, T=%d) needs them", iv, B, T);
-        // exact fp32 operands as fp16 triples, 8-unit x 32-row blocks (cvae_train_x3.h)
-        const int cus = cu_count(), NB = m.H / 8, nrt32 = Bp / 32;
-        int RT = NB > 0 ? cus / NB : 0;
-        RT = RT > nrt32 ? nrt32 : RT;
-        RT = RT < 1 ? 1 : RT;               // (Bp = 16: no 32-row tile at all, the 16-row geometry below)
-        if (opt(OPT_MAX_RT) >= 1 && opt(OPT_MAX_RT) < RT) RT = (int)opt(OPT_MAX_RT);
-        const long xbytes = (long)m.nch * mtot * 80;
-        const int kpw = x3_kpw(m), ntile32 = (nrt32 + RT - 1) / RT;
-        unsigned* tfl = (unsigned*)(S + sl.tflags);
-        int* stat = cx().status_sink ? cx().status_sink : (int*)(tfl + (size_t)(Bp / 16) * NB);
-        // two geometries (cvae_train_x3.h): 32-row tiles when a block gets at least two of them (their hand-off latencies hide each
-        // other and a 32-row task costs little more than a 16-row one), else 16-row tiles, of which a block then has two
-        const bool use32 = opt(OPT_X3_TILE) == 32 || (opt(OPT_X3_TILE) != 16 && ntile32 >= 2);
-        // 16-unit x 16-row-tile blocks with the zero column tiles dropped (cvae_train_w3.h) from four 16-row tiles on: 64 rows = one tile
-        // per block with a first-poll back-off (13.1K against 16.0K cycles per step of the 8-unit kernel), 128 rows = two tiles per block;
-        // smaller passes are faster on the 8-unit kernel with its back-off (B = 8 / 16 / 32: 11.1 / 11.9 / 15.3 against 11.7 / 12.5 / 15.5 ms)
-        const int NGw = m.H / 16, nt16w = Bp / 16;
-        int RTw = NGw > 0 ? cus / NGw : 0;
-        RTw = RTw < 1 ? 1 : (RTw > nt16w ? nt16w : RTw);
-        if (opt(OPT_MAX_RT) >= 1 && opt(OPT_MAX_RT) < RTw) RTw = (int)opt(OPT_MAX_RT);
-        const bool geom_w3f = cus >= NGw && (long)(T + 1) * (m.H / 32) * nt16w * 2560 < (1L << 32) &&
-                              (opt(OPT_TRAIN_FWD_GEOM) == 1 || (opt(OPT_TRAIN_FWD_GEOM) < 0 && opt(OPT_X3_TILE) == 0 && nt16w >= 4));
-        if (geom_w3f) {
-            const int gpw = w3_gpw(m), c32w = m.H == 1024 ? 8 : 1;
-            hipLaunchKernelGGL((k_train_x3h_slot0), dim3(nblk((long)Bp * m.H, 256)), dim3(256), 0, st, (const float*)(TP + tl.hrow),
-                               S + sl.hx3, Bp, m.H);
-            hipLaunchKernelGGL((k_train_x3h_maskbits), dim3(nblk((long)T * nt16w * 2048, 256)), dim3(256), 0, st,
-                               (const float*)(TP + tl.gmask), (unsigned char*)(S + sl.ox3), T, B, Bp, m.H, c32w);
-            TrainFwd3hParams q;
-            q.hx = S + sl.hx3; q.mbits = (const unsigned char*)(S + sl.ox3); q.w3 = P + pl.wfw3; q.gi = S + sl.gi; q.bhn = P + pl.bhn;
-            q.gmask = TP + tl.gmask; q.tape = TP + tl.gates; q.hrow = TP + tl.hrow; q.orow = TP + tl.orow; q.wyT = P + pl.wyT;
-            q.dy = S + sl.dy; q.Co = m.Co; q.B = B; q.Bp = Bp; q.H = m.H; q.T = T; q.rts = RTw; q.flags = tfl; q.status = stat;
-            q.backoff = opt(OPT_TRAIN_FWD_BACKOFF) >= 0 ? (int)opt(OPT_TRAIN_FWD_BACKOFF) : (RTw > 0 && (nt16w + RTw - 1) / RTw == 1 ? CVAE_FWD_BACKOFF_1TILE : 0);
-            q.xmap = (int)(opt(OPT_TRAIN_XMAP) & 1);
-            q.prof = opt(OPT_TRAIN_PROF) ? (long long*)(S + sl.tprof) : nullptr;
-            const int nl1 = m.H == 1024 ? CVAE_FWDW_NL1 : (opt(OPT_BWD_W3_L1_H64) ? 2 : 0);
-            const size_t ldsw = (size_t)(4 * 16 * 68) * sizeof(float) + 1280 + (size_t)4 * 6 * gpw * 512 + (size_t)4 * nl1 * 1024;
-            hipError_t e = m.H == 1024 ? cvae_launch_coop(k_train_fwd_steps_w3<8, 4, CVAE_FWDW_NL1>, dim3(NGw * RTw), dim3(256), ldsw, st, q)
-                           : nl1 == 2  ? cvae_launch_coop(k_train_fwd_steps_w3<1, 2, 2>, dim3(NGw * RTw), dim3(256), ldsw, st, q)
-                                       : cvae_launch_coop(k_train_fwd_steps_w3<1, 2, 0>, dim3(NGw * RTw), dim3(256), ldsw, st, q);
-            if (e != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(-3, "exact-operand forward training recurrence (16-unit blocks) failed to launch: %s", hipGetErrorString(e));
-            }
-            fwd_done = true;
-        } else
-        if (cus >= NB && xbytes < (1L << 31) && use32 && ntile32 <= 4) {
-            hipLaunchKernelGGL((k_train_x3_slot0), dim3(nblk((long)Bp * m.H, 256)), dim3(256), 0, st, (const float*)(TP + tl.hrow),
-                               S + sl.hx3, mtot, Bp, m.H);
-            hipLaunchKernelGGL((k_train_x3_maskbits), dim3(nblk((long)T * nrt32 * 4096, 256)), dim3(256), 0, st,
-                               (const float*)(TP + tl.gmask), (unsigned char*)(S + sl.ox3), T, B, Bp, m.H, kpw);
-            TrainFwd3Params q;
-            q.hx = S + sl.hx3; q.mbits = (const unsigned char*)(S + sl.ox3); q.mtot = mtot; q.w3 = P + pl.w3f; q.gi = S + sl.gi; q.bhn = P + pl.bhn;
-            q.gmask = TP + tl.gmask; q.tape = TP + tl.gates; q.hrow = TP + tl.hrow; q.orow = TP + tl.orow; q.wyT = P + pl.wyT;
-            q.dy = S + sl.dy; q.Co = m.Co; q.B = B; q.Bp = Bp; q.H = m.H; q.T = T; q.rts = RT; q.flags = tfl;
-            q.status = stat;
-            q.xmap = (int)(opt(OPT_TRAIN_XMAP) & 1);
-            q.prof = opt(OPT_TRAIN_PROF) ? (long long*)(S + sl.tprof) : nullptr;
-            const size_t lds = (size_t)(4 * 32 * 40 + 6 * 256) * sizeof(float) + 1280 + (size_t)4 * 2 * kpw * 1024;
-            hipError_t e = m.H == 1024 ? cvae_launch_coop(k_train_fwd_steps_x3<16>, dim3(NB * RT), dim3(256), lds, st, q)
-                                       : cvae_launch_coop(k_train_fwd_steps_x3<1>, dim3(NB * RT), dim3(256), lds, st, q);
-            if (e != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(-3, "exact-operand forward training recurrence failed to launch: %s", hipGetErrorString(e));
-            }
-            fwd_done = true;
-        } else if (cus >= NB && xbytes < (1L << 31)) {
-            const int nrt16 = Bp / 16;
-            int RT16 = cus / NB;
-            RT16 = RT16 < 1 ? 1 : (RT16 > nrt16 ? nrt16 : RT16);
-            if (opt(OPT_MAX_RT) >= 1 && opt(OPT_MAX_RT) < RT16) RT16 = (int)opt(OPT_MAX_RT);
-            hipLaunchKernelGGL((k_train_x3h_slot0), dim3(nblk((long)Bp * m.H, 256)), dim3(256), 0, st, (const float*)(TP + tl.hrow),
-                               S + sl.hx3, Bp, m.H);
-            const int c32w = m.H == 1024 ? 8 : 1;
-            hipLaunchKernelGGL((k_train_x3h_maskbits), dim3(nblk((long)T * nrt16 * 2048, 256)), dim3(256), 0, st,
-                               (const float*)(TP + tl.gmask), (unsigned char*)(S + sl.ox3), T, B, Bp, m.H, c32w);
-            TrainFwd3hParams q;
-            q.hx = S + sl.hx3; q.mbits = (const unsigned char*)(S + sl.ox3); q.w3 = P + pl.w3h; q.gi = S + sl.gi; q.bhn = P + pl.bhn;
-            q.gmask = TP + tl.gmask; q.tape = TP + tl.gates; q.hrow = TP + tl.hrow; q.orow = TP + tl.orow; q.wyT = P + pl.wyT;
-            q.dy = S + sl.dy; q.Co = m.Co; q.B = B; q.Bp = Bp; q.H = m.H; q.T = T; q.rts = RT16; q.flags = tfl; q.status = stat;
-            q.backoff = opt(OPT_TRAIN_FWD_BACKOFF) >= 0 ? (int)opt(OPT_TRAIN_FWD_BACKOFF) : (RT16 > 0 && (nrt16 + RT16 - 1) / RT16 == 1 ? CVAE_FWD_BACKOFF_1TILE : 0);
-            q.xmap = (int)(opt(OPT_TRAIN_XMAP) & 1);
-            q.prof = opt(OPT_TRAIN_PROF) ? (long long*)(S + sl.tprof) : nullptr;
-            const int kw = m.H == 1024 ? 4 : 2;
-            const size_t lds = (size_t)(4 * 16 * 36) * sizeof(float) + 640 + (size_t)kw * 4 * c32w * 1024;
-            hipError_t e = m.H == 1024 ? cvae_launch_coop(k_train_fwd_steps_x3h<8, 4>, dim3(NB * RT16), dim3(256), lds, st, q)
-                                       : cvae_launch_coop(k_train_fwd_steps_x3h<1, 2>, dim3(NB * RT16), dim3(256), lds, st, q);
-            if (e != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(-3, "exact-operand forward training recurrence (16-row tiles) failed to launch: %s", hipGetErrorString(e));
-            }
-            fwd_done = true;
-        }
+    case FWD_W3: {           // exact operands, 16-unit blocks with the zero column tiles of [W_hh | F] dropped (cvae_train_w3.h)
+        const TrainFwd3hParams q = fwd3h(P + pl.wfw3);
+        const int nl1 = m.H == 1024 ? CVAE_FWDW_NL1 : (opt(OPT_BWD_W3_L1_H64) ? 2 : 0);
+        const size_t lds = (size_t)(4 * 16 * 68) * sizeof(float) + 1280 + (size_t)4 * 6 * w3_gpw(m) * 512 + (size_t)4 * nl1 * 1024;
+        const dim3 g((m.H / 16) * pn.fwd_rts);
+        e = m.H == 1024 ? cvae_launch_coop(k_train_fwd_steps_w3<8, 4, CVAE_FWDW_NL1>, g, dim3(256), lds, st, q)
+          : nl1 == 2    ? cvae_launch_coop(k_train_fwd_steps_w3<1, 2, 2>, g, dim3(256), lds, st, q)
+                        : cvae_launch_coop(k_train_fwd_steps_w3<1, 2, 0>, g, dim3(256), lds, st, q);
+        what = "exact-operand forward training recurrence (16-unit blocks)";
+        break;
     }
-    if (!fwd_done) {   // persistent recurrence when every block fits on its own CU (H = 1024 or the 64 used by tests)
-        const int cus = cu_count(), ng = m.H / 8, nrt = Bp / 16;
-        const bool small = (long)m.nch * mtot * 64 < (1L << 31);
-        if (!opt(OPT_TRAIN_PER_STEP) && small && T > 1 && (m.H == 1024 || m.H == 64) && cus >= ng &&
-            (iv & (opt(OPT_TRAIN_FP32_MFMA) ? TV_FP32 : TV_PAIR))) {     // (image without them: the per-step launches below)
-            int RT = cus / ng;
-            RT = RT < 1 ? 1 : (RT > nrt ? nrt : RT);
-            if (opt(OPT_MAX_RT) >= 1 && opt(OPT_MAX_RT) < RT) RT = (int)opt(OPT_MAX_RT);   // tests: several row tiles per block
-            unsigned* tfl = (unsigned*)(S + sl.tflags);
-            TrainFwdParams q;
-            q.hbuf = S + sl.hbuf; q.obuf = S + sl.obuf; q.mtot = mtot; q.hrow = TP + tl.hrow; q.orow = TP + tl.orow;
-            q.wrec_t8 = P + pl.wrec_t8; q.gi = S + sl.gi; q.bhn = P + pl.bhn; q.gmask = TP + tl.gmask; q.tape = TP + tl.gates;
-            q.wyT = P + pl.wyT; q.dy = S + sl.dy; q.Co = m.Co; q.B = B; q.Bp = Bp; q.H = m.H; q.T = T; q.rts = RT;
-            q.flags = tfl; q.status = cx().status_sink ? cx().status_sink : (int*)(tfl + (size_t)nrt * ng);
-            q.prof = opt(OPT_TRAIN_PROF) ? (long long*)(S + sl.tprof) : nullptr;
-            q.backoff = (int)opt(OPT_TRAIN_BACKOFF);   // swept 0..64 at B=8: 22.1 / 21.3 / 20.7 / 20.5 / 20.7 / 21.0 ms per step
-            const size_t lds = (4 * 16 * 36 + 2 * 128) * sizeof(float);
-            hipError_t e;
-            if (!opt(OPT_TRAIN_FP32_MFMA)) {   // default: the matrix product on fp16 pairs (same form as the eval kernel)
-                q.wrec_t8 = P + pl.wrec_t8h;
-                e = m.H == 1024 ? cvae_launch_coop(k_train_fwd_steps_h<16>, dim3(ng * RT), dim3(256), lds, st, q)
-                                : cvae_launch_coop(k_train_fwd_steps_h<1>, dim3(ng * RT), dim3(256), lds, st, q);
-            } else {
-                e = m.H == 1024 ? cvae_launch_coop(k_train_fwd_steps<32>, dim3(ng * RT), dim3(256), lds, st, q)
-                                : cvae_launch_coop(k_train_fwd_steps<2>, dim3(ng * RT), dim3(256), lds, st, q);
-            }
-            if (e == hipSuccess) fwd_done = true; else (void)hipGetLastError();
-        }
+    case FWD_X3: {           // exact operands as fp16 triples, 8-unit x 32-row-tile blocks (cvae_train_x3.h)
+        const int kpw = x3_kpw(m);
+        hipLaunchKernelGGL((k_train_x3_slot0), dim3(nblk((long)Bp * m.H, 256)), dim3(256), 0, st, (const float*)(TP + tl.hrow),
+                           S + sl.hx3, mtot, Bp, m.H);
+        hipLaunchKernelGGL((k_train_x3_maskbits), dim3(nblk((long)T * (Bp / 32) * 4096, 256)), dim3(256), 0, st,
+                           (const float*)(TP + tl.gmask), (unsigned char*)(S + sl.ox3), T, B, Bp, m.H, kpw);
+        TrainFwd3Params q;
+        q.hx = S + sl.hx3; q.mbits = (const unsigned char*)(S + sl.ox3); q.mtot = mtot; q.w3 = P + pl.w3f; q.gi = S + sl.gi; q.bhn = P + pl.bhn;
+        q.gmask = TP + tl.gmask; q.tape = TP + tl.gates; q.hrow = TP + tl.hrow; q.orow = TP + tl.orow; q.wyT = P + pl.wyT;
+        q.dy = S + sl.dy; q.Co = m.Co; q.B = B; q.Bp = Bp; q.H = m.H; q.T = T; q.rts = pn.fwd_rts; q.flags = tfl; q.status = stat;
+        q.xmap = xmap; q.prof = prof;
+        const size_t lds = (size_t)(4 * 32 * 40 + 6 * 256) * sizeof(float) + 1280 + (size_t)4 * 2 * kpw * 1024;
+        const dim3 g((m.H / 8) * pn.fwd_rts);
+        e = m.H == 1024 ? cvae_launch_coop(k_train_fwd_steps_x3<16>, g, dim3(256), lds, st, q)
+                        : cvae_launch_coop(k_train_fwd_steps_x3<1>, g, dim3(256), lds, st, q);
+        what = "exact-operand forward training recurrence";
+        break;
     }
-    for (int tt = 0; tt < T && !fwd_done; ++tt) {
-        sp.t = tt;
-        // two 16-column tiles per block where that still gives every CU a block (hu2048: 256 blocks)
-        if ((m.H / 4) % 2 == 0 && opt(OPT_STEP_COL_TILES) != 1 && (opt(OPT_STEP_COL_TILES) == 2 || m.H / 8 >= cu_count()))
-            if (Bp >= 128) hipLaunchKernelGGL((k_gru_step_train<2, 8>), dim3(m.H / 8), dim3(256), 2 * 4 * 128 * 20 * sizeof(float), st, sp);
-            else hipLaunchKernelGGL((k_gru_step_train<2>), dim3(m.H / 8), dim3(256), 2 * 4 * 64 * 20 * sizeof(float), st, sp);
+    case FWD_X3H: {          // the same with 16-row tiles
+        const TrainFwd3hParams q = fwd3h(P + pl.w3h);
+        const size_t lds = (size_t)(4 * 16 * 36) * sizeof(float) + 640 + (size_t)(m.H == 1024 ? 4 : 2) * 4 * c32w * 1024;
+        const dim3 g((m.H / 8) * pn.fwd_rts);
+        e = m.H == 1024 ? cvae_launch_coop(k_train_fwd_steps_x3h<8, 4>, g, dim3(256), lds, st, q)
+                        : cvae_launch_coop(k_train_fwd_steps_x3h<1, 2>, g, dim3(256), lds, st, q);
+        what = "exact-operand forward training recurrence (16-row tiles)";
+        break;
+    }
+    case FWD_PAIR:
+    case FWD_FP32: {         // the matrix product on fp16 pairs (same form as the eval kernel) or on the fp32-input MFMA
+        TrainFwdParams q;
+        q.hbuf = S + sl.hbuf; q.obuf = S + sl.obuf; q.mtot = mtot; q.hrow = TP + tl.hrow; q.orow = TP + tl.orow;
+        q.wrec_t8 = form == FWD_PAIR ? P + pl.wrec_t8h : P + pl.wrec_t8; q.gi = S + sl.gi; q.bhn = P + pl.bhn; q.gmask = TP + tl.gmask;
+        q.tape = TP + tl.gates; q.wyT = P + pl.wyT; q.dy = S + sl.dy; q.Co = m.Co; q.B = B; q.Bp = Bp; q.H = m.H; q.T = T;
+        q.rts = pn.fwd_rts; q.flags = tfl; q.status = stat; q.prof = prof; q.backoff = pn.fwd_backoff;
+        const size_t lds = (4 * 16 * 36 + 2 * 128) * sizeof(float);
+        const dim3 g((m.H / 8) * pn.fwd_rts);
+        if (form == FWD_PAIR)
+            e = m.H == 1024 ? cvae_launch_coop(k_train_fwd_steps_h<16>, g, dim3(256), lds, st, q)
+                            : cvae_launch_coop(k_train_fwd_steps_h<1>, g, dim3(256), lds, st, q);
         else
-            hipLaunchKernelGGL((k_gru_step_train<1>), dim3(m.H / 4), dim3(256), 4 * 64 * 20 * sizeof(float), st, sp);
+            e = m.H == 1024 ? cvae_launch_coop(k_train_fwd_steps<32>, g, dim3(256), lds, st, q)
+                            : cvae_launch_coop(k_train_fwd_steps<2>, g, dim3(256), lds, st, q);
+        if (e == hipSuccess) break;
+        (void)hipGetLastError();     // (a grid that does not fit: the per-step launches)
+        e = hipSuccess;
+    }
+    [[fallthrough]];
+    case FWD_STEPS: {
+        TrainStepParams sp;
+        sp.hbuf = S + sl.hbuf; sp.obuf = S + sl.obuf; sp.mtot = mtot; sp.hrow = TP + tl.hrow; sp.orow = TP + tl.orow;
+        sp.wrec_t = P + pl.wrec_t; sp.gi = S + sl.gi; sp.bhn = P + pl.bhn; sp.gmask = TP + tl.gmask; sp.tape = TP + tl.gates;
+        sp.wyT = P + pl.wyT; sp.dy = S + sl.dy; sp.Co = m.Co; sp.B = B; sp.Bp = Bp; sp.H = m.H;
+        for (int tt = 0; tt < T; ++tt) {
+            sp.t = tt;
+            if (pn.fwd_col_tiles == 1)
+                hipLaunchKernelGGL((k_gru_step_train<1>), dim3(m.H / 4), dim3(256), 4 * 64 * 20 * sizeof(float), st, sp);
+            else if (Bp >= 128)
+                hipLaunchKernelGGL((k_gru_step_train<2, 8>), dim3(m.H / 8), dim3(256), 2 * 4 * 128 * 20 * sizeof(float), st, sp);
+            else
+                hipLaunchKernelGGL((k_gru_step_train<2>), dim3(m.H / 8), dim3(256), 2 * 4 * 64 * 20 * sizeof(float), st, sp);
+        }
+        break;
+    }
+    }
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(-3, "%s failed to launch: %s", what, hipGetErrorString(e));
     }
     }
     // raw projection of the dropped states, then scale_out / clamp
@@ -891,8 +934,9 @@ int cvae_gru_rnn_backward(cvae_ctx* ctx, const cvae_net_desc* d, const void* ima
     hipStream_t st = (hipStream_t)stream;
     const TDims t = make_tdims(m, T);
     const TPrep pl = tprep_layout(m, d->has_scale_in != 0, d->has_scale_out != 0);
-    const TTape tl = ttape_layout(m, B, T);
-    const TScratch sl = tscratch_layout(m, B, T);
+    const TrainPlan pn = plan_train_pass(m, B, T);
+    const TTape tl = ttape_layout(m, B, T, pn.Bp);
+    const TScratch sl = tscratch_layout(m, T, pn.Bp);
     const float* P = (const float*)image;
     const float* TP = (const float*)tape;
     float* S = (float*)scratch;
@@ -910,11 +954,9 @@ int cvae_gru_rnn_backward(cvae_ctx* ctx, const cvae_net_desc* d, const void* ima
             }
         if (!known && cx().side_last) CVAE_HIP_OK(hipStreamWaitEvent(st, cx().side_last, 0));
     }
-    // everything from dyl on is backward scratch: zero it (padding frames of dc1p / dc0p, dh, dyfb, dead rows)
-    // (the word-exchange and the per-step reverse paths rely on zeroed gate gradients as well: dgi / dgh lie right in front of dyl)
-    const bool zero_gates = !(bwd_persist_ok(m) && !opt(OPT_TRAIN_BWD_PER_STEP) && T > 1) || ll_rows(m, B, T) ||
-                            (B <= 3 && opt(OPT_TRAIN_KERNEL) == 0 && !opt(OPT_NO_LL) && x3_ok(m));
-    const long zero_from = zero_gates ? sl.dgi : sl.dyl;
+    // everything from dyl on is backward scratch: zero it (padding frames of dc1p / dc0p, dh, dyfb, dead rows); the gate gradients
+    // dgi / dgh right in front of dyl as well, unless the reverse recurrence writes every row of them
+    const long zero_from = pn.bwd_writes_gates ? sl.dyl : sl.dgi;
     CVAE_HIP_OK(hipMemsetAsync(S + zero_from, 0, (size_t)(sl.total - zero_from) * sizeof(float), st));
     // (the LDS form holds scale_out^T whole: beyond ~120 outputs it no longer fits 64 KB and the plain kernel takes over)
     if (d->has_scale_out && (size_t)(m.Co * m.Co + CVAE_BWD_DY_ROWS * m.Co) * sizeof(float) <= 64 * 1024)
@@ -925,49 +967,42 @@ int cvae_gru_rnn_backward(cvae_ctx* ctx, const cvae_net_desc* d, const void* ima
         hipLaunchKernelGGL((k_bwd_dy), dim3(nblk((long)M * m.Cop, 256)), dim3(256), 0, st, dout, TP + tl.ybuf,
                            d->has_scale_out ? (const float*)(P + pl.sout_w) : (const float*)nullptr,
                            d->has_scale_out ? -1 : clamp_dim(clamp_lat_dim), clamp_floor(clamp_lat_dim), S + sl.dyl, B, Bp, T, m.Co, m.Cop);
-    const int cus_b = cu_count(), NBb = m.H / 8, nt16 = Bp / 16;
-    const bool persist_bwd = bwd_persist_ok(m) && !opt(OPT_TRAIN_BWD_PER_STEP) && T > 1 && cus_b >= NBb &&
-                             (long)T * NBb * nt16 * 2560 < (1L << 32);
-    // at most three rows: the word-exchange reverse recurrence (cvae_train_ll.h); it writes the live rows of dgi / dgh only
-    const bool ll_bwd = persist_bwd && opt(OPT_TRAIN_KERNEL) == 0 && !opt(OPT_NO_LL) && B <= 3 && T < 65536 && x3_ok(m) && cus_b >= m.H / 4;
-    if ((!persist_bwd || ll_bwd) && !zero_gates) CVAE_HIP_OK(hipMemsetAsync(S + sl.dgi, 0, (size_t)(sl.dyl - sl.dgi) * sizeof(float), st));
-    bool bwd_on_w3 = false;      // the reverse recurrence ran in 16-unit blocks: nothing can share their CUs, the side stream's GEMMs take whole CUs
-    if (persist_bwd) {
-        // dovl[t*Bp + b][k] = sum_c dyl[.][c] * out_1.w[c][k]: one GEMM for all steps; then the reverse recurrence as one launch;
-        // then d loss / d y_t = dyl_t + W_ih[:, C9:]^T dgi_{t+1} for the weight-gradient GEMMs, again one GEMM for all steps
+    const int NB = m.H / 8, nt16 = Bp / 16;
+    if (pn.bwd != BWD_STEPS) {
+        // dovl[t*Bp + b][k] = sum_c dyl[.][c] * out_1.w[c][k]: one GEMM for all steps; then the reverse recurrence (one launch, or one
+        // per two tiles per block); d loss / d y_t = dyl_t + W_ih[:, C9:]^T dgi_{t+1} is formed with the weight gradients (WgradWork)
         gemm_nt(st, S + sl.dyl, m.Cop, m.Cop, 0, P + pl.woT, m.Cop, nullptr, S + sl.dovl, m.H, M, m.H, m.Cop, 0, bws);
         TrainBwdParams q;
-        q.wbk = P + pl.wbk; q.gx = S + sl.gx; q.flags = (unsigned*)(S + sl.bflags);
-        q.status = cx().status_sink ? cx().status_sink : (int*)(S + sl.bflags) + nt16 * NBb;
+        q.gx = S + sl.gx; q.flags = (unsigned*)(S + sl.bflags);
+        q.status = cx().status_sink ? cx().status_sink : (int*)(S + sl.bflags) + nt16 * NB;
         q.dovl = S + sl.dovl; q.tape = TP + tl.gates; q.hrow = TP + tl.hrow; q.gmask = TP + tl.gmask; q.dgi = S + sl.dgi;
         q.dgh = S + sl.dgh; q.dhz = S + sl.dh; q.B = B; q.Bp = Bp; q.H = m.H; q.T = T; q.ovf = (float)opt(OPT_BWD_OVERFLOW_AT);
         q.prof = opt(OPT_TRAIN_PROF) ? (long long*)(S + sl.tprof) : nullptr;
-        int RT = cus_b / NBb;
-        RT = RT < 1 ? 1 : (RT > nt16 ? nt16 : RT);
-        if (opt(OPT_MAX_RT) >= 1 && opt(OPT_MAX_RT) < RT) RT = (int)opt(OPT_MAX_RT);
-        q.rts = RT;
-        q.xmap = (int)((opt(OPT_TRAIN_XMAP) >> 1) & 1);
-        // (word-exchange passes have Bp < 16: no 16-row tile at all, RT = 0 -- their kernels take their own back-off below)
-        q.backoff = opt(OPT_TRAIN_BWD_BACKOFF) >= 0 ? (int)opt(OPT_TRAIN_BWD_BACKOFF) : (RT > 0 && (nt16 + RT - 1) / RT == 1 ? 32 : 0);
+        q.rts = pn.bwd_rts; q.xmap = (int)((opt(OPT_TRAIN_XMAP) >> 1) & 1); q.backoff = pn.bwd_backoff;
         q.tile_lo = 0; q.tile_n = 0;
-        const size_t lds = (size_t)(4 * 16 * 20) * sizeof(float) + 2048;
-        hipError_t e;
-        if (!ll_bwd) {
-            const int need = opt(OPT_TRAIN_KERNEL) == 0 && x3_ok(m) ? TV_EXACT : TV_PAIR, ivb = image_variants(image);
+        if (pn.bwd != BWD_LL) {
+            const int need = pn.bwd == BWD_PAIR ? TV_PAIR : TV_EXACT, ivb = image_variants(image);
             if (!(ivb & need))
                 return fail(-4, "the train image was prepared without the weight images of the persistent reverse recurrence "
                                 "(cvae_net_prepare_train_v variants %d, needed %d; B=%d, T=%d)", ivb, need, B, T);
         }
         TrainProf tprof(st, TPROF_BWD, 0.0);
-        // which exact-operand geometry (option train_bwd_geom): 16-unit blocks where a block gets at least two tiles, else 8-unit blocks
-        const bool geom_w3 = opt(OPT_TRAIN_BWD_GEOM) == 1 ||
-                             (opt(OPT_TRAIN_BWD_GEOM) < 0 && cus_b >= m.H / 16 && nt16 >= (opt(OPT_BWD_W3_TWO_TILES) ? 4 : 2 * (cus_b / (m.H / 16))));
-        bwd_on_w3 = !ll_bwd && opt(OPT_TRAIN_KERNEL) == 0 && x3_ok(m) && geom_w3 && cus_b >= m.H / 16;
-        if (ll_bwd) {
+        hipError_t e = hipSuccess;
+        // the row tiles of the pass in launches of pn.bwd_per_launch tiles (0: all in one)
+        auto by_launch = [&](auto launch) {
+            const int per = pn.bwd_per_launch;
+            for (int lo = 0; lo < nt16 && e == hipSuccess; lo += per ? per : nt16) {
+                q.tile_lo = lo;
+                q.tile_n = per ? (nt16 - lo < per ? nt16 - lo : per) : 0;
+                e = launch();
+            }
+        };
+        switch (pn.bwd) {
+        case BWD_LL: {       // at most three rows (cvae_train_ll.h): it writes the live rows of dgi / dgh only
             TrainBwdLLParams lq;
             lq.xbuf = S + sl.llx;
             lq.nonce = (cx().ll_train_launch.fetch_add(1u) & 0xffffu) << 16;
-            lq.backoff = opt(OPT_LL_BACKOFF) >= 0 ? (int)opt(OPT_LL_BACKOFF) : (B == 1 ? 18 : 16);
+            lq.backoff = pn.bwd_backoff;
             lq.wrec_t = P + pl.wrec_t; lq.dovl = S + sl.dovl; lq.tape = TP + tl.gates; lq.hrow = TP + tl.hrow; lq.gmask = TP + tl.gmask;
             lq.dgi = S + sl.dgi; lq.dgh = S + sl.dgh; lq.B = B; lq.Bp = Bp; lq.H = m.H; lq.T = T; lq.status = q.status;
             const dim3 gl(m.H / 4);
@@ -975,68 +1010,59 @@ int cvae_gru_rnn_backward(cvae_ctx* ctx, const cvae_net_desc* d, const void* ima
             e = B == 1 ? cvae_launch_coop(k_train_bwd_steps_ll<1>, gl, dim3(256), ldsl, st, lq)
               : B == 2 ? cvae_launch_coop(k_train_bwd_steps_ll<2>, gl, dim3(256), ldsl, st, lq)
                        : cvae_launch_coop(k_train_bwd_steps_ll<3>, gl, dim3(256), ldsl, st, lq);
-        } else
-        if (opt(OPT_TRAIN_KERNEL) == 0 && x3_ok(m) && geom_w3 && cus_b >= m.H / 16) {
-            // exact operands, 16 units x ONE 16-row tile per block, zero rows dropped (cvae_train_w3.h): half the loads per CU and step
+            break;
+        }
+        case BWD_W3: {       // exact operands, 16 units x 16-row tiles per block, zero rows dropped (cvae_train_w3.h)
             q.wbk = P + pl.wbw3;
-            const int NGw = m.H / 16, gpw = w3_gpw(m);
-            int RTw = cus_b / NGw;
-            RTw = RTw < 1 ? 1 : (RTw > nt16 ? nt16 : RTw);
-            if (opt(OPT_MAX_RT) >= 1 && opt(OPT_MAX_RT) < RTw) RTw = (int)opt(OPT_MAX_RT);
-            if (opt(OPT_BWD_W3_TWO_TILES) && nt16 >= 2 && RTw > nt16 / 2) RTw = nt16 / 2;
-            q.rts = RTw;
-            q.backoff = opt(OPT_TRAIN_BWD_BACKOFF) >= 0 ? (int)opt(OPT_TRAIN_BWD_BACKOFF) : (RTw > 0 && (nt16 + RTw - 1) / RTw == 1 ? 32 : 0);
             const int nl1 = m.H == 1024 ? CVAE_BWDW_NL1 : (opt(OPT_BWD_W3_L1_H64) ? 2 : 0);
-            const size_t ldsw = (size_t)(4 * 16 * 36) * sizeof(float) + 5120 + (size_t)4 * 6 * gpw * 512 + (size_t)4 * nl1 * 1024;
-            const int per = 2 * RTw;       // at most two tiles per block and launch (the carried z-path gradient stays in registers)
-            e = hipSuccess;
-            for (int lo = 0; lo < nt16 && e == hipSuccess; lo += (opt(OPT_BWD_SPLIT_LAUNCH) && nt16 > per ? per : nt16)) {
-                q.tile_lo = lo;
-                q.tile_n = opt(OPT_BWD_SPLIT_LAUNCH) && nt16 > per ? (nt16 - lo < per ? nt16 - lo : per) : 0;
-                e = m.H == 1024 ? cvae_launch_coop(k_train_bwd_steps_w3<8, 4, CVAE_BWDW_NL1>, dim3(NGw * RTw), dim3(256), ldsw, st, q)
-                  : nl1 == 2    ? cvae_launch_coop(k_train_bwd_steps_w3<1, 2, 2>, dim3(NGw * RTw), dim3(256), ldsw, st, q)
-                                : cvae_launch_coop(k_train_bwd_steps_w3<1, 2, 0>, dim3(NGw * RTw), dim3(256), ldsw, st, q);
-            }
-        } else
-        if (opt(OPT_TRAIN_KERNEL) == 0 && x3_ok(m)) {    // exact operands: limb triples (cvae_train_x3.h)
+            const size_t lds = (size_t)(4 * 16 * 36) * sizeof(float) + 5120 + (size_t)4 * 6 * w3_gpw(m) * 512 + (size_t)4 * nl1 * 1024;
+            const dim3 g((m.H / 16) * pn.bwd_rts);
+            by_launch([&] {
+                return m.H == 1024 ? cvae_launch_coop(k_train_bwd_steps_w3<8, 4, CVAE_BWDW_NL1>, g, dim3(256), lds, st, q)
+                     : nl1 == 2    ? cvae_launch_coop(k_train_bwd_steps_w3<1, 2, 2>, g, dim3(256), lds, st, q)
+                                   : cvae_launch_coop(k_train_bwd_steps_w3<1, 2, 0>, g, dim3(256), lds, st, q);
+            });
+            break;
+        }
+        case BWD_X3: {       // exact operands as limb triples, 8-unit blocks (cvae_train_x3.h)
             q.wbk = P + pl.wbk3;
-            const size_t lds3 = (size_t)(4 * 16 * 20) * sizeof(float) + 2560 + (size_t)4 * (m.H / 32) * 512;
-            // more than two tiles per block (the stacked rec || cv pass at B = 64: four): one launch per 2 * RT tiles.  Rows are
-            // independent, the kernel is bound by what a CU loads per row, and with two tiles per block the carried z-path gradient
-            // stays in registers (same-run A/B at B = 64, option bwd_split_launch: profiles/r04_notes_training.md)
-            const int per = 2 * RT;
-            e = hipSuccess;
-            for (int lo = 0; lo < nt16 && e == hipSuccess; lo += (opt(OPT_BWD_SPLIT_LAUNCH) && nt16 > per ? per : nt16)) {
-                q.tile_lo = lo;
-                q.tile_n = opt(OPT_BWD_SPLIT_LAUNCH) && nt16 > per ? (nt16 - lo < per ? nt16 - lo : per) : 0;
-                e = m.H == 1024 ? cvae_launch_coop(k_train_bwd_steps_x3<32>, dim3(NBb * RT), dim3(256), lds3, st, q)
-                                : cvae_launch_coop(k_train_bwd_steps_x3<2>, dim3(NBb * RT), dim3(256), lds3, st, q);
-            }
-        } else
-        e = m.H == 1024 ? cvae_launch_coop(k_train_bwd_steps<32>, dim3(NBb * RT), dim3(256), lds, st, q)
-                                   : cvae_launch_coop(k_train_bwd_steps<2>, dim3(NBb * RT), dim3(256), lds, st, q);
+            const size_t lds = (size_t)(4 * 16 * 20) * sizeof(float) + 2560 + (size_t)4 * (m.H / 32) * 512;
+            const dim3 g(NB * pn.bwd_rts);
+            by_launch([&] {
+                return m.H == 1024 ? cvae_launch_coop(k_train_bwd_steps_x3<32>, g, dim3(256), lds, st, q)
+                                   : cvae_launch_coop(k_train_bwd_steps_x3<2>, g, dim3(256), lds, st, q);
+            });
+            break;
+        }
+        default: {           // fp16 pairs (cvae_train_bwd.h)
+            q.wbk = P + pl.wbk;
+            const size_t lds = (size_t)(4 * 16 * 20) * sizeof(float) + 2048;
+            e = m.H == 1024 ? cvae_launch_coop(k_train_bwd_steps<32>, dim3(NB * pn.bwd_rts), dim3(256), lds, st, q)
+                            : cvae_launch_coop(k_train_bwd_steps<2>, dim3(NB * pn.bwd_rts), dim3(256), lds, st, q);
+            break;
+        }
+        }
         if (e != hipSuccess) {
             (void)hipGetLastError();
             return fail(-3, "persistent reverse recurrence failed to launch: %s", hipGetErrorString(e));
         }
         tprof.end();
-    } else {
-    BwdStepParams bp;
-        const bool two_gemms_early = opt(OPT_TRAIN_OLD_GEMM) != 0;
+    } else {         // 2T per-step launches on fp32 products
+        const bool old_gemm = opt(OPT_TRAIN_OLD_GEMM) != 0;
+        BwdStepParams bp;
         bp.dyl = S + sl.dyl; bp.dytot = S + sl.dytot; bp.dyfb = S + sl.dyfb; bp.wo = P + pl.wo; bp.dh = S + sl.dh;
         bp.tape = TP + tl.gates; bp.hrow = TP + tl.hrow; bp.gmask = TP + tl.gmask; bp.dgi = S + sl.dgi; bp.dgh = S + sl.dgh;
-        bp.dgic = two_gemms_early ? nullptr : S + sl.dgic; bp.dghc = two_gemms_early ? nullptr : S + sl.dghc;
+        bp.dgic = old_gemm ? nullptr : S + sl.dgic; bp.dghc = old_gemm ? nullptr : S + sl.dghc;
         bp.B = B; bp.Bp = Bp; bp.H = m.H; bp.Co = m.Co; bp.Cop = m.Cop;
-        const bool two_gemms = opt(OPT_TRAIN_OLD_GEMM) != 0;
         bp.part = nullptr; bp.nparts = 0;
         BwdGemmParams gq;
         gq.wbp = P + pl.wbp; gq.part = S + sl.bpart; gq.Bp = Bp; gq.H = m.H; gq.Co = m.Co; gq.Cop = m.Cop;
-        const int nrt_b = Bp / 16, NRTB = nrt_b >= 4 ? 4 : (nrt_b >= 2 ? 2 : 1);
+        const int NRTB = nt16 >= 4 ? 4 : (nt16 >= 2 ? 2 : 1);
         TrainProf tprof(st, TPROF_BWD, 0.0);
         for (int tt = T - 1; tt >= 0; --tt) {
             bp.t = tt;
             hipLaunchKernelGGL((k_gru_step_bwd), dim3(nblk(m.H, 256), Bp), dim3(256), m.Cop * sizeof(float), st, bp);
-            if (tt > 0 && two_gemms) {
+            if (tt > 0 && old_gemm) {
                 // d loss / d h_{t-1} += W_hh^T dgh_t ;  d loss / d y_{t-1} = W_ih[:, C9:]^T dgi_t
                 gemm_ks(st, S + sl.dgh + (long)tt * Bp * m.H3, m.H3, P + pl.whhT, m.H3, S + sl.dh, m.H, Bp, m.H, m.H3, 1);
                 gemm_ks(st, S + sl.dgi + (long)tt * Bp * m.H3, m.H3, P + pl.wyT, m.H3, S + sl.dyfb, m.Cop, Bp, m.Co, m.H3, 0);
@@ -1044,47 +1070,35 @@ int cvae_gru_rnn_backward(cvae_ctx* ctx, const cvae_net_desc* d, const void* ima
                 // both products as K-split partial sums in one launch; step tt-1 adds them up
                 gq.dgh = S + sl.dghc;      // (the chunk-major copy k_gru_step_bwd just wrote)
                 gq.dgi = S + sl.dgic;
-                // four column tiles per block where there are enough of them (hu2048: 132) and H / 16 divides by 4
-                const bool wide0 = (m.H + m.Cop) / 16 >= 128 && (m.H / 16) % 4 == 0 && NRTB == 4;
-                int KSr = opt(OPT_BWD_KS) >= 1 && opt(OPT_BWD_KS) <= BWD_KS_MAX ? (int)opt(OPT_BWD_KS) : BWD_KS;
-                const bool wide = opt(OPT_BWD_WIDE) && wide0;
-                const dim3 g(wide ? nblk((m.H + m.Cop) / 16, 4) : (m.H + m.Cop) / 16, KSr, nblk(nrt_b, NRTB));
-                const size_t lds = (size_t)4 * (wide ? 4 : 1) * NRTB * 16 * 20 * sizeof(float);
-                if (wide) hipLaunchKernelGGL((k_bwd_step_gemm<4, 4>), g, dim3(256), lds, st, gq);
-                else if (NRTB == 4) hipLaunchKernelGGL((k_bwd_step_gemm<4, 1>), g, dim3(256), lds, st, gq);
+                const int KSr = opt(OPT_BWD_KS) >= 1 && opt(OPT_BWD_KS) <= BWD_KS_MAX ? (int)opt(OPT_BWD_KS) : BWD_KS;
+                const dim3 g((m.H + m.Cop) / 16, KSr, nblk(nt16, NRTB));
+                const size_t lds = (size_t)4 * NRTB * 16 * 20 * sizeof(float);
+                if (NRTB == 4) hipLaunchKernelGGL((k_bwd_step_gemm<4, 1>), g, dim3(256), lds, st, gq);
                 else if (NRTB == 2) hipLaunchKernelGGL((k_bwd_step_gemm<2, 1>), g, dim3(256), lds, st, gq);
                 else hipLaunchKernelGGL((k_bwd_step_gemm<1, 1>), g, dim3(256), lds, st, gq);
                 bp.part = S + sl.bpart; bp.nparts = KSr;
             }
         }
-}
+    }
     // ---- parameter gradients: contractions over all (t, b) rows.  The four recurrent / projection ones and their bias sums
     // feed nothing in this backward: with a side stream they run there.
-    WgradWork wgrad_held;
-    int wg_order = 0;
-    {
-        WgradWork w;
-        w.m = m; w.t = t; w.tl = tl; w.sl = sl; w.TP = TP; w.S = S; w.scratch = scratch; w.g = *g;
-        w.M = M; w.Bp = Bp; w.acc = acc; w.T = T;
-        w.wyT = persist_bwd ? P + pl.wyT : nullptr;
-        // (small tiles pay beside the blocks of a persistent recurrence; beside per-step launches -- hu2048: 169 vs 176 ms -- they only cost)
-        w.cap = persist_bwd && !ll_bwd && !bwd_on_w3 ? (int)opt(OPT_SIDE_TILE_CAP) : 0;
-        if (overlap) {
-            // Where the side-stream work starts (round 5, same-run A/B on MI355X, B = 64: 24.9 ms all at once / 24.8 all behind the
-            // chain / 24.5 split): the light part at once -- it barely disturbs the data-gradient chain, which the NEXT backward pass
-            // waits for --, the two big contractions behind the chain, where they run under the next pass's reverse recurrence (they
-            // fit beside its blocks since CVAE_BWD_RING = 5; the recurrence slows by ~0.2 ms per pass, the chain gains ~0.3).
-            // Passes of fewer than 64 rows: everything at once (B = 8: 13.8 vs 13.9 ms, one utterance 5.33 vs 5.42).
-            wg_order = opt(OPT_WGRAD_ORDER) >= 0 ? (int)opt(OPT_WGRAD_ORDER) : (Bp >= 64 ? 2 : 0);
-            if (wg_order == 0) {
-                if (int rc = launch_wgrad_side(st, w)) return rc;
-            } else if (wg_order == 2) {
-                if (int rc = launch_wgrad_side(st, w, 1)) return rc;      // the light part at once, the big contractions behind the chain
-            }
-        } else {
-            launch_wgrad(st, bws, w);
-        }
-        wgrad_held = w;
+    WgradWork w;
+    w.m = m; w.t = t; w.tl = tl; w.sl = sl; w.TP = TP; w.S = S; w.scratch = scratch; w.g = *g;
+    w.M = M; w.Bp = Bp; w.acc = acc; w.T = T;
+    w.wyT = pn.bwd != BWD_STEPS ? P + pl.wyT : nullptr;
+    // 64 x 64 tiles beside the 8-unit blocks of a persistent reverse recurrence (several fit on a CU beside one); the 16-unit blocks
+    // leave half the chip to the side stream, and beside per-step launches (hu2048: 169 vs 176 ms) small tiles only cost
+    w.cap = pn.bwd == BWD_X3 || pn.bwd == BWD_PAIR ? 2 : 0;
+    // Where the side-stream work starts (round 5, same-run A/B on MI355X, B = 64: 24.9 ms all at once / 24.8 all behind the chain /
+    // 24.5 split): from 64 rows on, the light part at once -- it barely disturbs the data-gradient chain, which the NEXT backward pass
+    // waits for --, the two big contractions behind the chain, where they run under the next pass's reverse recurrence (they fit
+    // beside its blocks since CVAE_BWD_RING = 5; the recurrence slows by ~0.2 ms per pass, the chain gains ~0.3).  Passes of fewer
+    // than 64 rows: everything at once (B = 8: 13.8 vs 13.9 ms, one utterance 5.33 vs 5.42).
+    const bool big_behind_chain = overlap && Bp >= 64;
+    if (overlap) {
+        if (int rc = launch_wgrad_side(st, w, big_behind_chain ? 1 : 3)) return rc;
+    } else {
+        launch_wgrad(st, bws, w);
     }
     auto colsum = [&](hipStream_t cs, SplitWs part, const float* A, long lda, float* out, int rows, int n) {
         colsum_launch(cs, part, A, lda, out, rows, n, acc);
@@ -1106,8 +1120,8 @@ int cvae_gru_rnn_backward(cvae_ctx* ctx, const cvae_net_desc* d, const void* ima
         hipLaunchKernelGGL((k_scale_in_bwd), dim3(nblk((long)B * T * m.C, 256)), dim3(256), 0, st, (const float*)(S + sl.dxn),
                            (const float*)nullptr, dx, B, Bp, T, m.C, t.Cq, m.pad);
     }
-    if (overlap && wg_order != 0)
-        if (int rc = launch_wgrad_side(st, wgrad_held, wg_order == 2 ? 2 : 3)) return rc;
+    if (big_behind_chain)
+        if (int rc = launch_wgrad_side(st, w, 2)) return rc;
     {
         hipStream_t cs = st;
         SplitWs part = bws;
@@ -1148,7 +1162,7 @@ int cvae_train_debug_counters(cvae_ctx* ctx, const cvae_net_desc* d, int B, int 
     Dims m;
     if (int rc = make_dims(d, &m)) return rc;
     if (!scratch || !out) return fail(-1, "null argument");
-    const TScratch sl = tscratch_layout(m, B, T);
+    const TScratch sl = tscratch_layout(m, T, plan_train_pass(m, B, T).Bp);
     CVAE_HIP_OK(hipMemcpyAsync(out, (const float*)scratch + sl.tprof, 8 * sizeof(long long), hipMemcpyDeviceToHost, (hipStream_t)stream));
     CVAE_HIP_OK(hipStreamSynchronize((hipStream_t)stream));
     return 0;

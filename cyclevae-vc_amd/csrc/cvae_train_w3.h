@@ -1,5 +1,5 @@
 // k_train_bwd_steps_w3: the exact-operand reverse recurrence (k_train_bwd_steps_x3: same arithmetic, same hand-off) in the geometry
-// that HALVES what a CU loads per step: block = 16 hidden units x ONE 16-row tile instead of 8 units x two tiles.
+// that HALVES what a CU loads per row tile and step: block = 16 hidden units x 16-row tiles instead of 8 units.
 //
 // Why.  Every block needs ALL 4H gate gradients of its rows per step (5 bytes each); the 8-unit kernel's CU pulls two tiles =
 // 640 KB per step through a ~45 B/clk load path (14K of its 23.6K cycles per step, profiles/r05_notes_training.md).  A 16-unit
@@ -15,8 +15,9 @@
 //     N : dnp of units 32G .. 32G+31                                 -> feedback columns only  (F_n^T)
 // A producer block (16 units = half h of group G) writes chunk P_h and the kq halves {2h, 2h+1} of Q and N: every piece is a run of
 // whole 128-byte lines that no second producer touches.  288 MFMAs per wave and step instead of 384, 320 instead of 640 KB.
-// With one tile per block the hand-off latency is exposed (nothing else to run under it); passes of 128 rows give a block two
-// tiles, which hide each other's.
+// With one tile per block the hand-off latency is exposed (nothing else to run under it), so a block gets two tiles wherever the
+// pass has two (plan_train_pass): they hide each other's, and a 64-row pass runs on half the chip, leaving the other half to the
+// side stream's weight-gradient GEMMs.
 #pragma once
 #include <cvae_intrin.h>
 
@@ -304,7 +305,8 @@ __global__ __launch_bounds__(256, 1) void k_train_bwd_steps_w3(TrainBwdParams p)
 // = 36 MFMAs per chunk where the 8-unit kernels issue 48 (two 16-column tiles x two paths x six products, a quarter of the columns
 // zero), and the per-task costs that do not shrink with the tile (reduction, cell, publish) are paid per 16 units instead of per 8.
 // Measured (MI355X, 128 rows x 80 frames, cycles per step of block 0): 25.8K -> 23.1K; with ONE tile per block (64 rows) the exposed
-// hand-off cancels the gain (16.8K vs 16.0K for k_train_fwd_steps_x3h), so those passes stay on the 8-unit kernel.
+// hand-off cancels the gain (16.8K vs 16.0K for k_train_fwd_steps_x3h) unless the block sleeps before its first poll of a task:
+// 13.1K behind that back-off, so this kernel carries every pass from 64 rows on.
 // Exchange, dropout bits and slot 0: exactly k_train_fwd_steps_x3h's (k_train_x3h_slot0, k_train_x3h_maskbits with C32W = GPW): a
 // 16-unit block publishes the kq halves {2h, 2h+1} (h = g & 1) of chunk g >> 1 -- runs of whole 128-byte lines.
 // ------------------------------------------------------------------------------------------------------------------------

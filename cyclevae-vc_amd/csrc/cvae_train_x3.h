@@ -340,8 +340,9 @@ __global__ __launch_bounds__(256, 1) void k_train_fwd_steps_x3(TrainFwd3Params p
 // Why both geometries exist.  A dependent step costs one chip-wide hand-off (publish, drain, flag, poll, first operand back:
 // ~3 us).  With ONE tile per block that latency is exposed in full every step (32-row kernel at B = 64: flag wait 8.6K of 23.5K
 // cycles per step); with two or more tiles per block the other tiles' work runs under it.  At B = 64 on 256 CUs a 32-row tiling
-// leaves one tile per block, a 16-row tiling two: this kernel serves passes of up to 64 rows per 128 blocks, the 32-row kernel the
-// larger ones (the stacked rec || cv decoder pass), where it needs half the flag waits, reductions and publishes per row.
+// leaves one tile per block, a 16-row tiling two.  Since the 16-unit kernel (cvae_train_w3.h) carries every pass from 64 rows on, this
+// kernel serves the smaller ones (one tile per block behind a first-poll back-off); the 32-row kernel runs where option x3_tile asks
+// for it, or where a block gets at least two 32-row tiles and the 16-unit form is switched off.
 // Exchange: 2.5 KiB per (slot, 32-k chunk, 16-row tile) = { l0 [4 kq][16 rows][8 halves] | l1 likewise | l2 [4 kq][16 rows][8 B] }.
 // ------------------------------------------------------------------------------------------------------------------------
 struct TrainFwd3hParams {
@@ -657,7 +658,7 @@ __global__ void k_prep_wbk3(const float* F, const float* whh, float* wbk3, int H
 // Operand ring depth of the reverse recurrence (k-steps in flight per wave).  5 instead of 8 costs the recurrence nothing (9.74-9.80 ms
 // per step either way) and takes the kernel from 256 + 178 to 256 + 140 registers per lane: 116 free, so that a block of the big
 // weight-gradient GEMMs (k_gemm_tn2<3,4>, 63 + 48) or two of the small ones fit on a SIMD beside it -- the side stream's GEMMs run
-// at 7.2 instead of 9.5 ms of kernel time per step and may be started BEHIND the data-gradient chain (option wgrad_order)
+// at 7.2 instead of 9.5 ms of kernel time per step and may be started BEHIND the data-gradient chain (passes of >= 64 rows)
 #define CVAE_BWD_RING 5
 #endif
 template <int KPW>   // 32-k steps per wave = 4H / 128

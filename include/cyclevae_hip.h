@@ -156,18 +156,17 @@ int cvae_set_draw_parts(cvae_ctx* ctx, int32_t parts);
  *   "v6_limbs_h64"      3        2: the two-limb form of k_gru_steps_v6 (what H = 2048 runs) at H = 64, for the emulator tests
  *   "old_outproj"       0        1: projection of an exact-operand pass from the fp32 state copy instead of the limb triples
  *   "exp"               0        measurement switches of the dataflow kernels (bit layout: Step6Params::exp)
- *   "train_kernel"      0        training recurrences: 0 exact fp32 operands (three fp16 limbs), 1 fp16 pairs (22 bits), 2 fp32-input MFMA
+ *   "train_kernel"      0        training recurrences: 0 exact fp32 operands (three fp16 limbs), non-zero fp16 pairs (22 bits)
  *   "bwd_overflow_at"   60000    |gate gradient * 2^8| from which the persistent reverse recurrences raise status 5 (tests lower it)
  *   "x3_tile"           0        exact-operand forward training recurrence: 16 / 32 force that row-tile geometry (0: by tiles per block)
  *   "train_per_step"    0        1: forward training recurrence as T launches
  *   "train_bwd_per_step" 0       1: reverse training recurrence as 2T launches (fp32 products; the fallback of a range overflow)
- *   "train_fp32_mfma"   0        1: same as train_kernel = 2 for the forward recurrence (kept for the tests)
+ *   "train_fp32_mfma"   0        1: the forward training recurrence on the fp32-input MFMA (kept for the tests)
  *   "train_backoff"     32       s_sleep units before the first poll of a step (pair-form forward training recurrence)
  *   "train_prof"        0        1: phase cycle sums of block 0 of the training recurrences (cvae_train_debug_counters)
  *   "train_old_gemm"    0        1: the simple GEMM kernels (the unaligned-operand fallbacks) everywhere
  *   "gemm_max_split"    16       cap on the contraction split the tile picker may choose for a training GEMM (1: never split)
  *   "bwd_ks"            8        K slices of the per-step reverse product (the any-H path, e.g. H = 2048); 1..32
- *   "bwd_wide"          0        1: four column tiles per block in that product (measured at hu2048: no gain)
  *   "v6_limbs_h2048"    3        2: k_gru_steps_v6 at H = 2048 on fp16 PAIRS (22-23 bit operands, 1.5x faster) instead of exact triples
  *                                with the third weight limb streamed from L2
  *   "v6_w2s_h64"        0        1: that streamed form at H = 64, for the emulator tests
@@ -180,28 +179,22 @@ int cvae_set_draw_parts(cvae_ctx* ctx, int32_t parts);
  *   "gemm_log"          0        measurement: every training GEMM bracketed by HIP events and printed to stderr (synchronises)
  *   "gemm_trace"        0        1: print when a GEMM takes a fallback kernel
  *   "train_xmap"        0        bit 0 / bit 1: XCD-aware block placement in the exact-operand forward / reverse training recurrence
- *   "ll_wide_rows"      0        1: training passes of <= 3 rows pad their time-major buffers to 32 rows per frame (round 3) instead of B
  *   "ll_row_pad"        0        rows per frame of the time-major buffers of a training pass of <= 3 rows (the word-exchange kernels address
  *                                rows by stride only): 0 = exactly B, so that every GEMM of a one-utterance pass runs over T rows; 4: round 4
  *   "gemm_min_depth"    128      training GEMMs: a split contraction keeps at least this many k per slice (256 until round 5)
- *   "gemm_nt_fit"       1        tile picker: constants fitted to the round-5 sweep (tools/gemm_sweep.sh) for the launch stream's GEMMs; 0: the shared ones
- *   "gemm_occ_model"    1        tile picker of the training GEMMs counts the workgroups a CU really holds (registers of each tile's
- *                                kernel); 0: at most four per CU whatever the tile (round 4)
- *   "train_bwd_backoff" 0        x 64 cycles before the first flag poll of a task of the exact reverse training recurrence (measured: no gain)
- *   "train_bp16"        1        training passes of 4..16 rows are padded to one 16-row tile; 0: to 32 rows (two 16-row tiles, one dead: round 3)
- *   "bwd_split_launch"  1        exact reverse recurrence: passes with more than two row tiles per block run as one launch per two tiles
- *                                per block (rows are independent); 0: one launch per pass (round 3)
+ *   "train_bwd_backoff" -1       >= 0: x 64 cycles before the first flag poll of a task of the persistent reverse training recurrences
+ *                                (-1: 32 when a block has one row tile, else 0)
+ *   "train_fwd_backoff" -1       >= 0: the same for the exact forward training recurrences with 16-row tiles (-1: 24 with one tile, else 0)
+ *   "train_fwd_geom"    -1       exact forward training recurrence: 1 = 16-unit blocks (k_train_fwd_steps_w3), 0 = 8-unit blocks
+ *                                (k_train_fwd_steps_x3 / x3h); -1: 16-unit blocks for passes of at least 64 rows
+ *   "train_bwd_geom"    -1       exact reverse training recurrence: 1 = 16-unit blocks (k_train_bwd_steps_w3), 0 = 8-unit blocks
+ *                                (k_train_bwd_steps_x3); -1: 16-unit blocks for passes of at least 64 rows
+ *   "bwd_w3_l1_h64"     0        1: the 16-unit reverse recurrence at H = 64 keeps second limbs in LDS (what H = 1024 runs), for the emulator tests
  *   "train_profile"     0        1: HIP events on the launch stream around the training recurrences and GEMMs (cvae_train_profile_collect)
  *   "v6_backoff"        -1       >= 0: units of 64 cycles a block of k_gru_steps_v6 with one row tile sleeps before the first flag poll
  *                                of a step (-1: swept per front-end width: 8 for the decoder's KFW = 6, 2 for the encoder's 8)
  *   "masks_on_side"     1        train-mode forward with a side stream set: the dropout mask of the recurrence's feedback operand is
  *                                drawn on the side stream, beside the prologue and the front-end GEMMs (0: on the launch stream)
- *   "wgrad_order"       -1       where the side-stream weight-gradient GEMMs of a backward pass start: 0 all right behind its reverse
- *                                recurrence (beside the data-gradient chain), 1 all behind that chain (under the NEXT pass's recurrence),
- *                                2 the light ones at once and the two big contractions behind the chain; -1: 2 for passes of >= 64
- *                                rows, else 0 (profiles/r05_notes_training.md)
- *   "side_tile_cap"     2        > 0 caps the tiles of side-stream GEMMs at 32*cap x 32*cap (small tiles fit on a CU
- *                                beside a block of the reverse recurrence); 0: no cap
  */
 int cvae_set_option(cvae_ctx* ctx, const char* name, int64_t value);
 int cvae_get_option(cvae_ctx* ctx, const char* name, int64_t* value);
@@ -372,8 +365,9 @@ int cvae_step_timing(cvae_ctx* ctx, const cvae_net_desc* d, int B, int T, const 
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Training (stage 4, train_gru_cyclevae_gauss_batch.py:1326-1420): train-mode pass with a tape, BPTT backward, Adam.
- * Recurrences: one persistent launch per pass and direction at H = 1024 / 64 (exact fp32 operands as fp16 triples by default, option
- * "train_kernel"), per-step launches at other sizes; GEMMs on the fp32-input MFMA.
+ * Recurrences: at H = 1024 / 64 persistent launches (exact fp32 operands as fp16 triples by default, option "train_kernel"; 16-unit
+ * blocks from 64 rows on, 8-unit blocks below; word-exchange kernels for passes of at most three rows), per-step launches at other
+ * sizes; GEMMs on the fp32-input MFMA.
  * ------------------------------------------------------------------------------------------------------------------ */
 
 /* Gradient outputs in the reference's state_dict layout (scale_in / scale_out are frozen, train...:369-372). */

@@ -64,3 +64,23 @@ def test_recurrent_kernels_do_not_spill():
         assert scratch == 0, "%s spills %d bytes per lane" % (name, scratch)
     assert {"k_gru_steps_v6", "k_gru_steps_ll", "k_train_fwd_steps_x3", "k_train_fwd_steps_w3", "k_train_bwd_steps"} <= seen
     assert any("k_train_bwd_steps_w3" in b.split()[0] for b in blocks)          # (covered by the k_train_bwd_steps prefix above)
+
+
+def test_option_table_matches_the_library():
+    """The option table in include/cyclevae_hip.h lists exactly the names and defaults of g_opt (cvae_lib.hip), and a fresh context
+    reports those defaults."""
+    from emu_util import emu_lib
+    text = open(os.path.join(ROOT, "include", "cyclevae_hip.h")).read()
+    table = text[text.index(" *   name                default  meaning"):text.index("int cvae_set_option(")]
+    documented = {n: int(v) for n, v in re.findall(r'^ \*   "([a-z0-9_]+)"\s+(-?\d+)\s', table, re.M)}
+    src = open(os.path.join(ROOT, "cyclevae-vc_amd", "csrc", "cvae_lib.hip")).read()
+    g_opt = src[src.index("const OptEntry g_opt[OPT_COUNT] = {"):]
+    g_opt = g_opt[:g_opt.index("\n};")]
+    defined = {n: int(v) for n, v in re.findall(r'^\s*\{"([a-z0-9_]+)",\s*(-?\d+)\}', g_opt, re.M)}
+    assert len(defined) >= 30
+    assert documented == defined, ({k: documented.get(k) for k in set(documented) ^ set(defined)},
+                                   {k: (documented[k], defined[k]) for k in set(documented) & set(defined) if documented[k] != defined[k]})
+    lib = emu_lib()
+    lib.reset_options()
+    for name, dflt in defined.items():
+        assert lib.get_option(name) == dflt, name

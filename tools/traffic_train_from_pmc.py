@@ -13,8 +13,8 @@ import sqlite3
 import sys
 
 CLASSES = {
-    "fwd_recurrence": ("k_train_fwd_steps_x3", "k_train_fwd_steps_w3"),   # x3h<8,4> (64-row passes), w3<8,4,11> (stacked 128-row passes, round 6)
-    "bwd_recurrence": ("k_train_bwd_steps_x3", "k_train_bwd_steps_w3"),   # x3<32> (64-row passes), w3<8,4,12> (128-row passes, round 6)
+    "fwd_recurrence": ("k_train_fwd_steps_x3", "k_train_fwd_steps_w3"),   # x3h<8,4> (passes below 64 rows), w3<8,4,11> (from 64 rows on, round 6)
+    "bwd_recurrence": ("k_train_bwd_steps_x3", "k_train_bwd_steps_w3"),   # x3<32> (passes below 64 rows), w3<8,4,12> (from 64 rows on, round 6)
     "forward_and_dgrad_gemms": ("k_gemm_nt2",),
     "wgrad_gemms": ("k_gemm_tn2",),
 }
