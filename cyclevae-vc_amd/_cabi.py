@@ -7,7 +7,7 @@ library is missing or its ABI version differs, loading raises.
 import ctypes as C
 import os
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 FLAG_PERSISTENT = 1
 FLAG_PROFILE = 2
 FLAG_GENERIC_STEP = 4
@@ -44,6 +44,20 @@ class NetWeights(C.Structure):
 
 
 GRAD_FIELDS = ("conv0_w", "conv0_b", "conv1_w", "conv1_b", "w_ih", "w_hh", "b_ih", "b_hh", "out_w", "out_b")
+
+
+class GruLayer(C.Structure):
+    """The four tensors of one GRU layer l >= 1 (cvae_gru_layer, ABI 7)."""
+    _fields_ = [(f, _fp) for f in ("w_ih", "w_hh", "b_ih", "b_hh")]
+
+
+def upper_layer_keys(n_layers):
+    """state_dict keys of the GRU layers 1 .. n_layers-1, per layer in the field order of GruLayer."""
+    return [tuple("gru.%s_l%d" % (k, l) for k in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")) for l in range(1, n_layers)]
+
+
+DEEP_PER_STEP, DEEP_GENERIC, DEEP_RESIDENT = 0, 1, 2      # cvae_plan_pass_deep
+MAX_LAYERS = 8                                              # CVAE_DEEP_MAX_LAYERS
 
 
 class NetGrads(C.Structure):
@@ -146,6 +160,19 @@ class CvaeLib(object):
         L.cvae_gru_rnn_forward_stacked_carry.argtypes = [C.POINTER(NetDesc), _fp, C.c_int, C.POINTER(PassInput), C.POINTER(C.c_void_p),
                                                          C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p),
                                                          C.POINTER(C.c_void_p), _fp, C.c_size_t, C.c_int, _fp]
+        for fn in ("cvae_net_prepared_bytes_deep", "cvae_net_prepare_scratch_bytes_deep"):
+            getattr(L, fn).restype = C.c_size_t
+            getattr(L, fn).argtypes = [C.POINTER(NetDesc), C.c_int]
+        L.cvae_net_prepare_deep.restype = C.c_int
+        L.cvae_net_prepare_deep.argtypes = [C.POINTER(NetDesc), C.c_int, C.POINTER(NetWeights), C.POINTER(GruLayer), _fp, C.c_size_t, _fp,
+                                            C.c_size_t, _fp]
+        L.cvae_pass_workspace_bytes_deep.restype = C.c_size_t
+        L.cvae_pass_workspace_bytes_deep.argtypes = [C.POINTER(NetDesc), C.c_int, C.c_int, C.c_int]
+        L.cvae_plan_pass_deep.restype = C.c_int
+        L.cvae_plan_pass_deep.argtypes = [C.POINTER(NetDesc), C.c_int, C.c_int, C.c_int, C.c_int]
+        L.cvae_gru_rnn_forward_deep.restype = C.c_int
+        L.cvae_gru_rnn_forward_deep.argtypes = [C.POINTER(NetDesc), C.c_int, _fp, C.POINTER(PassInput), _fp, _fp, C.c_int, C.c_int,
+                                                C.c_int, _fp, _fp, _fp, _fp, C.c_size_t, C.c_int, _fp]
         L.cvae_sample.restype = C.c_int
         L.cvae_sample.argtypes = [_fp, C.c_int, C.c_int, _fp, C.c_uint64, C.c_uint64, _fp, _fp, _fp]
         L.cvae_sample_laplace.restype = C.c_int
@@ -321,6 +348,45 @@ class CvaeLib(object):
         self._check(self.lib.cvae_gru_rnn_forward(C.byref(d), prepared, C.byref(pin), y_in, h_in or None, B, T,
                                                   clamp_lat_dim, trj_out, y_last or None, h_last or None, ws, ws_bytes,
                                                   flags, stream or None), "cvae_gru_rnn_forward")
+
+    # -- networks with n_layers >= 2 GRU layers (ABI 7; n_layers == 1: the one-layer entry points under another name) ----
+    def prepared_bytes_deep(self, d, n_layers):
+        n = self.lib.cvae_net_prepared_bytes_deep(C.byref(d), n_layers)
+        if n == 0:
+            raise CvaeError("bad net descriptor / n_layers: %s" % self.lib.cvae_last_error_string().decode())
+        return n
+
+    def prepare_scratch_bytes_deep(self, d, n_layers):
+        return self.lib.cvae_net_prepare_scratch_bytes_deep(C.byref(d), n_layers)
+
+    def net_prepare_deep(self, d, n_layers, weight_ptrs, upper_ptrs, prepared, prepared_bytes, scratch, scratch_bytes, stream=0):
+        """upper_ptrs: one (w_ih, w_hh, b_ih, b_hh) tuple of device addresses per GRU layer 1 .. n_layers-1."""
+        if len(upper_ptrs) != n_layers - 1:
+            raise CvaeError("net_prepare_deep: %d upper layers given, n_layers=%d" % (len(upper_ptrs), n_layers))
+        w = NetWeights(**{f: weight_ptrs.get(f) or None for f in WEIGHT_FIELDS})
+        up = (GruLayer * max(1, n_layers - 1))(*[GruLayer(*u) for u in upper_ptrs])
+        self._check(self.lib.cvae_net_prepare_deep(C.byref(d), n_layers, C.byref(w), up, prepared, prepared_bytes, scratch,
+                                                   scratch_bytes, stream or None), "cvae_net_prepare_deep")
+
+    def pass_workspace_bytes_deep(self, d, n_layers, B, T):
+        n = self.lib.cvae_pass_workspace_bytes_deep(C.byref(d), n_layers, B, T)
+        if n == 0:
+            raise CvaeError("cvae_pass_workspace_bytes_deep: bad arguments (n_layers=%d, B=%d, T=%d)" % (n_layers, B, T))
+        return n
+
+    def plan_pass_deep(self, d, n_layers, B, T, flags=0):
+        """DEEP_PER_STEP / DEEP_GENERIC / DEEP_RESIDENT: the recurrence a pass of this shape takes."""
+        rc = self.lib.cvae_plan_pass_deep(C.byref(d), n_layers, B, T, flags)
+        if rc < 0:
+            self._check(rc, "cvae_plan_pass_deep")
+        return rc
+
+    def gru_rnn_forward_deep(self, d, n_layers, prepared, pin, y_in, h_in, B, T, clamp_lat_dim, trj_out, y_last, h_last, ws, ws_bytes,
+                             flags=0, stream=0):
+        """h_in / h_last: [n_layers][B][H] device addresses or None."""
+        self._check(self.lib.cvae_gru_rnn_forward_deep(C.byref(d), n_layers, prepared, C.byref(pin), y_in, h_in or None, B, T,
+                                                       clamp_lat_dim, trj_out, y_last or None, h_last or None, ws, ws_bytes, flags,
+                                                       stream or None), "cvae_gru_rnn_forward_deep")
 
     def sample(self, lat, rows, lat_dim, eps, seed, draw_id, z, eps_out=None, stream=0):
         self._check(self.lib.cvae_sample(lat, rows, lat_dim, eps or None, seed, draw_id, z, eps_out or None,
@@ -532,4 +598,6 @@ EXPORTS = ("cvae_last_error_string", "cvae_abi_version", "cvae_ctx_create", "cva
            "cvae_gru_rnn_forward_train", "cvae_gru_rnn_backward", "cvae_adam_step", "cvae_adam_step_counted", "cvae_train_debug_counters",
            "cvae_sample_cat", "cvae_sample_cat_backward", "cvae_stage4_loss", "cvae_mcd_l1", "cvae_mcd_l1_backward", "cvae_kl_gauss",
            "cvae_kl_gauss_backward",
-           "cvae_gv_postfilter", "cvae_mcd_aligned", "cvae_mc2e", "cvae_dtw_work_bytes", "cvae_dtw_org_to_trg")
+           "cvae_gv_postfilter", "cvae_mcd_aligned", "cvae_mc2e", "cvae_dtw_work_bytes", "cvae_dtw_org_to_trg",
+           "cvae_net_prepared_bytes_deep", "cvae_net_prepare_scratch_bytes_deep", "cvae_net_prepare_deep", "cvae_pass_workspace_bytes_deep",
+           "cvae_plan_pass_deep", "cvae_gru_rnn_forward_deep")

@@ -16,6 +16,7 @@
 
 #include "cvae_kernels.h"
 #include "cvae_train_kernels.h"
+#include "cvae_deep.h"
 #include "cyclevae_hip.h"
 
 namespace {
@@ -1176,3 +1177,4 @@ int cvae_workspace_status(cvae_ctx* ctx, const void* workspace, int32_t status_o
 #include "cvae_train.inc"
 #include "cvae_stage4.inc"
 #include "cvae_stage6.inc"
+#include "cvae_deep.inc"

@@ -11,6 +11,10 @@ clamp_vae_laplace flag of GRU_RNN.forward (reference gru_vae.py:101-145, :415-41
 The VQ helpers of the same file (nn_search, nn_search_batch, weighted_ctr: gru_vae.py:148-195) are torch ops, as in the reference;
 sampling_vae (:69-82) is the 2-D form of sampling_vae_batch.  Not carried over (dead code): GMM, the relu_vae
 (variance-parameter) branches and the forward flags noise/res/softmax/sigmoid/exp/scale_in_out; they raise NotImplementedError.
+
+hidden_layers >= 2 (nn.GRU(tot_in_dim, H, hidden_layers), gru_vae.py:309-312): eval / no-grad passes, the fresh CycleChain and the
+stage-6 conversion run on the *_deep entry points (cvae_gru_rnn_forward_deep: h is [L, B, H]); train-mode / autograd passes,
+stage4.Stage4Step, the carry form of the chain and the windowed stage-6 forms raise NotImplementedError naming hidden_layers.
 """
 import torch
 from torch import nn
@@ -263,6 +267,9 @@ class _Prepared(object):
         lib = _lib()
         fields = _weight_fields(mod, device)
         key = tuple((f, t.data_ptr(), t._version) for f, t in sorted(fields.items()))
+        L = mod.hidden_layers
+        if L > 1:
+            return self._get_deep(mod, device, lib, fields, key, L)
         if key != self.key:
             d = lib.desc(mod.in_dim, mod.out_dim, mod.hidden_units, mod.kernel_size, mod.dilation_size,
                          mod.scale_in_flag, mod.scale_out_flag)
@@ -273,10 +280,34 @@ class _Prepared(object):
             self.key, self.image, self.desc, self._keep = key, image, d, (fields, scratch)
         return self.desc, self.image
 
+    def _get_deep(self, mod, device, lib, fields, key, L):
+        """hidden_layers >= 2: the image of cvae_net_prepare_deep, rebuilt when a tensor of ANY layer changes."""
+        upper = []
+        for l in range(1, L):
+            ts = []
+            for leaf in ("weight_ih_l%d", "weight_hh_l%d", "bias_ih_l%d", "bias_hh_l%d"):
+                t = mod.gru._parameters[leaf % l]
+                if t.device != device or t.dtype != torch.float32:
+                    raise RuntimeError("parameter gru.%s is %s/%s, expected float32 on %s" % (leaf % l, t.device, t.dtype, device))
+                ts.append(t.detach() if t.is_contiguous() else t.detach().contiguous())
+            upper.append(tuple(ts))
+        key = key + tuple((l, t.data_ptr(), t._version) for l, ts in enumerate(upper) for t in ts)
+        if key != self.key:
+            d = lib.desc(mod.in_dim, mod.out_dim, mod.hidden_units, mod.kernel_size, mod.dilation_size,
+                         mod.scale_in_flag, mod.scale_out_flag)
+            image = torch.empty(lib.prepared_bytes_deep(d, L), dtype=torch.uint8, device=device)
+            scratch = torch.empty(lib.prepare_scratch_bytes_deep(d, L), dtype=torch.uint8, device=device)
+            lib.net_prepare_deep(d, L, {f: t.data_ptr() for f, t in fields.items()}, [tuple(t.data_ptr() for t in ts) for ts in upper],
+                                 image.data_ptr(), image.numel(), scratch.data_ptr(), scratch.numel(), _stream())
+            self.key, self.image, self.desc, self._keep = key, image, d, (fields, upper, scratch)
+            self.layers = L
+        return self.desc, self.image
+
     def workspace(self, B, T, device):
         """One buffer per device, grown to the largest (B, T) seen; a replaced buffer goes back to the caching allocator, which
         orders its reuse after the work already queued on the stream that used it (the eval passes run on one stream)."""
-        need = _lib().pass_workspace_bytes(self.desc, B, T)
+        L = getattr(self, "layers", 1)
+        need = _lib().pass_workspace_bytes(self.desc, B, T) if L == 1 else _lib().pass_workspace_bytes_deep(self.desc, L, B, T)
         buf = self.ws.get(device)
         if buf is None or buf.numel() < need:
             buf = self.ws[device] = torch.empty(need, dtype=torch.uint8, device=device)
@@ -519,8 +550,9 @@ class GRU_RNN(nn.Module):
     def __init__(self, in_dim=39, out_dim=35, hidden_units=1024, hidden_layers=1, kernel_size=3, dilation_size=2,
                  do_prob=0, scale_in_flag=True, scale_out_flag=True, scale_in_out_flag=False):
         super(GRU_RNN, self).__init__()
-        if hidden_layers != 1:
-            raise NotImplementedError("hidden_layers=%d: the recipe uses a single GRU layer" % hidden_layers)
+        if int(hidden_layers) != hidden_layers or not 1 <= hidden_layers <= _cabi.MAX_LAYERS:
+            raise ValueError("hidden_layers must be an integer in 1..%d, got %r" % (_cabi.MAX_LAYERS, hidden_layers))
+        hidden_layers = int(hidden_layers)
         if scale_in_out_flag:
             raise NotImplementedError("scale_in_out_flag is dead code in this recipe")
         self.in_dim, self.out_dim = in_dim, out_dim
@@ -534,7 +566,11 @@ class GRU_RNN(nn.Module):
         self.tot_in_dim = in_dim * self.receptive_field + out_dim
         if do_prob > 0:
             self.conv_drop = nn.Dropout(p=do_prob)
-        self.gru = nn.GRU(self.tot_in_dim, hidden_units, hidden_layers, batch_first=True)  # parameter container
+        # parameter container (as the reference builds it, gru_vae.py:309-312: inter-layer dropout only for stacked layers)
+        if do_prob > 0 and hidden_layers > 1:
+            self.gru = nn.GRU(self.tot_in_dim, hidden_units, hidden_layers, dropout=do_prob, batch_first=True)
+        else:
+            self.gru = nn.GRU(self.tot_in_dim, hidden_units, hidden_layers, batch_first=True)
         if do_prob > 0:
             self.gru_drop = nn.Dropout(p=do_prob)
         self.out_1 = nn.Conv1d(hidden_units, out_dim, 1)
@@ -559,6 +595,11 @@ class GRU_RNN(nn.Module):
             raise NotImplementedError("forward flag outside the CycleVAE recipe (dead code in the reference)")
         # clamp of the second half of the outputs (gru_vae.py:408-417): clamp_vae wins over clamp_vae_laplace, as in the reference
         clamp = lat_dim if clamp_vae else ((lat_dim | _cabi.CLAMP_LAPLACE) if clamp_vae_laplace else -1)
+        if self.hidden_layers > 1 and ((self.do_prob > 0 and do and self.training) or (
+                torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())))):
+            raise NotImplementedError(
+                "hidden_layers=%d: train-mode / autograd passes of a stacked GRU (tape, reverse recurrence, the inter-layer dropout "
+                "of nn.GRU) are not implemented; eval passes run under model.eval() and torch.no_grad()" % self.hidden_layers)
         _need_cuda(x, "GRU_RNN.forward(x)")
         _lib()
         check_status()
@@ -568,6 +609,8 @@ class GRU_RNN(nn.Module):
         needs_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
         if needs_grad or p_drop > 0:
             return self._forward_train(x, y_in, h_in, p_drop, clamp)
+        if self.hidden_layers > 1:
+            return self._forward_deep(x, y_in, h_in, clamp)
         two_d = x.dim() == 2
         if two_d:
             x = x.unsqueeze(0)
@@ -591,6 +634,57 @@ class GRU_RNN(nn.Module):
         if two_d:
             trj = trj.squeeze(0)
         return trj, y_last, h_last
+
+
+def _forward_deep(self, x, y_in, h_in, clamp_lat_dim):
+    """Eval pass of a module with hidden_layers >= 2 (cvae_gru_rnn_forward_deep): h_in / the returned h are [L, B, H]."""
+    two_d = x.dim() == 2
+    if two_d:
+        x = x.unsqueeze(0)
+    x = x.to(torch.float32).contiguous()
+    B, T, Cin = x.shape
+    if Cin != self.in_dim:
+        raise ValueError("input has %d features, network expects %d" % (Cin, self.in_dim))
+    L, H, dev = self.hidden_layers, self.hidden_units, x.device
+    d, image = self._prep.get(self, dev)
+    ws = self._prep.workspace(B, T, dev)
+    y0 = y_in.to(torch.float32).reshape(B, self.out_dim).contiguous()
+    h0 = None
+    if h_in is not None:
+        if h_in.numel() != L * B * H:
+            raise ValueError("h_in has shape %s, a %d-layer GRU takes [%d, %d, %d]" % (tuple(h_in.shape), L, L, B, H))
+        h0 = h_in.to(torch.float32).reshape(L, B, H).contiguous()
+    trj = torch.empty(B, T, self.out_dim, dtype=torch.float32, device=dev)
+    y_last = torch.empty(B, 1, self.out_dim, dtype=torch.float32, device=dev)
+    h_last = torch.empty(L, B, H, dtype=torch.float32, device=dev)
+    lib = _lib()
+    pin = lib.pass_input((x.data_ptr(), Cin, Cin))
+    lib.gru_rnn_forward_deep(d, L, image.data_ptr(), pin, y0.data_ptr(), None if h0 is None else h0.data_ptr(), B, T, clamp_lat_dim,
+                             trj.data_ptr(), y_last.data_ptr(), h_last.data_ptr(), ws.data_ptr(), ws.numel(), _flags(), _stream())
+    if two_d:
+        trj = trj.squeeze(0)
+    return trj, y_last, h_last
+
+
+GRU_RNN._forward_deep = _forward_deep
+
+
+def run_cells(mod, d, image, pins, y_ins, T, clamp_lat_dim, trj_outs, ws, flags, stream):
+    """Independent single-row inputs (cells) through one net: ONE row-stacked pass for a one-layer module
+    (cvae_gru_rnn_forward_stacked); cell by cell through cvae_gru_rnn_forward_deep for hidden_layers >= 2, whose rows are the
+    same independent recurrences (ws: at least `cells_workspace_bytes`)."""
+    lib = _lib()
+    if mod.hidden_layers == 1:
+        lib.gru_rnn_forward_stacked(d, image.data_ptr(), pins, y_ins, 1, T, clamp_lat_dim, trj_outs, ws.data_ptr(), ws.numel(), flags, stream)
+        return
+    for pin, y, out in zip(pins, y_ins, trj_outs):
+        lib.gru_rnn_forward_deep(d, mod.hidden_layers, image.data_ptr(), pin, y, None, 1, T, clamp_lat_dim, out, None, None,
+                                 ws.data_ptr(), ws.numel(), flags, stream)
+
+
+def cells_workspace_bytes(mod, d, ncell, T):
+    lib = _lib()
+    return lib.pass_workspace_bytes(d, ncell, T) if mod.hidden_layers == 1 else lib.pass_workspace_bytes_deep(d, mod.hidden_layers, 1, T)
 
 
 def _forward_train(self, x, y_in, h_in, p_drop, clamp_lat_dim):
@@ -885,6 +979,9 @@ class CycleChain(object):
         continues from its own (y_last, h) of the previous window, as the reference's windowed loop does (train...:1299-1311).
         With return_state the result is (outputs, state); state = {"y_enc" [n_cyc,2,B,2L], "y_dec" [n_cyc,3,B,Cout],
         "h_enc" [n_cyc,2,B,H], "h_dec" [n_cyc,3,B,H]} (encoder slots lat, latcv; decoder slots rec, cv, reccyc)."""
+        if (self.enc.hidden_layers > 1 or self.dec.hidden_layers > 1) and (state is not None or return_state):
+            raise NotImplementedError("hidden_layers=%d/%d: the carry form of CycleChain (state / return_state) is single-layer"
+                                      % (self.enc.hidden_layers, self.dec.hidden_layers))
         _need_cuda(x, "CycleChain(x)")
         lib = _lib()
         check_status()
@@ -892,6 +989,9 @@ class CycleChain(object):
         f = lambda t: t.to(torch.float32).contiguous()
         x, cvx, code_src, code_trg = f(x), f(cvx), f(code_src), f(code_trg)
         B, T, _ = x.shape
+        if self.enc.hidden_layers > 1 or self.dec.hidden_layers > 1:
+            return self._call_deep(x, cvx, code_src, code_trg, f(y_in_enc.reshape(B, -1)), f(y_in_dec.reshape(B, -1)),
+                                   None if eps is None else f(eps), _draw_seed() if seed is None else seed, outputs)
         de, ie = self.enc.prepared(dev)
         dd, idd = self.dec.prepared(dev)
         need = lib.cycle_workspace_bytes(de, dd, B, T, self.n_cyc)
@@ -929,6 +1029,48 @@ class CycleChain(object):
                                 p("lat"), p("rec"), p("cv"), p("latcv"), p("reccyc"), self._ws.data_ptr(), self._ws.numel(),
                                 _flags(), _stream(), ptrs(s_in), ptrs(s_out))
         return (out, s_out) if return_state else out
+
+    def _call_deep(self, x, cvx, code_src, code_trg, ye, yd, eps, seed, outputs):
+        """The fresh chain with a stacked encoder and / or decoder: the passes of cvae_cycle_forward (cycle_forward_impl, same inputs,
+        same draw ids: pass k of cycle i draws with id 3i + k) issued one by one through cvae_gru_rnn_forward_deep, the latent draw
+        inside each decoder pass's prologue; rec and cv are two passes instead of one row-stacked one (rows are independent)."""
+        lib = _lib()
+        dev = x.device
+        B, T, Ce = x.shape
+        n, L, Co, enc, dec = self.n_cyc, self.lat_dim, self.dec.out_dim, self.enc, self.dec
+        stdim, ncode = cvx.shape[2], code_src.shape[2]
+        if enc.out_dim != 2 * L or dec.in_dim != ncode + L or enc.in_dim != stdim + Co or Ce != enc.in_dim:
+            raise ValueError("CycleChain: encoder %d -> %d, decoder %d -> %d do not fit lat_dim %d, stdim %d, %d code columns"
+                             % (enc.in_dim, enc.out_dim, dec.in_dim, Co, L, stdim, ncode))
+        de, ie = enc.prepared(dev)
+        dd, idd = dec.prepared(dev)
+        wse, wsd = enc._prep.workspace(B, T, dev), dec._prep.workspace(B, T, dev)
+        out = {k: torch.empty(n if outputs else 1, B, T, c, dtype=torch.float32, device=dev)
+               for k, c in (("lat", 2 * L), ("rec", Co), ("cv", Co), ("latcv", 2 * L), ("reccyc", Co))}
+        flags, st = _flags(), _stream()
+
+        def run(mod, d_, img, ws, pin, y, clamp, dst):
+            lib.gru_rnn_forward_deep(d_, mod.hidden_layers, img.data_ptr(), pin, y.data_ptr(), None, B, T, clamp, dst.data_ptr(), None,
+                                     None, ws.data_ptr(), ws.numel(), flags, st)
+
+        prev = None
+        for i in range(n):
+            o = {k: v[i if outputs else 0] for k, v in out.items()}
+            ep = lambda k: None if eps is None else eps[i, k].data_ptr()
+            if i == 0:
+                pin = lib.pass_input((x.data_ptr(), Ce, Ce))
+            else:
+                pin = lib.pass_input((x.data_ptr(), stdim, Ce), (prev.data_ptr(), Co, Co))
+            run(enc, de, ie, wse, pin, ye, L, o["lat"])
+            run(dec, dd, idd, wsd, lib.pass_input((code_src.data_ptr(), ncode, ncode), lat=o["lat"].data_ptr(), lat_dim=L, eps=ep(0),
+                                                  seed=seed, draw_id=3 * i), yd, -1, o["rec"])
+            run(dec, dd, idd, wsd, lib.pass_input((code_trg.data_ptr(), ncode, ncode), lat=o["lat"].data_ptr(), lat_dim=L, eps=ep(1),
+                                                  seed=seed, draw_id=3 * i + 1), yd, -1, o["cv"])
+            run(enc, de, ie, wse, lib.pass_input((cvx.data_ptr(), stdim, stdim), (o["cv"].data_ptr(), Co, Co)), ye, L, o["latcv"])
+            run(dec, dd, idd, wsd, lib.pass_input((code_src.data_ptr(), ncode, ncode), lat=o["latcv"].data_ptr(), lat_dim=L, eps=ep(2),
+                                                  seed=seed, draw_id=3 * i + 2), yd, -1, o["reccyc"])
+            prev = o["reccyc"]          # (read by the next cycle's first pass, rewritten by its last)
+        return out if outputs else {}
 
     def status(self):
         """Synchronises; [0] != 0 = a hand-off spin timed out somewhere since the last check."""

@@ -284,6 +284,10 @@ class Stage4Step(object):
         --force-dist: the RCCL path executes on a one-GPU box).  script_loss (fused=False only): form the loss with the training
         script's own per-utterance loop and its host read-backs (script_loss_loop) instead of the vectorised loss_terms."""
         import shard
+        for m in (enc, dec):
+            if getattr(m, "hidden_layers", 1) > 1:
+                raise NotImplementedError("hidden_layers=%d: training a stacked GRU (Stage4Step) is not implemented; the eval passes, "
+                                          "the fresh CycleChain and the stage-6 conversion are" % m.hidden_layers)
         self.script_loss = bool(script_loss)
         self.mods = {"enc": enc, "dec": dec}
         on_gpu = next(enc.parameters()).is_cuda

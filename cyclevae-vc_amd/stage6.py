@@ -113,12 +113,13 @@ def _encode_pairs(model_encoder, pairs, y_in_pp, lat_dim):
     de, ie = model_encoder.prepared(dev)
     ypp = f(y_in_pp.reshape(1, -1))
     lat = torch.empty(2 * N, T, 2 * L, dtype=torch.float32, device=dev)
-    ws = torch.empty(lib.pass_workspace_bytes(de, 2 * N, T), dtype=torch.uint8, device=dev)
+    ws = torch.empty(gru_vae.cells_workspace_bytes(model_encoder, de, 2 * N, T), dtype=torch.uint8, device=dev)
     pins = []
     for (a, b), (ta, tb) in zip(feats, lens):
         pins += [lib.pass_input((a.data_ptr(), Cin, Cin), frames=ta), lib.pass_input((b.data_ptr(), Cin, Cin), frames=tb)]
-    lib.gru_rnn_forward_stacked(de, ie.data_ptr(), pins, [ypp.data_ptr()] * (2 * N), 1, T, L,
-                                [lat[r].data_ptr() for r in range(2 * N)], ws.data_ptr(), ws.numel(), gru_vae._flags(), st)
+    # (hidden_layers >= 2: the same cells pass by pass, gru_vae.run_cells)
+    gru_vae.run_cells(model_encoder, de, ie, pins, [ypp.data_ptr()] * (2 * N), T, L, [lat[r].data_ptr() for r in range(2 * N)], ws,
+                      gru_vae._flags(), st)
     return {"N": N, "lens": lens, "T": T, "lat": lat, "dev": dev, "keep": (feats, ypp, ws)}
 
 
@@ -131,7 +132,7 @@ def _decode_pairs(model_decoder, enc, y_in_src, y_in_trg, lat_dim, n_smpl_dec, e
     f = lambda t: t.to(torch.float32).contiguous()
     st = torch.cuda.current_stream().cuda_stream
     dd, idd = model_decoder.prepared(dev)
-    ws = torch.empty(lib.pass_workspace_bytes(dd, 3 * N, T), dtype=torch.uint8, device=dev)
+    ws = torch.empty(gru_vae.cells_workspace_bytes(model_decoder, dd, 3 * N, T), dtype=torch.uint8, device=dev)
     codes = torch.tensor([[1.0, 0.0], [0.0, 1.0]], dtype=torch.float32, device=dev)     # src_code, trg_code (decode...:309-314)
 
     def pad_eps(e):
@@ -164,8 +165,7 @@ def _decode_pairs(model_decoder, enc, y_in_src, y_in_trg, lat_dim, n_smpl_dec, e
         d0 = 2 * n * (q if pair_ids is None else int(pair_ids[q]))
         pins += [cell(1, 2 * q, es, ta, d0), cell(0, 2 * q, es, ta, d0), cell(1, 2 * q + 1, et, tb, d0 + n)]
         yins += [yt.data_ptr(), ys.data_ptr(), yt.data_ptr()]
-    lib.gru_rnn_forward_stacked(dd, idd.data_ptr(), pins, yins, 1, T, -1, [out[r].data_ptr() for r in range(3 * N)],
-                                ws.data_ptr(), ws.numel(), gru_vae._flags(), st)
+    gru_vae.run_cells(model_decoder, dd, idd, pins, yins, T, -1, [out[r].data_ptr() for r in range(3 * N)], ws, gru_vae._flags(), st)
     return out, [(out[3 * q, :ta], out[3 * q + 1, :ta], out[3 * q + 2, :tb], lat[2 * q, :ta], lat[2 * q + 1, :tb])
                  for q, (ta, tb) in enumerate(lens)]
 
@@ -193,6 +193,9 @@ def convert_pairs(model_encoder, model_decoder, pairs, y_in_pp, y_in_src, y_in_t
     if window and len(pairs) != 1:
         raise ValueError("convert_pairs(window=...) runs ONE pair as a wavefront of windows, got %d pairs" % len(pairs))
     if window:
+        if model_encoder.hidden_layers > 1 or model_decoder.hidden_layers > 1:
+            raise NotImplementedError("hidden_layers=%d/%d: the windowed wavefront (window=...) carries single-layer states; convert "
+                                      "stacked networks without window" % (model_encoder.hidden_layers, model_decoder.hidden_layers))
         gru_vae._need_cuda(pairs[0][0], "convert_pairs(feat_src)")
         return _convert_pair_windowed(model_encoder, model_decoder, pairs[0], y_in_pp, y_in_src, y_in_trg, lat_dim, n_smpl_dec,
                                       None if eps is None else eps[0], seed, window)
@@ -433,7 +436,7 @@ def split_file_list(items, n_dev):
 
 def _net_config(m):
     """What a worker process needs to rebuild a GRU_RNN: constructor arguments and the state dict on the host."""
-    kw = dict(in_dim=m.in_dim, out_dim=m.out_dim, hidden_units=m.hidden_units, kernel_size=m.kernel_size,
+    kw = dict(in_dim=m.in_dim, out_dim=m.out_dim, hidden_units=m.hidden_units, hidden_layers=m.hidden_layers, kernel_size=m.kernel_size,
               dilation_size=m.dilation_size, do_prob=m.do_prob, scale_in_flag=m.scale_in_flag, scale_out_flag=m.scale_out_flag)
     return kw, {k: v.detach().cpu().numpy() for k, v in m.state_dict().items()}      # (numpy: a worker need not import torch to unpickle it)
 

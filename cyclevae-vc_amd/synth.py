@@ -87,12 +87,14 @@ def onehot_codes(B, T, src_is_first=True):
 
 
 def gru_rnn_state(name, in_dim, out_dim, hidden, scale_in=None, scale_out=None, bias_scale=0.0,
-                  kernel_size=3, seed=SEED):
+                  kernel_size=3, seed=SEED, hidden_layers=1):
     """state_dict (numpy float32) of one GRU_RNN with the reference's key names and shapes.
 
     scale_in / scale_out: optional (mu, sigma) pairs -> frozen (un)normalisation layers.
     bias_scale > 0 draws biases from U(+-bias_scale) instead of the reference's zero init, so parity
     tests exercise every bias path.
+    hidden_layers > 1 adds gru.*_l1 .. (nn.GRU(num_layers=...)) drawn from name keys of their own ("gru.wih_l1", ...), so
+    every tensor of the one-layer state -- and its SHA -- is the same for any hidden_layers.
     """
     ks = kernel_size
     c1, c2 = in_dim * ks, in_dim * ks * ks
@@ -116,6 +118,11 @@ def gru_rnn_state(name, in_dim, out_dim, hidden, scale_in=None, scale_out=None, 
     sd["gru.weight_hh_l0"] = xavier(name + "/gru.whh", (3 * hidden, hidden), seed)
     sd["gru.bias_ih_l0"] = bias("gru.bih", 3 * hidden)
     sd["gru.bias_hh_l0"] = bias("gru.bhh", 3 * hidden)
+    for l in range(1, hidden_layers):
+        sd["gru.weight_ih_l%d" % l] = xavier(name + "/gru.wih_l%d" % l, (3 * hidden, hidden), seed)
+        sd["gru.weight_hh_l%d" % l] = xavier(name + "/gru.whh_l%d" % l, (3 * hidden, hidden), seed)
+        sd["gru.bias_ih_l%d" % l] = bias("gru.bih_l%d" % l, 3 * hidden)
+        sd["gru.bias_hh_l%d" % l] = bias("gru.bhh_l%d" % l, 3 * hidden)
     sd["out_1.weight"] = xavier(name + "/out1.w", (out_dim, hidden, 1), seed)
     sd["out_1.bias"] = bias("out1.b", out_dim)
     if scale_out is not None:
@@ -129,17 +136,18 @@ class CycleVAEProblem(object):
     """One synthetic CycleVAE workload: encoder/decoder weights, a (B,T) feature window, codes, eps."""
 
     def __init__(self, B, T, in_dim=54, out_dim=50, lat_dim=32, hidden=1024, n_cyc=2, bias_scale=0.0,
-                 seed=SEED, tag="w"):
+                 seed=SEED, tag="w", hidden_layers=1):
         self.B, self.T = B, T
         self.in_dim, self.out_dim, self.lat_dim, self.hidden, self.n_cyc = in_dim, out_dim, lat_dim, hidden, n_cyc
+        self.hidden_layers = hidden_layers
         self.stdim = in_dim - out_dim
         mu, sg = feature_stats(tag + "/stats", in_dim, seed)
         self.mu, self.sigma = mu, sg
         mu_t, sg_t = mu[self.stdim:], sg[self.stdim:]
         self.enc = gru_rnn_state(tag + "/enc", in_dim, 2 * lat_dim, hidden, scale_in=(mu, sg),
-                                 bias_scale=bias_scale, seed=seed)
+                                 bias_scale=bias_scale, seed=seed, hidden_layers=hidden_layers)
         self.dec = gru_rnn_state(tag + "/dec", lat_dim + 2, out_dim, hidden, scale_out=(mu_t, sg_t),
-                                 bias_scale=bias_scale, seed=seed)
+                                 bias_scale=bias_scale, seed=seed, hidden_layers=hidden_layers)
         self.x = features(tag + "/x", B, T, mu, sg, seed=seed)
         self.cvx = features(tag + "/cvx", B, T, mu[:self.stdim], sg[:self.stdim], seed=seed)
         self.code_src, self.code_trg = onehot_codes(B, T)

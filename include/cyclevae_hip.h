@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CVAE_ABI_VERSION 6
+#define CVAE_ABI_VERSION 7
 
 /* Shape of one reference GRU_RNN (src/nets/gru_vae.py:282-320). */
 typedef struct cvae_net_desc {
@@ -282,6 +282,38 @@ int cvae_gru_rnn_forward_stacked_carry(cvae_ctx* ctx, const cvae_net_desc* d, co
                                        const float* const* y_in, const float* const* h_in, int B, int T, int clamp_lat_dim,
                                        float* const* trj_out, float* const* h_last, void* workspace, size_t workspace_bytes,
                                        int flags, void* stream);
+
+/*
+ * ABI 7 -- networks with n_layers >= 2 GRU layers (the reference's `hidden_layers`, gru_vae.py:282-320: nn.GRU(tot_in_dim, H,
+ * hidden_layers); "deep" here, because cvae_gru_rnn_forward_stacked above stacks ROWS).  Eval mode only: layer 0 reads
+ * [conv front-end ; y_{t-1}] through weight_ih_l0, layer l >= 1 reads h_{l-1,t} through weight_ih_l{l} [3H][H], y_t = out_1(h_{L-1,t}),
+ * no dropout between layers (gru_vae.py:376-394 with the module in eval mode).  `w` carries layer 0 and everything around the GRU
+ * exactly as for cvae_net_prepare; `upper[l-1]` the four tensors of layer l = 1 .. n_layers-1 (an array in HOST memory of device
+ * pointers).  The prepared image is the one-layer image of layer 0 (front-end fold, biases, projection) followed by per-layer
+ * recurrent images [W_hh_l | U_l], U_0 = W_ih_l0[:, 9C:] . out_1.w (the feedback fold, applied to the TOP layer's previous state),
+ * U_l = W_ih_l.  h_in / h_last are [n_layers][B][H] (what nn.GRU takes and returns) or NULL; everything else as in
+ * cvae_gru_rnn_forward, whose `flags` apply as far as they make sense: CVAE_FLAG_PERSISTENT (one launch for the whole L*T chain of
+ * sub-steps where the grid is resident), CVAE_FLAG_GENERIC_STEP (the any-H kernel even where the resident one exists),
+ * CVAE_FLAG_PROFILE (one bracket per recurrence LAUNCH).  Every product is exact fp32 arithmetic on either kernel.
+ * n_layers == 1: each of these entry points IS its one-layer counterpart (same image, same workspace, same kernels; `upper` unused).
+ * cvae_plan_pass_deep reports the recurrence a pass would take: 0 one launch per sub-step, 1 the any-H kernel as one launch,
+ * 2 the resident exact-operand kernel (H = 1024 or 64, n_layers * H/8 blocks resident); negative = error.
+ */
+typedef struct cvae_gru_layer {
+    const float* w_ih;  /* gru.weight_ih_l{l}  [3H, H]  */
+    const float* w_hh;  /* gru.weight_hh_l{l}  [3H, H]  */
+    const float* b_ih;  /* gru.bias_ih_l{l}    [3H]     */
+    const float* b_hh;  /* gru.bias_hh_l{l}    [3H]     */
+} cvae_gru_layer;
+size_t cvae_net_prepared_bytes_deep(cvae_ctx* ctx, const cvae_net_desc* d, int n_layers);
+size_t cvae_net_prepare_scratch_bytes_deep(cvae_ctx* ctx, const cvae_net_desc* d, int n_layers);
+int cvae_net_prepare_deep(cvae_ctx* ctx, const cvae_net_desc* d, int n_layers, const cvae_net_weights* w, const cvae_gru_layer* upper,
+                          void* prepared, size_t prepared_bytes, void* scratch, size_t scratch_bytes, void* stream);
+size_t cvae_pass_workspace_bytes_deep(cvae_ctx* ctx, const cvae_net_desc* d, int n_layers, int B, int T);
+int cvae_plan_pass_deep(cvae_ctx* ctx, const cvae_net_desc* d, int n_layers, int B, int T, int flags);
+int cvae_gru_rnn_forward_deep(cvae_ctx* ctx, const cvae_net_desc* d, int n_layers, const void* prepared, const cvae_pass_input* in,
+                              const float* y_in, const float* h_in, int B, int T, int clamp_lat_dim, float* trj_out, float* y_last,
+                              float* h_last, void* workspace, size_t workspace_bytes, int flags, void* stream);
 
 /*
  * sampling_vae_batch (gru_vae.py:85-98) on device: z[n,l] = lat[n,l] + exp(lat[n,L+l]/2) * eps[n,l],
