@@ -7,7 +7,7 @@ library is missing or its ABI version differs, loading raises.
 import ctypes as C
 import os
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 FLAG_PERSISTENT = 1
 FLAG_PROFILE = 2
 FLAG_GENERIC_STEP = 4
@@ -15,6 +15,8 @@ FLAG_STEP_TIMING = 8
 FLAG_HOISTED_FRONTEND = 32
 FLAG_SPLIT_F16 = 256
 FLAG_EXACT3 = 512
+STATUS_RANGE = 7        # CVAE_STATUS_RANGE: an operand of a limb-operand eval kernel was outside the window of its fp16 limbs (ABI 8)
+STATUS_RANGE_WORD = 3   # the status word that carries it (word 0: time-outs, status 5)
 CLAMP_LAPLACE = 1 << 30     # OR into a clamp_lat_dim argument: clamp_vae_laplace's floor (gru_vae.py:417) instead of ln(1e-6)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -76,6 +78,10 @@ class PassInput(C.Structure):
 
 class CvaeError(RuntimeError):
     pass
+
+
+class CvaeRangeError(CvaeError):
+    """STATUS_RANGE: the passes since the last check ran the limb-operand kernels on a value their fp16 limbs cannot carry."""
 
 
 class CycleState(C.Structure):
@@ -148,6 +154,8 @@ class CvaeLib(object):
             getattr(L, fn).argtypes = [C.POINTER(NetDesc)]
         L.cvae_net_prepare.restype = C.c_int
         L.cvae_net_prepare.argtypes = [C.POINTER(NetDesc), C.POINTER(NetWeights), _fp, C.c_size_t, _fp, C.c_size_t, _fp]
+        L.cvae_net_prepared_in_range.restype = C.c_int
+        L.cvae_net_prepared_in_range.argtypes = [C.POINTER(NetDesc), C.c_int, _fp, _fp]
         L.cvae_pass_workspace_bytes.restype = C.c_size_t
         L.cvae_pass_workspace_bytes.argtypes = [C.POINTER(NetDesc), C.c_int, C.c_int]
         L.cvae_gru_rnn_forward.restype = C.c_int
@@ -305,6 +313,14 @@ class CvaeLib(object):
         w = NetWeights(**{f: weight_ptrs.get(f) or None for f in WEIGHT_FIELDS})
         self._check(self.lib.cvae_net_prepare(C.byref(d), C.byref(w), prepared, prepared_bytes, scratch, scratch_bytes,
                                               stream or None), "cvae_net_prepare")
+
+    def net_prepared_in_range(self, d, n_layers, prepared, stream=0):
+        """True when the folded weights of a prepared image fit the fp16 limb images (ABI 8; synchronises `stream`).  The context
+        remembers a False by the image's address and runs that image's passes on the fp32-operand kernels."""
+        rc = self.lib.cvae_net_prepared_in_range(C.byref(d), n_layers, prepared, stream or None)
+        if rc < 0:
+            self._check(rc, "cvae_net_prepared_in_range")
+        return rc == 1
 
     def pass_workspace_bytes(self, d, B, T):
         n = self.lib.cvae_pass_workspace_bytes(C.byref(d), B, T)
@@ -600,4 +616,4 @@ EXPORTS = ("cvae_last_error_string", "cvae_abi_version", "cvae_ctx_create", "cva
            "cvae_kl_gauss_backward",
            "cvae_gv_postfilter", "cvae_mcd_aligned", "cvae_mc2e", "cvae_dtw_work_bytes", "cvae_dtw_org_to_trg",
            "cvae_net_prepared_bytes_deep", "cvae_net_prepare_scratch_bytes_deep", "cvae_net_prepare_deep", "cvae_pass_workspace_bytes_deep",
-           "cvae_plan_pass_deep", "cvae_gru_rnn_forward_deep")
+           "cvae_plan_pass_deep", "cvae_gru_rnn_forward_deep", "cvae_net_prepared_in_range")

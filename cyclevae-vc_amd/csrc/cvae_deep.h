@@ -38,7 +38,9 @@ __global__ void k_prep_deep_bias(const float* bih, const float* bhh, float* gbia
 
 // wrec[path][g][c][col][kk] of one layer for k_gru_steps_deep: col = a*4 + u, unit j = 4g + u, k = 16c + kk
 //   path 0 (operand h_{l,t-1}): a = 0: W_hr, 1: W_hz, 2: 0,   3: W_hn        path 1 (operand u): a = 0: U_r, 1: U_z, 2: U_n, 3: 0
-__global__ void k_prep_wrec_deep(const float* U, const float* whh, float* wrec, int H) {
+// These are the values the layer's limb image (k_prep_wrec_x3, shared with the training images) splits: one that image cannot
+// carry is flagged here (unfit: cvae_flag_unfit).
+__global__ void k_prep_wrec_deep(const float* U, const float* whh, float* wrec, int H, int* unfit) {
     const int nch = H >> 4;
     const long per = (long)(H >> 2) * nch * 256, idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx < 2 * per) {
@@ -54,13 +56,17 @@ __global__ void k_prep_wrec_deep(const float* U, const float* whh, float* wrec, 
             w = U[(long)(a * H + j) * H + k];
         }
         wrec[idx] = w;
+        cvae_flag_unfit(unfit, w);
     }
 }
 
 // slot 0 of every layer: fp32 (chunk-major) and, when hx is given, the limb triples k_gru_steps_deep3 exchanges
 // (layout of k_train_x3_slot0: 2560 B per (16-unit chunk, 32-row tile)); h_in [L][B][H] or null (zeros); rows >= B are zero
-__global__ void k_deep_slot0(const float* h_in, float* hb, long hb_ls, float* hx, long hx_ls, long mtot, int L, int B, int Bp, int H) {
+// range_word: null, or the word set to range_val when a state of the limb form leaves its range (ProParams::range_word)
+__global__ void k_deep_slot0(const float* h_in, float* hb, long hb_ls, float* hx, long hx_ls, long mtot, int L, int B, int Bp, int H,
+                             int* range_word, int range_val, float range_at) {
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    bool bad = false;
     if (idx < (long)L * Bp * H) {
         const int k = (int)(idx % H), r = (int)((idx / H) % Bp), l = (int)(idx / ((long)H * Bp));
         const float v = h_in && r < B ? h_in[((long)l * B + r) * H + k] : 0.0f;
@@ -69,6 +75,7 @@ __global__ void k_deep_slot0(const float* h_in, float* hb, long hb_ls, float* hx
             unsigned short l0, l1;
             unsigned char l2;
             cvae_split3_f16b8(v, l0, l1, l2);
+            bad = cvae_out_of_range(v, range_at);
             unsigned char* h8 = (unsigned char*)(hx + (long)l * hx_ls) + ((long)(k >> 4) * (mtot >> 5) + (r >> 5)) * 2560;
             const int kh = (k >> 3) & 1, rr = r & 31, e = k & 7;
             ((unsigned short*)(h8 + kh * 512 + rr * 16))[e] = l0;
@@ -76,6 +83,7 @@ __global__ void k_deep_slot0(const float* h_in, float* hb, long hb_ls, float* hx
             h8[2048 + kh * 256 + rr * 8 + e] = l2;
         }
     }
+    if (range_word && !cvae_block_all(!bad) && threadIdx.x == 0) *range_word = range_val;
 }
 
 struct DeepStepParams {

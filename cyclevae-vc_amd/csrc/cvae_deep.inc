@@ -100,6 +100,8 @@ int run_pass_deep(const Dims& m, const cvae_net_desc* d, int L, const float* P, 
     const float* PD = P + pl.total;
     const DeepPrep dl = deep_prep_layout(m, L);
     const DeepWork wl = deep_work_layout(m, L, B, T);
+    // an image whose weights do not fit the limb images (cvae_net_prepared_in_range) runs k_gru_steps_deep, on fp32 operands
+    if (image_known_unfit(P)) flags |= CVAE_FLAG_GENERIC_STEP;
     const DeepPlan pn = plan_deep_pass(m, L, B, T, flags);
     int* status = cx().status_sink ? cx().status_sink : (int*)ws;
     const int w_in = in->seg0.width + (in->lat ? in->lat_dim : in->seg1.width);
@@ -119,6 +121,9 @@ int run_pass_deep(const Dims& m, const cvae_net_desc* d, int L, const float* P, 
     float* hx = pn.path == DEEP_RESIDENT ? ws + wl.hx : nullptr;
     unsigned* hflags = (unsigned*)(ws + wl.flags);
     const float* h_top = h_in ? h_in + (long)(L - 1) * B * m.H : nullptr;
+    int* range_word = nullptr;      // where k_deep_slot0 reports a carried-in state the limb form cannot hold (range_params)
+    int range_val = 0;
+    float range_at = 0.0f;
     {   // the one-layer prologue: assemble + scale_in + padding, dy from the TOP layer's h_in (the feedback is out_1 of that state),
         // flags and status zeroed; its slot-0 role writes the top layer's buffer, k_deep_slot0 below fills every layer
         ProParams pp;
@@ -142,17 +147,21 @@ int run_pass_deep(const Dims& m, const cvae_net_desc* d, int L, const float* P, 
         pp.xnp = xnp; pp.hbuf = hb_top; pp.dy = dy;
         pp.zero_words = hflags; pp.nzero = L * (wl.Bp / 32) * (m.H / 8);
         pp.zero_status = (int*)ws;      // the pass's own status words; a status sink stays sticky (the caller clears it)
+        pp.zero_status_n = 8;
         pp.nA = B * wl.Tp;
         pp.nH = (int)nblk((long)wl.Bp * m.H, 1024);
         pp.nD = (int)nblk((long)B * m.Co, 64);
         pp.wyT = P + pl.wyT;
+        // (layer 0's input side is an fp32 GEMM: of the exchanged values only the carried-in states take the limb form, k_deep_slot0)
+        range_params(pp, (int*)ws, pn.path == DEEP_RESIDENT, true, P, pl);
+        range_word = pp.range_word; range_val = pp.range_val; range_at = pp.range_at;
         if (many_draws)
             hipLaunchKernelGGL((k_prologue), dim3(pp.nA + pp.nH + pp.nD + 1), dim3(256), (size_t)(m.C + 1024 + 256) * sizeof(float), st, pp);
         else
             hipLaunchKernelGGL((k_prologue), dim3(pp.nA + pp.nH + pp.nD + 1), dim3(64), m.C * sizeof(float), st, pp);
     }
     hipLaunchKernelGGL((k_deep_slot0), dim3(nblk((long)L * wl.Bp * m.H, 256)), dim3(256), 0, st, h_in, hb, wl.hb_ls, hx, wl.hx_ls,
-                       wl.mtot, L, B, wl.Bp, m.H);
+                       wl.mtot, L, B, wl.Bp, m.H, h_in && hx ? range_word : (int*)nullptr, range_val, range_at);
     {   // layer 0's input side for all frames: gx[b*Tp + t] = afold . xnp[b, t:t+R, :] + cfold, one GEMM over overlapping rows
         const int M = B * wl.Tp, N = m.H3;
         hipLaunchKernelGGL((k_gemm_nt<4, 4, 2, 2, false>), dim3(nblk(N, 128), nblk(M, 128)), dim3(256), 0, st, (const float*)xnp,
@@ -281,7 +290,7 @@ int cvae_net_prepare_deep(cvae_ctx* ctx, const cvae_net_desc* d, int n_layers, c
         const float* U = l == 0 ? PD + dl.ffold : upper[l - 1].w_ih;
         const float* whh = l == 0 ? w->w_hh : upper[l - 1].w_hh;
         hipLaunchKernelGGL((k_prep_wrec_deep), dim3(nblk(2L * (m.H / 4) * m.nch * 256, 256)), dim3(256), 0, st, U, whh,
-                           PD + dl.wrec + (long)l * dl.wrec_ls, m.H);
+                           PD + dl.wrec + (long)l * dl.wrec_ls, m.H, (int*)(P + pl.range));
         if (deep3_ok(m))
             hipLaunchKernelGGL((k_prep_wrec_x3), dim3(nblk((long)(m.H / 8) * 4 * 2 * (m.H / 64) * 512, 256)), dim3(256), 0, st, U, whh,
                                PD + dl.w3 + (long)l * dl.w3_ls, m.H, m.H / 64, 1.0f);

@@ -59,7 +59,8 @@ struct Step6Params {
 // wrec3[c][wave][s][m][lane][e]: the folded recurrent weights (wrec2, fp32) of unit octet c as fp16 triples in the operand
 // order of v_mfma_f32_32x32x16_f16: lane (col = lane & 31, kh = lane >> 5) holds k = 16*(wave*KPW + s) + 8 * kh + e
 // of column col = 8*g + u (g: r, z, n_in, n_h; unit j = 8c + u).
-__global__ void k_prep_wrec3(const float* wrec2, float* wrec3, int H, int KPW) {
+// (unfit: cvae_flag_unfit; k_prep_wrec3_l2b splits the same values)
+__global__ void k_prep_wrec3(const float* wrec2, float* wrec3, int H, int KPW, int* unfit) {
     const int nch = H >> 4, NB = H >> 3;
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;      // one thread per (c, wave, s, lane, e)
     if (idx < (long)NB * 4 * KPW * 512) {
@@ -71,6 +72,7 @@ __global__ void k_prep_wrec3(const float* wrec2, float* wrec3, int H, int KPW) {
         if (k < H) w = wrec2[((((long)(j >> 4) * 4 + g) * nch + (k >> 4)) * 16 + (j & 15)) * 16 + (k & 15)];
         unsigned short l0, l1, l2;
         cvae_split3_f16(w, l0, l1, l2);
+        cvae_flag_unfit(unfit, w);
         unsigned short* dst = (unsigned short*)wrec3 + ((((long)c * 4 + wave) * KPW + s) * 3) * 512 + lane * 8 + e;
         dst[0] = l0;
         dst[512] = l1;
@@ -99,7 +101,7 @@ __global__ void k_prep_wrec3_l2b(const float* wrec2, unsigned char* w2s, int H, 
 
 // afold3[c][wave][s][m][lane][e]: the folded front-end weights (afold [3H][Kfe], fp32) likewise: k = 16*(wave*KFW + s) +
 // 8 * kh + e, column 8*g + u of gate g < 3 (the n_h column group takes no input term: zeros); zero beyond Kfe.
-__global__ void k_prep_afold3l(const float* afold, float* afold3, int H, int Kfe, int KFW) {
+__global__ void k_prep_afold3l(const float* afold, float* afold3, int H, int Kfe, int KFW, int* unfit) {
     const int NB = H >> 3;
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx < (long)NB * 4 * KFW * 512) {
@@ -110,6 +112,7 @@ __global__ void k_prep_afold3l(const float* afold, float* afold3, int H, int Kfe
         const float w = (g < 3 && k < Kfe) ? afold[(long)(g * H + 8 * c + u) * Kfe + k] : 0.0f;
         unsigned short l0, l1, l2;
         cvae_split3_f16(w, l0, l1, l2);
+        cvae_flag_unfit(unfit, w);
         unsigned short* dst = (unsigned short*)afold3 + ((((long)c * 4 + wave) * KFW + s) * 3) * 512 + lane * 8 + e;
         dst[0] = l0;
         dst[512] = l1;
@@ -414,7 +417,7 @@ struct Out6Params {
 };
 
 // wo3[n][s][m][lane][e] from wo2 [Cop][H] (scale_out . out_1 or out_1; rows >= Cop are zero)
-__global__ void k_prep_wo3(const float* wo2, float* wo3, int H, int Cop, int NT) {
+__global__ void k_prep_wo3(const float* wo2, float* wo3, int H, int Cop, int NT, int* unfit) {
     const int nk = H >> 4;
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx < (long)NT * nk * 512) {
@@ -423,6 +426,7 @@ __global__ void k_prep_wo3(const float* wo2, float* wo3, int H, int Cop, int NT)
         const float w = col < Cop ? wo2[(long)col * H + k] : 0.0f;
         unsigned short l0, l1, l2;
         cvae_split3_f16(w, l0, l1, l2);
+        cvae_flag_unfit(unfit, w);
         unsigned short* dst = (unsigned short*)wo3 + (((long)n * nk + s) * 3) * 512 + lane * 8 + e;
         dst[0] = l0;
         dst[512] = l1;

@@ -240,13 +240,38 @@ struct ProParams {
     long xs_plane;       //   same [row][Tp][Cp] indexing as xnp (Cp % 8 == 0: 8 consecutive halves are one 16-byte operand)
     float* dy;           // [ncell*B][Co]: y_in - out_1(h_in)
     unsigned* zero_words;
-    int* zero_status;    // null, or the pass's 8 status words: cleared here instead of by a launch of their own in front of the prologue
+    int* zero_status;    // null, or the pass's status words: cleared here instead of by a launch of their own in front of the prologue
+    int zero_status_n;   // how many: 8 in a workspace (status + spare words), the 4 words of a status sink (cvae_set_status_sink: int32[4])
     unsigned* ll_counter;   // null, or the workspace's launch counter of k_gru_steps_ll: incremented here, read there as the tag nonce
     int nA, nH, nD;      // block ranges: [0,nA) assemble rows, [nA,nA+nH) slot-0 init, then dy, then gx0, last block zeroing
     int nG;              // 0, or blocks of the frame-0 feedback correction gx0 (only when no cell carries a state in: dy = y_in - out_1.b)
     float* gx0;          // [ncell*B][3H]: W_ih[:, R*C:] . dy -- what the recurrent kernel adds to the gates of frame 0 (else it forms
     const float* wyT;    //   the sums itself, cvae_t0_fix: 4 loads per channel and thread in front of its first step); wyT [Co][3H]
+    // Range guard of the limb operands (CVAE_STATUS_RANGE).  range_word: null (the pass builds no limb operand: nothing is checked),
+    // or the word a block that saw a value v with !(|v| < range_at) sets to range_val -- NaN and inf included; such a value's first
+    // fp16 limb is inf.  Never a word of the zero_status set below (this launch would clear and raise it in unordered blocks): the
+    // sink's word 3, which the host clears, or workspace word 20 with range_val = the call's serial number, which the zeroing
+    // block also leaves in range_epoch (word 21) -- a raise of an earlier call, or whatever the buffer held before, then differs
+    // from the epoch and cvae_workspace_status reports nothing.
+    int* range_word;
+    int* range_epoch;
+    int range_val;
+    float range_at;            // option exact_range_at
+    const int* image_unfit;    // the prepared image's own flag (a weight left the range of its limb image: cvae_flag_unfit)
 };
+#ifndef CVAE_STATUS_RANGE_WORD
+#define CVAE_STATUS_RANGE_WORD 3   // of the four status words the host sees (include/cyclevae_hip.h)
+#endif
+#define CVAE_WS_RANGE_WORD 20      // workspace words behind the barrier counter (8..15) and the launch counter (16)
+#define CVAE_WS_RANGE_EPOCH 21
+// largest finite half: from here on the first limb of every split (pair or triple, rounded or truncated) stops carrying the value
+#define CVAE_LIMB_MAX 65504.0f
+__device__ __forceinline__ bool cvae_out_of_range(float v, float bound) { return !(fabsf(v) < bound); }
+// prepare kernels: a folded weight that its limb image cannot carry marks the image (one word, read by cvae_net_prepared_in_range
+// and by every prologue on that image)
+__device__ __forceinline__ void cvae_flag_unfit(int* unfit, float w) {
+    if (cvae_out_of_range(w, CVAE_LIMB_MAX)) *unfit = 1;
+}
 static_assert(sizeof(ProParams) <= 4096, "ProParams is a kernel argument: 4 KiB at most");
 
 // Everything a pass needs before its GEMM, in one launch of 64-thread blocks (role by block range):
@@ -362,6 +387,7 @@ __global__ void k_prologue(ProParams p) {
         // thread = (channel q = tid % 64 (+ 64, ...), rows tid / 64 + 4 i): one scale_in weight load feeds eight rows' FMAs, the
         // rows' inputs are LDS broadcasts (a wave shares its row)
         const ProCell* const cells = p.cell;
+        bool bad = false;
         for (int q = tid & 63; q < p.Cp; q += 64) {
             float v[8];
             bool ok[8];
@@ -388,12 +414,14 @@ __global__ void k_prologue(ProParams p) {
                 unsigned short l0, l1;
                 unsigned char l2;
                 cvae_split3_f16b8(ok[i] ? v[i] : 0.0f, l0, l1, l2);
+                bad = bad || (ok[i] && cvae_out_of_range(v[i], p.range_at));
                 ((unsigned short*)pc)[r * 8 + (q & 7)] = l0;
                 ((unsigned short*)(pc + 512))[r * 8 + (q & 7)] = l1;
                 pc[1024 + r * 8 + (q & 7)] = l2;
             }
         }
-        __syncthreads();
+        const bool fits = cvae_block_all(!bad);      // (the block barrier in front of the copy-out)
+        if (!fits && p.range_word && tid == 0) *p.range_word = p.range_val;
         f32x4* dst = (f32x4*)((unsigned char*)p.xt + ((long)tile * Tp + tp) * np * 1280);
         for (int e = tid; e < np * 80; e += 256) dst[e] = ((const f32x4*)img)[e];
         return;
@@ -451,6 +479,7 @@ __global__ void k_prologue(ProParams p) {
         if (valid)
             for (int q = tid; q < p.C; q += 64) row[q] = cvae_input_value(p, c, b, t, q, emean);
         __syncthreads();
+        bool bad = false;
         for (int q = tid; q < p.Cp; q += 64) {
             float v = 0.0f;
             if (valid && q < p.C) {
@@ -468,8 +497,11 @@ __global__ void k_prologue(ProParams p) {
                 unsigned short* xh = (unsigned short*)p.xs + ((long)bb * Tp + tp) * p.Cp + q;
                 xh[0] = hi;
                 xh[p.xs_plane] = lo;
+                bad = bad || cvae_out_of_range(v, p.range_at);
             }
         }
+        // (these roles are one wave: 64 threads, or the first 64 of 256)
+        if (p.xs && p.range_word && !cvae_wave_all(!bad) && tid == 0) *p.range_word = p.range_val;
     } else if (blk < p.nA + p.nH) {
         const long base = (long)(blk - p.nA) * 1024;
         bool any_h = false;
@@ -497,6 +529,7 @@ __global__ void k_prologue(ProParams p) {
             }
             return;
         }
+        bool bad = false;
         for (int e = 0; e < 16; ++e) {
             const long idx = base + e * 64 + tid;
             if (idx < (long)p.Bp * p.H) {
@@ -507,6 +540,7 @@ __global__ void k_prologue(ProParams p) {
                     if (h_in) v = h_in[(long)(r % p.B) * p.H + 16 * ch + kk];
                 }
                 p.hbuf[((long)ch * p.mtot + r) * 16 + kk] = v;
+                bad = bad || cvae_out_of_range(v, p.range_at);
                 if (p.hx) {   // 2560 bytes per (chunk, tile): l0 [kh][32 rows][8 halves] | l1 likewise | l2 [kh][32 rows][8 bytes]
                     unsigned short l0, l1;
                     unsigned char l2;
@@ -526,6 +560,7 @@ __global__ void k_prologue(ProParams p) {
                 }
             }
         }
+        if (p.range_word && !cvae_wave_all(!bad) && tid == 0) *p.range_word = p.range_val;
     } else if (blk < p.nA + p.nH + p.nD) {
         const int idx = (blk - p.nA - p.nH) * 64 + tid;
         if (idx < p.ncell * p.B * p.Co) {
@@ -550,7 +585,11 @@ __global__ void k_prologue(ProParams p) {
         if (p.xt)
             for (int q = tid; q < p.nxt_slack; q += 64) ((unsigned short*)p.xt)[(long)(p.Bp >> 5) * Tp * (p.Cp >> 3) * 640 + q] = 0;
         for (int q = tid; q < p.nzero; q += 64) p.zero_words[q] = 0u;
-        if (p.zero_status && tid < 8) p.zero_status[tid] = 0;
+        if (p.zero_status && tid < p.zero_status_n && tid != CVAE_STATUS_RANGE_WORD) p.zero_status[tid] = 0;
+        if (tid == 0) {
+            if (p.range_epoch) *p.range_epoch = p.range_val;
+            if (p.range_word && p.image_unfit && *p.image_unfit) *p.range_word = p.range_val;
+        }
         if (p.ll_counter && tid == 0) *p.ll_counter += 1u;
     }
 }
@@ -1190,7 +1229,7 @@ __global__ __launch_bounds__(256, 1) void k_gru_steps_v4(Step3Params p) {
 // wrec_h[jg][a][c32][hl][lane][e]: the recurrent weights of wrec2 (B[k][col], col = tile a / unit lane&15) as fp16 pairs in
 // the operand order of v_mfma_f32_16x16x32_f16: lane (j = lane & 15, kq = lane >> 4) holds k = 32*c32 + 8*kq + e, e = 0..7;
 // hl = 0: hi halves, hl = 1: lo halves (x = hi + lo/2048, cvae_split_f16).
-__global__ void k_prep_wrec_h(const float* wrec2, float* wrec_h, int H) {
+__global__ void k_prep_wrec_h(const float* wrec2, float* wrec_h, int H, int* unfit) {
     const int nch = H >> 4, n32 = H >> 5;
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;      // one thread per (jg, a, c32, lane, e)
     if (idx < (long)nch * 4 * n32 * 64 * 8) {
@@ -1200,6 +1239,7 @@ __global__ void k_prep_wrec_h(const float* wrec2, float* wrec_h, int H) {
         const float w = wrec2[(((long)jg * 4 + a) * nch + (k >> 4)) * 256 + lr * 16 + (k & 15)];
         unsigned short hi, lo;
         cvae_split_f16(w, hi, lo);
+        cvae_flag_unfit(unfit, w);
         unsigned short* dst = (unsigned short*)wrec_h + ((((long)jg * 4 + a) * n32 + c32) * 2) * 512 + lane * 8 + e;
         dst[0] = hi;
         dst[512] = lo;
@@ -1209,7 +1249,7 @@ __global__ void k_prep_wrec_h(const float* wrec2, float* wrec_h, int H) {
 // afold_h[jg][wave][cf][a][hl][lane][e]: the folded front-end weights (afold [3H][Kfe]) as fp16 pairs in the operand order of
 // v_mfma_f32_16x16x32_f16 and as the exact LDS image of k_gru_steps_v5: wave w owns the 32-k chunks NF32*w .. NF32*w + NF32-1,
 // lane (col = lane & 15 -> unit 16*jg + col of gate a, kq = lane >> 4) holds k = 32*chunk + 8*kq + e; zero beyond Kfe.
-__global__ void k_prep_afold_h(const float* afold, float* afold_h, int H, int Kfe, int NF32) {
+__global__ void k_prep_afold_h(const float* afold, float* afold_h, int H, int Kfe, int NF32, int* unfit) {
     const int nch = H >> 4;
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;      // one thread per (jg, wave, cf, a, lane, e)
     if (idx < (long)nch * 4 * NF32 * 3 * 512) {
@@ -1220,6 +1260,7 @@ __global__ void k_prep_afold_h(const float* afold, float* afold_h, int H, int Kf
         const float w = k < Kfe ? afold[(long)(a * H + 16 * jg + lr) * Kfe + k] : 0.0f;
         unsigned short hi, lo;
         cvae_split_f16(w, hi, lo);
+        cvae_flag_unfit(unfit, w);
         unsigned short* dst = (unsigned short*)afold_h + (((((long)jg * 4 + wave) * NF32 + cf) * 3 + a) * 2) * 512 + lane * 8 + e;
         dst[0] = hi;
         dst[512] = lo;

@@ -31,7 +31,7 @@ thread_local char g_err[512] = "";
 // Tuning / diagnostic switches (cvae_set_option): the library reads NO environment variable.
 enum OptId {
     OPT_V6_LIMBS_H64, OPT_NO_LL, OPT_MAX_RT, OPT_LL_BACKOFF, OPT_EXP, OPT_OLD_OUTPROJ, OPT_GEMM_FORCE, OPT_GEMM_LOG, OPT_TRAIN_OLD_GEMM,
-    OPT_GEMM_TRACE, OPT_TRAIN_PER_STEP, OPT_TRAIN_PROF, OPT_TRAIN_BACKOFF, OPT_TRAIN_FP32_MFMA, OPT_TRAIN_BWD_PER_STEP, OPT_TRAIN_KERNEL, OPT_X3_TILE, OPT_BWD_OVERFLOW_AT, OPT_GEMM_MAX_SPLIT, OPT_BWD_KS, OPT_COOP_LAUNCH, OPT_V6_LIMBS_H2048, OPT_V6_W2S_H64, OPT_STEP_COL_TILES, OPT_T0_IN_KERNEL, OPT_TRAIN_PROFILE, OPT_TRAIN_XMAP, OPT_MASKS_ON_SIDE, OPT_V6_BACKOFF, OPT_TRAIN_BWD_BACKOFF, OPT_LL_ROW_PAD, OPT_GEMM_MIN_DEPTH, OPT_TRAIN_BWD_GEOM, OPT_BWD_W3_L1_H64, OPT_TRAIN_FWD_GEOM, OPT_TRAIN_FWD_BACKOFF, OPT_COUNT
+    OPT_GEMM_TRACE, OPT_TRAIN_PER_STEP, OPT_TRAIN_PROF, OPT_TRAIN_BACKOFF, OPT_TRAIN_FP32_MFMA, OPT_TRAIN_BWD_PER_STEP, OPT_TRAIN_KERNEL, OPT_X3_TILE, OPT_BWD_OVERFLOW_AT, OPT_GEMM_MAX_SPLIT, OPT_BWD_KS, OPT_COOP_LAUNCH, OPT_V6_LIMBS_H2048, OPT_V6_W2S_H64, OPT_STEP_COL_TILES, OPT_T0_IN_KERNEL, OPT_TRAIN_PROFILE, OPT_TRAIN_XMAP, OPT_MASKS_ON_SIDE, OPT_V6_BACKOFF, OPT_TRAIN_BWD_BACKOFF, OPT_LL_ROW_PAD, OPT_GEMM_MIN_DEPTH, OPT_TRAIN_BWD_GEOM, OPT_BWD_W3_L1_H64, OPT_TRAIN_FWD_GEOM, OPT_TRAIN_FWD_BACKOFF, OPT_EXACT_RANGE_AT, OPT_COUNT
 };
 struct OptEntry { const char* name; long dflt; };
 const OptEntry g_opt[OPT_COUNT] = {      // names and DEFAULTS (immutable); the values live in the context
@@ -71,6 +71,7 @@ const OptEntry g_opt[OPT_COUNT] = {      // names and DEFAULTS (immutable); the 
     {"bwd_w3_l1_h64", 0},         // 1: k_train_bwd_steps_w3 at H = 64 keeps the second limbs of two fragments per wave in LDS (what runs at H = 1024), for the emulator tests
     {"train_fwd_geom", -1},       // exact forward training recurrence: 1 = 16 units x 16-row tiles with the zero column tiles of [W_hh | F] dropped (k_train_fwd_steps_w3, round 6), 0 = the 8-unit kernels (k_train_fwd_steps_x3 / x3h); -1: the 16-unit form for passes of at least four 16-row tiles (64 rows: one tile per block behind a first-poll back-off, 128 rows: two tiles per block), else the 8-unit form
     {"train_fwd_backoff", -1},    // x 64 cycles before the first flag poll of a task of the exact forward training recurrences (16-row-tile kernels); -1: 24 when a block has ONE tile (nothing else covers the hand-off and early polls slow the publishes they wait for), 0 with two or more
+    {"exact_range_at", 65504},    // |x| from which an exchanged value (normalised input, carried-in state) of the limb-operand eval kernels raises CVAE_STATUS_RANGE: 65504 = the first limb overflows; 2048 = the third limb (a bf8 byte) stops being exact
 };
 
 // hipEvent pairs recorded around the recurrent kernel when CVAE_FLAG_PROFILE is set
@@ -110,6 +111,10 @@ struct cvae_ctx {
     // without bound); the oldest entries go when the table is full
     std::map<const void*, std::pair<int, unsigned long>> train_var;
     unsigned long train_var_tick = 0;
+    // Range guard of the eval passes: images cvae_net_prepared_in_range found unfit for the limb kernels (by address; their passes
+    // run the fp32-operand kernels), and the serial number an entry point's passes raise workspace word 20 with (ProParams)
+    std::map<const void*, bool> image_unfit;
+    int range_serial = 0;
     std::atomic<unsigned> ll_train_launch{1u};                       // tag nonce of the word-exchange training kernels (cvae_train_ll.h)
 };
 
@@ -205,7 +210,7 @@ inline bool exact3_ok(const Dims& m) {
 // prepared image: offsets in floats, every block 64-float aligned
 struct Prep {
     long afold, afold3, afold_h, afold_t, cfold, wrec, wrec2, wrec_h, wrec_t, wrec_l2b, bhn, wyT, wo, bo, wo2, bo2, wo3, sin_w, sin_b, sout_w,
-        sout_b, total;
+        sout_b, range, total;
 };
 
 Prep prep_layout(const Dims& m, bool sin, bool sout) {
@@ -235,6 +240,7 @@ Prep prep_layout(const Dims& m, bool sin, bool sout) {
     p.sin_b = sin ? take(m.C) : -1;
     p.sout_w = sout ? take((long)m.Co * m.Co) : -1;
     p.sout_b = sout ? take(m.Co) : -1;
+    p.range = take(64);      // word 0: a folded weight does not fit its limb image (cvae_flag_unfit); the deep part of an image shares it
     p.total = o;
     return p;
 }
@@ -336,6 +342,32 @@ int cu_count() {
     return n;
 }
 
+// Range guard (CVAE_STATUS_RANGE): where a pass's prologue reports an operand the limb form cannot carry.  limbs: the pass builds
+// limb operands; new_call: first pass of an entry point (a new serial number; the workspace epoch is written).
+inline bool image_known_unfit(const float* P) {
+    auto it = cx().image_unfit.find((const void*)P);
+    return it != cx().image_unfit.end() && it->second;
+}
+inline void range_params(ProParams& pp, int* ws_status, bool limbs, bool new_call, const float* P, const Prep& pl) {
+    if (new_call) {
+        cx().range_serial += 1;
+        if (cx().range_serial <= 0) cx().range_serial = 1;
+    }
+    long at = opt(OPT_EXACT_RANGE_AT);
+    at = at < 1 ? 1 : (at > 65504 ? 65504 : at);
+    pp.range_at = (float)at;
+    pp.image_unfit = (const int*)(P + pl.range);
+    if (cx().status_sink) {      // sticky, cleared by the host
+        pp.range_word = limbs ? cx().status_sink + CVAE_STATUS_RANGE_WORD : nullptr;
+        pp.range_epoch = nullptr;
+        pp.range_val = CVAE_STATUS_RANGE;
+    } else {
+        pp.range_word = limbs ? ws_status + CVAE_WS_RANGE_WORD : nullptr;
+        pp.range_epoch = new_call ? ws_status + CVAE_WS_RANGE_EPOCH : nullptr;
+        pp.range_val = cx().range_serial;
+    }
+}
+
 // One cell of a pass: passes that share weights and have no mutual dependence (rec || cv of a cycle) run as ONE
 // pass whose batch is the cells' batches stacked; the recurrence then has extra independent row tiles to interleave.
 struct Cell {
@@ -352,6 +384,10 @@ int run_pass(const Dims& m, const cvae_net_desc* d, const float* P, const Cell* 
     const Prep pl = prep_layout(m, d->has_scale_in != 0, d->has_scale_out != 0);
     const int Brows = ncell * B;
     const Work wl = work_layout(m, Brows, T);
+    int* const ws_status = status;
+    // an image whose folded weights do not fit the limb images (cvae_net_prepared_in_range) runs on the fp32-operand kernels
+    const bool unfit = image_known_unfit(P);
+    if (unfit) flags &= ~CVAE_FLAG_SPLIT_F16;
     if (cx().status_sink) status = cx().status_sink;    // host-visible sticky word: a time-out is seen without reading the workspace back
     for (int c = 0; c < ncell; ++c) {
         const cvae_pass_input* in = cells[c].in;
@@ -369,13 +405,20 @@ int run_pass(const Dims& m, const cvae_net_desc* d, const float* P, const Cell* 
     if (ncell > CVAE_MAX_CELLS) return fail(-1, "at most %d stacked cells per pass", CVAE_MAX_CELLS);
     const int cus = cu_count();
     // k_gru_steps_v6 (exact fp32 operands as fp16 triples): 32-row tiles, 8-unit octets, every block resident
-    const bool use_exact3 = (flags & CVAE_FLAG_PERSISTENT) && (flags & CVAE_FLAG_EXACT3) && !(flags & CVAE_FLAG_GENERIC_STEP) &&
+    const bool use_exact3 = !unfit && (flags & CVAE_FLAG_PERSISTENT) && (flags & CVAE_FLAG_EXACT3) && !(flags & CVAE_FLAG_GENERIC_STEP) &&
                             !(flags & CVAE_FLAG_HOISTED_FRONTEND) && T > 1 && exact3_ok(m) && wl.Bp % 32 == 0 &&
                             cus >= m.H / 8 && (long)m.nch * wl.mtot * 80 < (1L << 31);
 
     // k_gru_steps_ll (at most three rows: a step is one store + one polled load per unit, plain fp32 FMAs): every block resident
     const bool use_ll = (flags & CVAE_FLAG_PERSISTENT) && (flags & CVAE_FLAG_EXACT3) && !(flags & CVAE_FLAG_GENERIC_STEP) && T > 1 &&
                         Brows <= 3 && T < 65536 && m.H % 64 == 0 && m.H <= 1024 && cus >= m.H / 4 && !opt(OPT_NO_LL);
+
+    // k_gru_steps_v5 (fp16 pairs): the geometries it is built for, when neither kernel above takes the pass (the same conditions
+    // as at its launch below; the range guard checks the pair copies only when this kernel will read them)
+    const bool use_split5 = !use_exact3 && !use_ll && (flags & CVAE_FLAG_PERSISTENT) && T > 1 && (flags & CVAE_FLAG_SPLIT_F16) &&
+                            !(flags & CVAE_FLAG_GENERIC_STEP) && !(flags & CVAE_FLAG_HOISTED_FRONTEND) &&
+                            (long)m.nch * wl.mtot * 64 < (1L << 31) && cus >= m.nch &&
+                            ((m.H == 1024 && (m.KFW == 8 || m.KFW == 6)) || (m.H == 64 && (m.KFW == 2 || m.KFW == 1)));
 
     bool gx0_ready = false;
     {   // one prologue launch: assemble + scale_in + padding, slot-0 init, frame-0 feedback correction, zeroing
@@ -423,6 +466,7 @@ int run_pass(const Dims& m, const cvae_net_desc* d, const float* P, const Cell* 
         // bar (8 words) ... flags are not adjacent: zero the flags here, the barrier words with the status block
         pp.zero_words = hflags; pp.nzero = nrt * m.nch;
         pp.zero_status = clear_status ? status : nullptr;     // (the recurrent kernel, the first writer of these words, runs behind the prologue)
+        pp.zero_status_n = cx().status_sink ? 4 : 8;          // (a sink is int32[4]: eight words ran over the end of the caller's buffer)
         pp.ll_counter = use_ll ? (unsigned*)(ws + wl.status) + 16 : nullptr;
         pp.nA = (use_exact3 ? wl.Bp / 32 : Brows) * wl.Tp;      // v6: one block per (32-row tile, padded frame)
         pp.nH = (int)nblk((long)wl.Bp * m.H, 1024);
@@ -432,6 +476,9 @@ int run_pass(const Dims& m, const cvae_net_desc* d, const float* P, const Cell* 
         gx0_ready = use_exact3 && !any_h_in && m.H3 % 4 == 0 && !opt(OPT_T0_IN_KERNEL);
         pp.nG = gx0_ready ? (int)nblk((long)Brows * m.H3 / 4, 256) : 0;
         pp.gx0 = ws + wl.gx0; pp.wyT = P + pl.wyT;
+        // (the pair copies are written whenever SPLIT_F16 is set, but only k_gru_steps_v5 reads them: a pass that ends up on
+        // k_gru_steps_ll or on an fp32-operand kernel has nothing to report)
+        range_params(pp, ws_status, use_exact3 || use_split5, clear_status, P, pl);
         if (use_exact3)
             hipLaunchKernelGGL((k_prologue), dim3(pp.nA + pp.nH + pp.nD + pp.nG + 1), dim3(256),
                                (size_t)32 * (m.C + 1) * sizeof(float) + (size_t)(m.Cp / 8) * 1280 + (size_t)32 * pp.L * sizeof(float), st, pp);
@@ -679,6 +726,7 @@ cvae_ctx* cvae_ctx_create(void) {
         return nullptr;
     }
     for (int i = 0; i < OPT_COUNT; ++i) c->opt[i] = g_opt[i].dflt;
+    c->range_serial = (int)(((uintptr_t)c >> 6) & 0x3fffffff);      // (two contexts do not count the calls on a workspace alike)
     return c;
 }
 
@@ -797,6 +845,8 @@ int cvae_net_prepare(cvae_ctx* ctx, const cvae_net_desc* d, const cvae_net_weigh
     float* P = (float*)prepared;
     double* mfull = (double*)scratch;
     double* bprime = mfull + (size_t)m.c2 * m.R * m.C;
+    int* unfit = (int*)(P + pl.range);      // raised by the kernels that write limb images (cleared with the image, just below)
+    cx().image_unfit.erase((const void*)P);
 
     CVAE_HIP_OK(hipMemsetAsync(P, 0, (size_t)pl.total * sizeof(float), st));
     hipLaunchKernelGGL((k_prep_mfull), dim3(nblk((long)m.c2 * m.R * m.C, 256)), dim3(256), 0, st, w->conv0_w, w->conv1_w,
@@ -806,7 +856,7 @@ int cvae_net_prepare(cvae_ctx* ctx, const cvae_net_desc* d, const cvae_net_weigh
     hipLaunchKernelGGL((k_prep_afold), dim3(nblk((long)m.H3 * m.Kfe, 256)), dim3(256), 0, st, w->w_ih,
                        (const double*)mfull, P + pl.afold, m.C, m.Cp, m.ks, m.tot, m.Kfe, m.H3);
     hipLaunchKernelGGL((k_prep_afold_h), dim3(nblk((long)m.nch * 4 * ((m.KFW + 1) / 2) * 3 * 512, 256)), dim3(256), 0, st,
-                       (const float*)(P + pl.afold), P + pl.afold_h, m.H, m.Kfe, (m.KFW + 1) / 2);
+                       (const float*)(P + pl.afold), P + pl.afold_h, m.H, m.Kfe, (m.KFW + 1) / 2, unfit);
     hipLaunchKernelGGL((k_prep_afold3), dim3(nblk((long)m.nch * 4 * m.KFW * 3 * 256, 256)), dim3(256), 0, st,
                        (const float*)(P + pl.afold), P + pl.afold3, m.H, m.Kfe, m.KFW);
     hipLaunchKernelGGL((k_prep_cfold), dim3(nblk(m.H3, 128)), dim3(128), 0, st, w->w_ih, w->b_ih, w->b_hh, w->out_b,
@@ -820,12 +870,12 @@ int cvae_net_prepare(cvae_ctx* ctx, const cvae_net_desc* d, const cvae_net_weigh
                        w->out_w, P + pl.wrec2, m.c2, m.Co, m.tot, m.H);
     if (m.H % 32 == 0)
         hipLaunchKernelGGL((k_prep_wrec_h), dim3(nblk((long)m.nch * 4 * (m.H / 32) * 512, 256)), dim3(256), 0, st,
-                           (const float*)(P + pl.wrec2), P + pl.wrec_h, m.H);
+                           (const float*)(P + pl.wrec2), P + pl.wrec_h, m.H, unfit);
     if (exact3_ok(m)) {
         hipLaunchKernelGGL((k_prep_wrec3), dim3(nblk((long)(m.H / 8) * 4 * exact3_kpw(m) * 512, 256)), dim3(256), 0, st,
-                           (const float*)(P + pl.wrec2), P + pl.wrec_t, m.H, exact3_kpw(m));
+                           (const float*)(P + pl.wrec2), P + pl.wrec_t, m.H, exact3_kpw(m), unfit);
         hipLaunchKernelGGL((k_prep_afold3l), dim3(nblk((long)(m.H / 8) * 4 * m.KFW * 512, 256)), dim3(256), 0, st,
-                           (const float*)(P + pl.afold), P + pl.afold_t, m.H, m.Kfe, m.KFW);
+                           (const float*)(P + pl.afold), P + pl.afold_t, m.H, m.Kfe, m.KFW, unfit);
         hipLaunchKernelGGL((k_prep_wrec3_l2b), dim3(nblk((long)(m.H / 8) * 4 * exact3_kpw(m) * 512, 256)), dim3(256), 0, st,
                            (const float*)(P + pl.wrec2), (unsigned char*)(P + pl.wrec_l2b), m.H, exact3_kpw(m));
     }
@@ -839,7 +889,7 @@ int cvae_net_prepare(cvae_ctx* ctx, const cvae_net_desc* d, const cvae_net_weigh
                        d->has_scale_out ? w->scale_out_b : (const float*)nullptr, P + pl.wo2, P + pl.bo2, m.Co, m.Cop, m.H);
     if (exact3_ok(m))
         hipLaunchKernelGGL((k_prep_wo3), dim3(nblk((long)((m.Cop + 31) / 32) * (m.H / 16) * 512, 256)), dim3(256), 0, st,
-                           (const float*)(P + pl.wo2), P + pl.wo3, m.H, m.Cop, (m.Cop + 31) / 32);
+                           (const float*)(P + pl.wo2), P + pl.wo3, m.H, m.Cop, (m.Cop + 31) / 32, unfit);
     if (d->has_scale_in) {
         copy2d(P + pl.sin_w, m.C, w->scale_in_w, m.C, m.C, m.C);
         copy2d(P + pl.sin_b, m.C, w->scale_in_b, m.C, 1, m.C);
@@ -1167,9 +1217,28 @@ int cvae_train_profile_collect(cvae_ctx* ctx, double total_ms[4], int launches[4
 int cvae_workspace_status(cvae_ctx* ctx, const void* workspace, int32_t status_out[4], void* stream) {
     CVAE_ENTER(ctx);
     if (!workspace || !status_out) return fail(-1, "null argument");
-    CVAE_HIP_OK(hipMemcpyAsync(status_out, workspace, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    int32_t w[CVAE_WS_RANGE_EPOCH + 1];
+    CVAE_HIP_OK(hipMemcpyAsync(w, workspace, sizeof(w), hipMemcpyDeviceToHost, (hipStream_t)stream));
     CVAE_HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+    for (int i = 0; i < 4; ++i) status_out[i] = w[i];
+    // the range word of the workspace holds the serial number of the call that raised it: only the latest call's counts (ProParams)
+    status_out[CVAE_STATUS_RANGE_WORD] = w[CVAE_WS_RANGE_WORD] != 0 && w[CVAE_WS_RANGE_WORD] == w[CVAE_WS_RANGE_EPOCH] ? CVAE_STATUS_RANGE : 0;
     return 0;
+}
+
+int cvae_net_prepared_in_range(cvae_ctx* ctx, const cvae_net_desc* d, int n_layers, const void* prepared, void* stream) {
+    CVAE_ENTER(ctx);
+    Dims m;
+    if (int rc = make_dims(d, &m)) return rc;
+    if (n_layers < 1 || !prepared) return fail(-1, "bad argument");
+    const Prep pl = prep_layout(m, d->has_scale_in != 0, d->has_scale_out != 0);
+    int32_t flag = 0;
+    CVAE_HIP_OK(hipMemcpyAsync(&flag, (const float*)prepared + pl.range, sizeof(flag), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    CVAE_HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+    if (cx().image_unfit.size() >= 4096) cx().image_unfit.clear();      // (addresses of images long gone)
+    if (flag != 0) cx().image_unfit[prepared] = true;
+    else cx().image_unfit.erase(prepared);
+    return flag != 0 ? 0 : 1;
 }
 
 }  // extern "C"

@@ -66,8 +66,17 @@ def check_status(sync=False, overflow_ok=False):
     code = int(sink[0])
     if code == 5 and overflow_ok:
         return
+    if code == 0 and int(sink[_cabi.STATUS_RANGE_WORD]) == _cabi.STATUS_RANGE:
+        # a word of its own (ABI 8): neither masks nor is masked by the codes of word 0, which are raised first
+        sink[_cabi.STATUS_RANGE_WORD] = 0
+        raise _cabi.CvaeRangeError(
+            "an eval pass on the exact-operand kernels was given a value its fp16 limbs cannot carry (status %d: a normalised "
+            "input or carried-in state with |v| >= the library option exact_range_at, or NaN / inf -- typically a huge 1/sigma in "
+            "scale_in): the results of the passes enqueued since the previous check are NaN / inf where the reference is finite.  "
+            "Run them on the fp32-operand kernels: gru_vae.set_kernel(\"fp32\"), or gru_vae.set_range_policy(\"retry\"), which "
+            "does that by itself for the calls that need it" % _cabi.STATUS_RANGE)
     if code != 0:
-        sink.zero_()
+        sink[:_cabi.STATUS_RANGE_WORD].zero_()
         if code == 5:
             raise _cabi.CvaeError("a gate gradient of the persistent reverse recurrence left the range of its limb exchange (|v| >= "
                                   "~234, status 5): the gradients of this backward are invalid; run it again with the library option "
@@ -178,11 +187,55 @@ def set_kernel(kernel=None, persistent=None, hoisted_frontend=None):
     return prev
 
 
+_range_policy = "raise"    # what the eval entry points do about STATUS_RANGE: set_range_policy()
+_range_fallback = 0        # > 0 while a call is being repeated on the fp32-operand kernels (_with_range_retry)
+
+
+def set_range_policy(policy):
+    """What the eval entry points (GRU_RNN.forward without autograd, CycleChain, stage6.convert_*) do when a pass on the
+    exact-operand kernels meets a value outside the window of its fp16 limbs (status 7):
+         raise (default)  nothing is added to any call; the NEXT check_status() -- every entry point makes one before it enqueues --
+                          raises CvaeRangeError, as a hand-off time-out is reported
+         retry            every such call waits for its own work (one stream synchronisation per call) and, if the status was
+                          raised, runs again on the fp32-operand kernels and returns that result, which is finite wherever the
+                          reference's is: the choice for offline conversion (stage 6), where a call is milliseconds long
+    Images whose WEIGHTS leave the range run the fp32-operand kernels under either policy.  Training passes are not concerned
+    (their normalised input goes through fp32 GEMMs and the state is bounded).  Returns the previous policy."""
+    global _range_policy
+    if policy not in ("raise", "retry"):
+        raise ValueError("range policy must be raise or retry, got %r" % (policy,))
+    prev, _range_policy = _range_policy, policy
+    return prev
+
+
+def _with_range_retry(fn):
+    """fn() enqueues eval passes behind the current stream and returns their result: run it under the range policy."""
+    global _range_fallback
+    sink = _sink()
+    if _range_policy != "retry" or _range_fallback or _status_owned or sink is None:
+        return fn()
+    out = fn()
+    torch.cuda.current_stream().synchronize()
+    if int(sink[_cabi.STATUS_RANGE_WORD]) != _cabi.STATUS_RANGE:
+        return out
+    sink[_cabi.STATUS_RANGE_WORD] = 0
+    _range_fallback += 1
+    try:
+        return fn()
+    finally:
+        _range_fallback -= 1
+
+
+def _deep_flags(f):
+    """Flags of a pass of a stacked module: its fp32-operand recurrence is the any-H kernel (k_gru_steps_deep)."""
+    return f | _cabi.FLAG_GENERIC_STEP if _range_fallback else f
+
+
 def _flags():
     f = _cabi.FLAG_PERSISTENT if _persistent else 0
     if _hoisted_frontend:
         f |= _cabi.FLAG_HOISTED_FRONTEND
-    kern = _force_kernel or "exact3"
+    kern = "fp32" if _range_fallback else (_force_kernel or "exact3")
     if kern not in ("exact3", "split2", "fp32"):
         raise ValueError("kernel must be exact3, split2 or fp32, got %r" % (kern,))
     if kern == "exact3":
@@ -277,6 +330,9 @@ class _Prepared(object):
             scratch = torch.empty(lib.prepare_scratch_bytes(d), dtype=torch.uint8, device=device)
             lib.net_prepare(d, {f: t.data_ptr() for f, t in fields.items()}, image.data_ptr(), image.numel(),
                             scratch.data_ptr(), scratch.numel(), _stream())
+            # once per build (synchronises): an image whose folded weights leave the fp16 range is run on the fp32-operand kernels
+            # from the start -- the library context remembers the answer by the image's address
+            self.in_range = lib.net_prepared_in_range(d, 1, image.data_ptr(), _stream())
             self.key, self.image, self.desc, self._keep = key, image, d, (fields, scratch)
         return self.desc, self.image
 
@@ -299,6 +355,7 @@ class _Prepared(object):
             scratch = torch.empty(lib.prepare_scratch_bytes_deep(d, L), dtype=torch.uint8, device=device)
             lib.net_prepare_deep(d, L, {f: t.data_ptr() for f, t in fields.items()}, [tuple(t.data_ptr() for t in ts) for ts in upper],
                                  image.data_ptr(), image.numel(), scratch.data_ptr(), scratch.numel(), _stream())
+            self.in_range = lib.net_prepared_in_range(d, L, image.data_ptr(), _stream())
             self.key, self.image, self.desc, self._keep = key, image, d, (fields, upper, scratch)
             self.layers = L
         return self.desc, self.image
@@ -610,7 +667,10 @@ class GRU_RNN(nn.Module):
         if needs_grad or p_drop > 0:
             return self._forward_train(x, y_in, h_in, p_drop, clamp)
         if self.hidden_layers > 1:
-            return self._forward_deep(x, y_in, h_in, clamp)
+            return _with_range_retry(lambda: self._forward_deep(x, y_in, h_in, clamp))
+        return _with_range_retry(lambda: self._forward_eval(x, y_in, h_in, clamp))
+
+    def _forward_eval(self, x, y_in, h_in, clamp):
         two_d = x.dim() == 2
         if two_d:
             x = x.unsqueeze(0)
@@ -660,7 +720,8 @@ def _forward_deep(self, x, y_in, h_in, clamp_lat_dim):
     lib = _lib()
     pin = lib.pass_input((x.data_ptr(), Cin, Cin))
     lib.gru_rnn_forward_deep(d, L, image.data_ptr(), pin, y0.data_ptr(), None if h0 is None else h0.data_ptr(), B, T, clamp_lat_dim,
-                             trj.data_ptr(), y_last.data_ptr(), h_last.data_ptr(), ws.data_ptr(), ws.numel(), _flags(), _stream())
+                             trj.data_ptr(), y_last.data_ptr(), h_last.data_ptr(), ws.data_ptr(), ws.numel(), _deep_flags(_flags()),
+                             _stream())
     if two_d:
         trj = trj.squeeze(0)
     return trj, y_last, h_last
@@ -679,7 +740,7 @@ def run_cells(mod, d, image, pins, y_ins, T, clamp_lat_dim, trj_outs, ws, flags,
         return
     for pin, y, out in zip(pins, y_ins, trj_outs):
         lib.gru_rnn_forward_deep(d, mod.hidden_layers, image.data_ptr(), pin, y, None, 1, T, clamp_lat_dim, out, None, None,
-                                 ws.data_ptr(), ws.numel(), flags, stream)
+                                 ws.data_ptr(), ws.numel(), _deep_flags(flags), stream)
 
 
 def cells_workspace_bytes(mod, d, ncell, T):
@@ -978,7 +1039,16 @@ class CycleChain(object):
         state: None (fresh window) or the dict a previous call returned with return_state=True: every pass of every cycle then
         continues from its own (y_last, h) of the previous window, as the reference's windowed loop does (train...:1299-1311).
         With return_state the result is (outputs, state); state = {"y_enc" [n_cyc,2,B,2L], "y_dec" [n_cyc,3,B,Cout],
-        "h_enc" [n_cyc,2,B,H], "h_dec" [n_cyc,3,B,H]} (encoder slots lat, latcv; decoder slots rec, cv, reccyc)."""
+        "h_enc" [n_cyc,2,B,H], "h_dec" [n_cyc,3,B,H]} (encoder slots lat, latcv; decoder slots rec, cv, reccyc).
+        Runs under the range policy (set_range_policy)."""
+        if seed is None and eps is None and _range_policy == "retry":
+            seed = _draw_seed()      # (a repeated call draws what the first one drew)
+        return _with_range_retry(lambda: self._run(x, cvx, code_src, code_trg, y_in_enc, y_in_dec, eps, seed, outputs, state,
+                                                   return_state))
+
+    def _run(self, x, cvx, code_src, code_trg, y_in_enc, y_in_dec, eps=None, seed=None, outputs=True, state=None,
+             return_state=False):
+        """CycleChain.__call__ behind the range policy."""
         if (self.enc.hidden_layers > 1 or self.dec.hidden_layers > 1) and (state is not None or return_state):
             raise NotImplementedError("hidden_layers=%d/%d: the carry form of CycleChain (state / return_state) is single-layer"
                                       % (self.enc.hidden_layers, self.dec.hidden_layers))
@@ -1051,7 +1121,7 @@ class CycleChain(object):
 
         def run(mod, d_, img, ws, pin, y, clamp, dst):
             lib.gru_rnn_forward_deep(d_, mod.hidden_layers, img.data_ptr(), pin, y.data_ptr(), None, B, T, clamp, dst.data_ptr(), None,
-                                     None, ws.data_ptr(), ws.numel(), flags, st)
+                                     None, ws.data_ptr(), ws.numel(), _deep_flags(flags) if mod.hidden_layers > 1 else flags, st)
 
         prev = None
         for i in range(n):
@@ -1073,6 +1143,7 @@ class CycleChain(object):
         return out if outputs else {}
 
     def status(self):
-        """Synchronises; [0] != 0 = a hand-off spin timed out somewhere since the last check."""
+        """Synchronises; [0] != 0 = a hand-off spin timed out somewhere since the last check; [3] == 7 = an operand left the window
+        of the limb kernels (check_status raises CvaeRangeError for it)."""
         torch.cuda.current_stream().synchronize()
         return [int(v) for v in _sink()] if _sink() is not None else _lib().workspace_status(self._ws.data_ptr(), _stream())

@@ -190,6 +190,14 @@ def convert_pairs(model_encoder, model_decoder, pairs, y_in_pp, y_in_src, y_in_t
     Returns a list of (cvmcep [Ts,Co], cvmcep_src [Ts,Co], cvmcep_trg [Tt,Co], lat_src [Ts,2L], lat_trg [Tt,2L]) (fp32, device).
     """
     gru_vae.check_status()
+    if seed is None and eps is None and gru_vae._range_policy == "retry":
+        seed = gru_vae._draw_seed()      # (a call repeated on the fp32-operand kernels draws what the first try drew)
+    return gru_vae._with_range_retry(lambda: _convert_pairs(model_encoder, model_decoder, pairs, y_in_pp, y_in_src, y_in_trg, lat_dim,
+                                                            n_smpl_dec, eps, seed, window))
+
+
+def _convert_pairs(model_encoder, model_decoder, pairs, y_in_pp, y_in_src, y_in_trg, lat_dim, n_smpl_dec, eps, seed, window):
+    """convert_pairs behind its status check and range policy (gru_vae.set_range_policy)."""
     if window and len(pairs) != 1:
         raise ValueError("convert_pairs(window=...) runs ONE pair as a wavefront of windows, got %d pairs" % len(pairs))
     if window:
@@ -362,6 +370,15 @@ def convert_list(model_encoder, model_decoder, groups, y_in_pp, y_in_src, y_in_t
         return []
     gru_vae._need_cuda(groups[0][0][0], "convert_list(feat_src)")
     gru_vae.check_status()
+    if seeds is None and eps is None and gru_vae._range_policy == "retry":
+        seeds = [gru_vae._draw_seed() for _ in groups]      # (a repeated call draws what the first try drew)
+    return gru_vae._with_range_retry(lambda: _convert_list(model_encoder, model_decoder, groups, y_in_pp, y_in_src, y_in_trg, lat_dim,
+                                                           n_smpl_dec, eps, seeds, pair_ids))
+
+
+def _convert_list(model_encoder, model_decoder, groups, y_in_pp, y_in_src, y_in_trg, lat_dim, n_smpl_dec, eps, seeds, pair_ids):
+    """convert_list behind its status check and range policy: everything joins the current stream before it returns, so the
+    policy's wait for the current stream covers both pipeline streams."""
     dev = groups[0][0][0].device
     if dev not in _pipe_streams:
         with torch.cuda.device(dev):
@@ -449,6 +466,7 @@ def _files_worker(rank, device, first, items, cfg, queue):
         import hdf5io
         dev = torch.device("cuda", int(device))
         torch.cuda.set_device(dev)
+        gru_vae.set_range_policy(cfg.get("range_policy", "raise"))
         nets = []
         for kw, sd in (cfg["enc"], cfg["dec"]):
             m = gru_vae.GRU_RNN(**kw)
@@ -488,7 +506,8 @@ def convert_files(model_encoder, model_decoder, file_pairs, devices, y_in_pp, y_
         raise ValueError("convert_files needs at least one device")
     cfg = {"enc": _net_config(model_encoder), "dec": _net_config(model_decoder),
            "y_in": [v.detach().cpu().numpy() for v in (y_in_pp, y_in_src, y_in_trg)], "lat_dim": int(lat_dim), "n_smpl_dec": int(n_smpl_dec),
-           "per_call": int(per_call), "seed": None if seed is None else int(seed), "key": key, "reader": reader}
+           "per_call": int(per_call), "seed": None if seed is None else int(seed), "key": key, "reader": reader,
+           "range_policy": gru_vae._range_policy}
     chunks = split_file_list(list(file_pairs), len(devices))
     fn = worker or _files_worker
     ctx = mp.get_context("spawn")

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CVAE_ABI_VERSION 7
+#define CVAE_ABI_VERSION 8
 
 /* Shape of one reference GRU_RNN (src/nets/gru_vae.py:282-320). */
 typedef struct cvae_net_desc {
@@ -123,6 +123,18 @@ int cvae_ctx_destroy(cvae_ctx* ctx);
  * status words, so the host-side module can notice it before using any result, without a device synchronisation.  The word is
  * sticky: the caller clears it.  (The reference has nothing to replace here: its GRU loop is a Python loop, gru_vae.py:391-394.)
  *
+ * ABI 8 -- the range word.  Status word 0 carries the codes 1-6 (hand-off time-outs, status 5 of the reverse training recurrences);
+ * word CVAE_STATUS_RANGE_WORD (3) is a word of its own for CVAE_STATUS_RANGE (7): an eval pass on the limb-operand kernels
+ * (CVAE_FLAG_EXACT3 / CVAE_FLAG_SPLIT_F16) was handed a value its fp16 limbs cannot carry -- a normalised input or a carried-in
+ * state with !(|v| < option exact_range_at), NaN and inf included, or an image whose folded weights leave the fp16 range that the
+ * caller never asked about (cvae_net_prepared_in_range).  The results of that pass are then NaN / inf where the reference is
+ * finite: run it again without the two flags (the fp32-operand kernels take the same image and workspace).  Neither word masks
+ * the other.  The check sits in the kernels that BUILD limb operands (the prologue of every pass, the slot-0 fill of the deep
+ * passes): passes that build none (<= 3 rows, the fp32 / generic kernels, a hidden size without an exact form) never raise it,
+ * and no pass has an extra launch.  With a sink the word is sticky like word 0 (sink[3], cleared by the caller; the passes do
+ * not clear it); without one, cvae_workspace_status reports it for the LATEST call on that workspace.  Training entry points are
+ * out of scope: their normalised input goes through fp32 GEMMs and the state of a GRU is bounded by 1.
+ *
  * cvae_set_draw_origin: place of this process in a data-parallel job: row0 = global index of its first batch
  * row, global_rows = batch rows of the whole job (0 = this process alone), frames_per_row = T of the windows fed to
  * cvae_sample (whose `rows` are flattened frames; 0 = no offset there).  The on-device Philox streams (latent draws, dropout
@@ -193,6 +205,10 @@ int cvae_set_draw_parts(cvae_ctx* ctx, int32_t parts);
  *   "train_profile"     0        1: HIP events on the launch stream around the training recurrences and GEMMs (cvae_train_profile_collect)
  *   "v6_backoff"        -1       >= 0: units of 64 cycles a block of k_gru_steps_v6 with one row tile sleeps before the first flag poll
  *                                of a step (-1: swept per front-end width: 8 for the decoder's KFW = 6, 2 for the encoder's 8)
+ *   "exact_range_at"    65504    |x| from which an exchanged value of the limb-operand eval kernels (normalised input, carried-in state)
+ *                                raises CVAE_STATUS_RANGE.  65504 (default, the largest finite half): the first limb overflows and the
+ *                                result is unusable.  2048: the bound below which the (fp16, fp16, bf8) triple is EXACT; in between
+ *                                the clamped bf8 limb costs at most 2^-23 relative.  Clamped to 1 .. 65504.
  *   "masks_on_side"     1        train-mode forward with a side stream set: the dropout mask of the recurrence's feedback operand is
  *                                drawn on the side stream, beside the prologue and the front-end GEMMs (0: on the launch stream)
  */
@@ -225,6 +241,18 @@ size_t cvae_net_prepare_scratch_bytes(cvae_ctx* ctx, const cvae_net_desc* d);
  */
 int cvae_net_prepare(cvae_ctx* ctx, const cvae_net_desc* d, const cvae_net_weights* w, void* prepared, size_t prepared_bytes,
                      void* scratch, size_t scratch_bytes, void* stream);
+/*
+ * ABI 8: do the weights of a prepared image (cvae_net_prepare, cvae_net_prepare_deep with its n_layers) fit the limb images?  The
+ * prepare kernels leave a flag in the image when a FOLDED weight (front-end fold, feedback fold + W_hh, scale_out . out_1, W_ih / W_hh
+ * of an upper layer) reaches the largest finite half, 65504: its first limb would be inf.  Returns 1 = fits, 0 = does not,
+ * negative = error; synchronises `stream` (call it once per image build, not per pass).  The context remembers a 0 by the image's
+ * address: passes on that image through this context then run the fp32-operand kernels whatever exact / split flags they are
+ * given (deep images: k_gru_steps_deep; cvae_plan_pass_deep does not see an image: for an unfit one the pass takes what it
+ * reports for flags | CVAE_FLAG_GENERIC_STEP) -- the reference simply computes on such weights, and so does the pass.  A pass on
+ * an unfit image the context was never asked about raises CVAE_STATUS_RANGE instead.  The answer is kept by ADDRESS until this
+ * context prepares an image there again: ask again after an image was rebuilt at the same address through another context.
+ */
+int cvae_net_prepared_in_range(cvae_ctx* ctx, const cvae_net_desc* d, int n_layers, const void* prepared, void* stream);
 
 /* Bytes of workspace one pass of (B,T) needs. */
 size_t cvae_pass_workspace_bytes(cvae_ctx* ctx, const cvae_net_desc* d, int B, int T);
@@ -242,6 +270,9 @@ size_t cvae_pass_workspace_bytes(cvae_ctx* ctx, const cvae_net_desc* d, int B, i
 #define CVAE_FLAG_STEP_TIMING 8  /* debugging: the tuned recurrent kernel accumulates per-phase cycle counters */
 #define CVAE_FLAG_PROFILE 2    /* bracket the recurrent kernel(s) of each pass with hipEvents (see cvae_profile_collect) */
 
+#define CVAE_STATUS_RANGE 7        /* status code of an operand outside the window of the limb form (cvae_set_status_sink, ABI 8) */
+#define CVAE_STATUS_RANGE_WORD 3   /* the status word that carries it */
+
 /*
  * One GRU_RNN.forward in eval mode (gru_vae.py:322-455, live branch: res/noise/softmax/... flags off).
  *   in      : the pass input, B*T rows of Cin = seg0.width + (lat ? lat_dim : seg1.width) features
@@ -252,7 +283,9 @@ size_t cvae_pass_workspace_bytes(cvae_ctx* ctx, const cvae_net_desc* d, int B, i
  *                   (clamp_vae_laplace, gru_vae.py:415-417); ignored when the net has scale_out.  The same
  *                   encoding holds for every clamp_lat_dim argument below (train-mode forward / backward included)
  *   trj_out : [B,T,Cout]; y_last: [B,Cout] raw last projection; h_last: [B,H]   (gru_vae.py:452-453)
- *   status  : device int32[4]; status[0] != 0 after completion means a grid barrier timed out
+ *   status  : int32[4] (the sink of cvae_set_status_sink, else read with cvae_workspace_status): status[0] != 0 after completion
+ *             means a hand-off spin or grid barrier timed out; status[3] == CVAE_STATUS_RANGE that an operand of a limb-operand
+ *             kernel was out of range (ABI 8, see cvae_set_status_sink): the pass ran to its end on inf / NaN operands
  */
 int cvae_gru_rnn_forward(cvae_ctx* ctx, const cvae_net_desc* d, const void* prepared, const cvae_pass_input* in,
                          const float* y_in, const float* h_in, int B, int T, int clamp_lat_dim,
@@ -561,7 +594,8 @@ size_t cvae_dtw_work_bytes(cvae_ctx* ctx, int T1, int T2);
 int cvae_dtw_org_to_trg(cvae_ctx* ctx, const double* org, const double* trg, int T1, int T2, int D, int mcd, double* aligned, long long* twf,
                         double* frames, double* mean_out, void* work, size_t work_bytes, void* stream);
 
-/* Copy status words (int32[4]) of a workspace to the host; synchronises `stream`.  status[0]!=0 = barrier timeout. */
+/* Copy status words (int32[4]) of a workspace to the host; synchronises `stream`.  status[0]!=0 = barrier timeout;
+ * status[3] == CVAE_STATUS_RANGE: the latest call on this workspace met an operand outside the limb window (no sink set). */
 int cvae_workspace_status(cvae_ctx* ctx, const void* workspace, int32_t status_out[4], void* stream);
 
 #ifdef __cplusplus
