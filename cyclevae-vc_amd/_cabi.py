@@ -7,7 +7,7 @@ library is missing or its ABI version differs, loading raises.
 import ctypes as C
 import os
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 FLAG_PERSISTENT = 1
 FLAG_PROFILE = 2
 FLAG_GENERIC_STEP = 4
@@ -59,6 +59,7 @@ def upper_layer_keys(n_layers):
 
 
 DEEP_PER_STEP, DEEP_GENERIC, DEEP_RESIDENT = 0, 1, 2      # cvae_plan_pass_deep
+EVAL_PER_STEP, EVAL_GENERIC, EVAL_V2, EVAL_V4, EVAL_V5, EVAL_V6, EVAL_LL = range(7)      # cvae_plan_pass (cvae_eval_form)
 MAX_LAYERS = 8                                              # CVAE_DEEP_MAX_LAYERS
 
 
@@ -176,6 +177,8 @@ class CvaeLib(object):
                                             C.c_size_t, _fp]
         L.cvae_pass_workspace_bytes_deep.restype = C.c_size_t
         L.cvae_pass_workspace_bytes_deep.argtypes = [C.POINTER(NetDesc), C.c_int, C.c_int, C.c_int]
+        L.cvae_plan_pass.restype = C.c_int
+        L.cvae_plan_pass.argtypes = [C.POINTER(NetDesc), C.c_int, C.c_int, C.c_int]
         L.cvae_plan_pass_deep.restype = C.c_int
         L.cvae_plan_pass_deep.argtypes = [C.POINTER(NetDesc), C.c_int, C.c_int, C.c_int, C.c_int]
         L.cvae_gru_rnn_forward_deep.restype = C.c_int
@@ -389,6 +392,13 @@ class CvaeLib(object):
         if n == 0:
             raise CvaeError("cvae_pass_workspace_bytes_deep: bad arguments (n_layers=%d, B=%d, T=%d)" % (n_layers, B, T))
         return n
+
+    def plan_pass(self, d, rows, T, flags=0):
+        """EVAL_PER_STEP .. EVAL_LL: the recurrence a one-layer eval pass of `rows` batch rows in all takes."""
+        rc = self.lib.cvae_plan_pass(C.byref(d), rows, T, flags)
+        if rc < 0:
+            self._check(rc, "cvae_plan_pass")
+        return rc
 
     def plan_pass_deep(self, d, n_layers, B, T, flags=0):
         """DEEP_PER_STEP / DEEP_GENERIC / DEEP_RESIDENT: the recurrence a pass of this shape takes."""
@@ -616,4 +626,4 @@ EXPORTS = ("cvae_last_error_string", "cvae_abi_version", "cvae_ctx_create", "cva
            "cvae_kl_gauss_backward",
            "cvae_gv_postfilter", "cvae_mcd_aligned", "cvae_mc2e", "cvae_dtw_work_bytes", "cvae_dtw_org_to_trg",
            "cvae_net_prepared_bytes_deep", "cvae_net_prepare_scratch_bytes_deep", "cvae_net_prepare_deep", "cvae_pass_workspace_bytes_deep",
-           "cvae_plan_pass_deep", "cvae_gru_rnn_forward_deep", "cvae_net_prepared_in_range")
+           "cvae_plan_pass", "cvae_plan_pass_deep", "cvae_gru_rnn_forward_deep", "cvae_net_prepared_in_range")

@@ -48,9 +48,7 @@ DeepPlan plan_deep_pass(const Dims& m, int L, int B, int T, int flags) {
     const int nrt32 = pn.Bp / 32, NB = m.H / 8;
     const long mtot = (long)(T + 1) * pn.Bp;
     if (!(flags & CVAE_FLAG_GENERIC_STEP) && deep3_ok(m) && cus >= L * NB && (long)L * m.nch * mtot * 80 < (1L << 31)) {
-        int rts = cus / (L * NB);
-        rts = rts > nrt32 ? nrt32 : rts;
-        if (opt(OPT_MAX_RT) >= 1 && opt(OPT_MAX_RT) < rts) rts = (int)opt(OPT_MAX_RT);
+        const int rts = row_tiles_per_block(cus, L * NB, nrt32);
         if ((nrt32 + rts - 1) / rts <= 4) {
             pn.path = DEEP_RESIDENT;
             pn.rts = rts;

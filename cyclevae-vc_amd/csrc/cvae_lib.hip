@@ -30,8 +30,8 @@ thread_local char g_err[512] = "";
 
 // Tuning / diagnostic switches (cvae_set_option): the library reads NO environment variable.
 enum OptId {
-    OPT_V6_LIMBS_H64, OPT_NO_LL, OPT_MAX_RT, OPT_LL_BACKOFF, OPT_EXP, OPT_OLD_OUTPROJ, OPT_GEMM_FORCE, OPT_GEMM_LOG, OPT_TRAIN_OLD_GEMM,
-    OPT_GEMM_TRACE, OPT_TRAIN_PER_STEP, OPT_TRAIN_PROF, OPT_TRAIN_BACKOFF, OPT_TRAIN_FP32_MFMA, OPT_TRAIN_BWD_PER_STEP, OPT_TRAIN_KERNEL, OPT_X3_TILE, OPT_BWD_OVERFLOW_AT, OPT_GEMM_MAX_SPLIT, OPT_BWD_KS, OPT_COOP_LAUNCH, OPT_V6_LIMBS_H2048, OPT_V6_W2S_H64, OPT_STEP_COL_TILES, OPT_T0_IN_KERNEL, OPT_TRAIN_PROFILE, OPT_TRAIN_XMAP, OPT_MASKS_ON_SIDE, OPT_V6_BACKOFF, OPT_TRAIN_BWD_BACKOFF, OPT_LL_ROW_PAD, OPT_GEMM_MIN_DEPTH, OPT_TRAIN_BWD_GEOM, OPT_BWD_W3_L1_H64, OPT_TRAIN_FWD_GEOM, OPT_TRAIN_FWD_BACKOFF, OPT_EXACT_RANGE_AT, OPT_COUNT
+    OPT_V6_LIMBS_H64, OPT_NO_LL, OPT_MAX_RT, OPT_LL_BACKOFF, OPT_EXP, OPT_GEMM_FORCE, OPT_GEMM_LOG, OPT_TRAIN_OLD_GEMM,
+    OPT_GEMM_TRACE, OPT_TRAIN_PER_STEP, OPT_TRAIN_PROF, OPT_TRAIN_BACKOFF, OPT_TRAIN_FP32_MFMA, OPT_TRAIN_BWD_PER_STEP, OPT_TRAIN_KERNEL, OPT_X3_TILE, OPT_BWD_OVERFLOW_AT, OPT_GEMM_MAX_SPLIT, OPT_BWD_KS, OPT_COOP_LAUNCH, OPT_V6_LIMBS_H2048, OPT_V6_W2S_H64, OPT_STEP_COL_TILES, OPT_TRAIN_PROFILE, OPT_TRAIN_XMAP, OPT_MASKS_ON_SIDE, OPT_V6_BACKOFF, OPT_TRAIN_BWD_BACKOFF, OPT_LL_ROW_PAD, OPT_GEMM_MIN_DEPTH, OPT_TRAIN_BWD_GEOM, OPT_BWD_W3_L1_H64, OPT_TRAIN_FWD_GEOM, OPT_TRAIN_FWD_BACKOFF, OPT_EXACT_RANGE_AT, OPT_COUNT
 };
 struct OptEntry { const char* name; long dflt; };
 const OptEntry g_opt[OPT_COUNT] = {      // names and DEFAULTS (immutable); the values live in the context
@@ -40,7 +40,6 @@ const OptEntry g_opt[OPT_COUNT] = {      // names and DEFAULTS (immutable); the 
     {"max_rt", 0},                // > 0: cap on the row tiles handled concurrently (tests: several row tiles per block on small problems)
     {"ll_backoff", -1},          // >= 0: s_sleep units before the first poll of a step in k_gru_steps_ll (-1: the swept default)
     {"exp", 0},                   // measurement switches of the dataflow kernels (Step6Params::exp)
-    {"old_outproj", 0},           // 1: projection of a v6 pass from the fp32 state copy instead of the limb triples
     {"gemm_force", 0},            // measurement: TM*10000 + TN*100 + ks forces the tile / split of every training GEMM
     {"gemm_log", 0},              // measurement: every training GEMM bracketed by HIP events and printed to stderr
     {"train_old_gemm", 0},        // 1: the simple GEMM kernels kept as unaligned-operand fallbacks, everywhere
@@ -59,7 +58,6 @@ const OptEntry g_opt[OPT_COUNT] = {      // names and DEFAULTS (immutable); the 
     {"v6_limbs_h2048", 3},        // 2: k_gru_steps_v6 at H = 2048 on fp16 PAIRS (faster, 22-23 bit operands) instead of exact triples
     {"v6_w2s_h64", 0},            // 1: the streamed-third-limb form of k_gru_steps_v6 (what runs at H = 2048) at H = 64, for the emulator tests
     {"step_col_tiles", 0},        // per-step forward training kernel: 0 pick (two 16-column tiles per block when every CU still gets a block), 1 / 2 force
-    {"t0_in_kernel", 0},          // 1: k_gru_steps_v6 forms the frame-0 feedback correction itself (cvae_t0_fix) instead of reading the prologue's gx0
     {"train_profile", 0},         // 1: HIP events around the training recurrences and GEMMs, summed per class (cvae_train_profile_collect)
     {"train_xmap", 0},            // bit 0 / 1: XCD-aware block placement in the exact forward / reverse training recurrences
     {"masks_on_side", 1},         // train-mode forward with a side stream set: the recurrence's dropout mask is drawn on it, beside the front-end GEMMs (0: on the launch stream)
@@ -192,20 +190,49 @@ int make_dims(const cvae_net_desc* d, Dims* o) {
     return 0;
 }
 
-// k_gru_steps_v6 is instantiated for H = 1024 (16 16-k steps per wave, three limbs), H = 64 (one step, three limbs; tests) and
-// H = 2048 (32 steps, TWO limbs: the hu2048 stress configuration, BASELINE configs[4]); front-end steps per wave as listed
+// ---- Kernel instances of the eval recurrences: what is built, by geometry.  The layouts (is there a limb image to lay out?), the
+// plan (plan_eval_pass) and the launches all look up THESE tables; a geometry without a row has no such kernel.
+//
+// k_gru_steps_v6 (exact fp32 operands): H = 1024 (16 16-k steps per wave, three limbs), H = 2048 (32 steps: three limbs with the
+// third weight limb streamed from L2, or fp16 PAIRS, option v6_limbs_h2048 -- the hu2048 stress configuration, BASELINE configs[4])
+// and H = 64 (one step; every form, picked by the options v6_limbs_h64 / v6_w2s_h64: tests at a size the host-fiber emulator runs)
+struct V6Inst { int H, KFW, limbs; bool w2s; void (*fn)(Step6Params); };
+const V6Inst g_v6_inst[] = {
+    {1024, 8, 3, false, k_gru_steps_v6<16, 8>},       {1024, 6, 3, false, k_gru_steps_v6<16, 6>},
+    {2048, 8, 3, true, k_gru_steps_v6<32, 8, 3, true>}, {2048, 11, 3, true, k_gru_steps_v6<32, 11, 3, true>},
+    {2048, 8, 2, false, k_gru_steps_v6<32, 8, 2>},    {2048, 11, 2, false, k_gru_steps_v6<32, 11, 2>},
+    {64, 3, 3, false, k_gru_steps_v6<1, 3>},          {64, 2, 3, false, k_gru_steps_v6<1, 2>},          {64, 1, 3, false, k_gru_steps_v6<1, 1>},
+    {64, 3, 3, true, k_gru_steps_v6<1, 3, 3, true>},  {64, 2, 3, true, k_gru_steps_v6<1, 2, 3, true>},  {64, 1, 3, true, k_gru_steps_v6<1, 1, 3, true>},
+    {64, 3, 2, false, k_gru_steps_v6<1, 3, 2>},       {64, 2, 2, false, k_gru_steps_v6<1, 2, 2>},       {64, 1, 2, false, k_gru_steps_v6<1, 1, 2>},
+};
+// the 16-row fused kernels: k_gru_steps_v5 (fp16 pairs) and k_gru_steps_v4 (fp32 MFMA), always built together
+struct Fused16Inst { int H, KFW; void (*v5)(Step3Params); void (*v4)(Step3Params); };
+const Fused16Inst g_fused16_inst[] = {
+    {1024, 8, k_gru_steps_v5<16, 8>, k_gru_steps_v4<16, 8>}, {1024, 6, k_gru_steps_v5<16, 6>, k_gru_steps_v4<16, 6>},
+    {64, 2, k_gru_steps_v5<1, 2>, k_gru_steps_v4<1, 2>},     {64, 1, k_gru_steps_v5<1, 1>, k_gru_steps_v4<1, 1>},
+};
+// k_outproj_v6, the projection from the limb triples a k_gru_steps_v6 pass leaves
+struct Out6Inst { int H; void (*fn)(Out6Params); };
+const Out6Inst g_out6_inst[] = {{1024, k_outproj_v6<16>}, {2048, k_outproj_v6<32>}, {64, k_outproj_v6<1>}};
+
 inline int exact3_kpw(const Dims& m) { return m.H / 64; }
+// limbs < 0: any form of that geometry (what the layouts ask: a limb image exists whatever the options pick)
+inline const V6Inst* find_v6(const Dims& m, int limbs = -1, bool w2s = false) {
+    for (const V6Inst& i : g_v6_inst)
+        if (i.H == m.H && i.KFW == m.KFW && (limbs < 0 || (i.limbs == limbs && i.w2s == w2s))) return &i;
+    return nullptr;
+}
+inline const Fused16Inst* find_fused16(const Dims& m) {
+    for (const Fused16Inst& i : g_fused16_inst)
+        if (i.H == m.H && i.KFW == m.KFW) return &i;
+    return nullptr;
+}
+inline bool exact3_ok(const Dims& m) { return find_v6(m) != nullptr; }
+// the form of k_gru_steps_v6 the options pick at this H: limbs per operand, third weight limb streamed
 inline int v6_limbs(const Dims& m) {
-    if (m.H == 64) {   // tests: the two-limb code path at a size the host-fiber emulator can run
-        if (opt(OPT_V6_LIMBS_H64) == 2) return 2;
-    }
-    return m.H == 2048 && opt(OPT_V6_LIMBS_H2048) == 2 ? 2 : 3;
+    return (m.H == 64 && opt(OPT_V6_LIMBS_H64) == 2) || (m.H == 2048 && opt(OPT_V6_LIMBS_H2048) == 2) ? 2 : 3;
 }
 inline bool v6_w2s(const Dims& m) { return v6_limbs(m) == 3 && (m.H == 2048 || (m.H == 64 && opt(OPT_V6_W2S_H64))); }
-inline bool exact3_ok(const Dims& m) {
-    return (m.H == 1024 && (m.KFW == 8 || m.KFW == 6)) || (m.H == 64 && m.KFW >= 1 && m.KFW <= 3) ||
-           (m.H == 2048 && (m.KFW == 8 || m.KFW == 11));
-}
 
 // prepared image: offsets in floats, every block 64-float aligned
 struct Prep {
@@ -248,16 +275,21 @@ Prep prep_layout(const Dims& m, bool sin, bool sout) {
 // pass workspace: offsets in floats.  Brows = total batch rows of the pass (cells stacked along the batch axis)
 struct Work {
     long status, xnp, xs, xs_plane, xt, xt_slack, gx, hbuf, hs, y, dy, gx0, prof, flags, total;
-    int Bp, Tp;
+    int Bp, Tp, prof_blocks;
     long mtot;
 };
 
+// Batch rows are padded to whole row tiles: one 16-row tile for the word-exchange kernel (at most 3 rows), 32-row tiles
+// (k_gru_steps_v6: exact operands) from 4 rows on wherever that kernel exists -- ONE arithmetic width for every batch size, a pass
+// of 4..16 rows runs a half-empty tile rather than the 22-bit pair kernel -- else 16-row tiles up to 16 rows.  Independent of the
+// pass's flags: the workspace size query has none.
+inline int eval_row_pad(const Dims& m, int Brows) {
+    return Brows <= 3 ? 16 : (exact3_ok(m) || Brows > 16 ? (int)up(Brows, 32) : 16);
+}
+
 Work work_layout(const Dims& m, int Brows, int T) {
     Work w;
-    // batch rows are padded to whole row tiles: one 16-row tile for the word-exchange kernel (at most 3 rows), 32-row tiles
-    // (k_gru_steps_v6: exact operands) from 4 rows on wherever that kernel exists -- ONE arithmetic width for every batch size,
-    // a pass of 4..16 rows runs a half-empty tile rather than the 22-bit pair kernel -- else 16-row tiles up to 16 rows
-    w.Bp = Brows <= 3 ? 16 : (exact3_ok(m) || Brows > 16 ? (int)up(Brows, 32) : 16);
+    w.Bp = eval_row_pad(m, Brows);
     w.Tp = T + 2 * m.pad;
     w.mtot = (long)(T + 1) * w.Bp;
     long o = 0;
@@ -275,10 +307,101 @@ Work work_layout(const Dims& m, int Brows, int T) {
     w.y = take((long)T * w.Bp * m.Cop);
     w.dy = take((long)w.Bp * m.Co);
     w.gx0 = take((long)w.Bp * m.H3);   // frame-0 feedback correction of the exact-operand kernel (prologue role gx0)
-    w.prof = take(2048);  // long long[<=256 blocks][4] step-timing counters
+    w.prof_blocks = 256;
+    w.prof = take(w.prof_blocks * 8L);  // long long[prof_blocks][4] step-timing counters
     w.flags = take((long)(w.Bp / 16) * m.nch);
     w.total = o;
     return w;
+}
+
+// Row tiles a block of an all-resident grid handles: as few as the chip allows (every CU gets a block), at most all of them.
+// per_tile: blocks one row tile takes.  Option max_rt caps it (tests: several row tiles per block on small problems).
+inline int row_tiles_per_block(int cus, int per_tile, int ntiles) {
+    int rts = per_tile > 0 ? cus / per_tile : 1;
+    rts = rts < 1 ? 1 : (rts > ntiles ? ntiles : rts);
+    if (opt(OPT_MAX_RT) >= 1 && opt(OPT_MAX_RT) < rts) rts = (int)opt(OPT_MAX_RT);
+    return rts;
+}
+
+// Which kernels an eval pass of a one-layer network runs (the one place that decides; cvae_plan_pass reports the form; the table
+// of form x condition is DESIGN.md 4.1).  The forms are numbered so that a refused cooperative launch steps DOWN:
+// V5 -> V4 -> V2 -> GENERIC -> PER_STEP (run_pass; LL and V6 return the error).
+struct PassFacts {      // what a call's pointers decide
+    bool h_in, y_last, h_last, many_draws;      // any cell with a carried-in state / a raw last projection / a state out / n_draws > 1
+};
+enum { PRO_ROWS = 0, PRO_DRAWS = 1, PRO_TILES = 2 };      // prologue launch: 64 threads per (row, frame); 256 (draws summed in slices); 256 per (32-row tile, frame)
+enum { PROJ_GEMM = 0, PROJ_FUSED = 1, PROJ_V6 = 2 };      // projection: GEMM + k_epilogue; k_outproj<1|4|8>; k_outproj_v6
+struct EvalPlan {
+    int form;                             // CVAE_EVAL_*
+    void (*k6)(Step6Params);              // the instance to launch: V6
+    void (*k5)(Step3Params);              // V5
+    void (*k4)(Step3Params);              // V4, and what a refused V5 steps down to
+    void (*kout6)(Out6Params);            // PROJ_V6
+    int rts;                              // row tiles per block (V6: of 32 rows; V5 / V4 / V2: of 16)
+    int backoff;                          // first-poll back-off (LL: s_sleep units, V6: x 64 cycles)
+    bool limbs;                           // the pass BUILDS limb operands: its prologue gets the range word
+    bool pairs;                           // the prologue writes the fp16-pair copies (SPLIT_F16 off V6; V6: the limb triples instead)
+    bool gx0_ready;                       // the prologue forms the frame-0 feedback correction (else k_gru_steps_v6 does: cvae_t0_fix)
+    bool want_f32;                        // V6 also writes the fp32 state copy
+    int prologue, proj;                   // PRO_*, PROJ_*
+};
+
+inline bool generic_resident(const Dims& m, int cus) { return cus <= 0 || m.H / 4 <= cus; }      // one 256-thread block per CU is always admitted
+
+EvalPlan plan_eval_pass(const Dims& m, int Brows, int T, int flags, int cus, bool unfit, const PassFacts& f) {
+    EvalPlan pn;
+    memset(&pn, 0, sizeof(pn));
+    // an image whose folded weights do not fit the limb images (cvae_net_prepared_in_range) runs on the fp32-operand kernels
+    if (unfit) flags &= ~CVAE_FLAG_SPLIT_F16;
+    const int Bp = eval_row_pad(m, Brows);
+    const long mtot = (long)(T + 1) * Bp;
+    const bool persistent = (flags & CVAE_FLAG_PERSISTENT) && T > 1, generic = (flags & CVAE_FLAG_GENERIC_STEP) != 0;
+    const bool hoisted = (flags & CVAE_FLAG_HOISTED_FRONTEND) != 0, exact = persistent && (flags & CVAE_FLAG_EXACT3) && !generic;
+    const V6Inst* i6 = find_v6(m, v6_limbs(m), v6_w2s(m));
+    const Fused16Inst* i16 = find_fused16(m);
+    if (exact && Brows <= 3 && T < 65536 && m.H % 64 == 0 && m.H <= 1024 && cus >= m.H / 4 && !opt(OPT_NO_LL)) {
+        // at most three rows: a step is one store + one polled load per unit, plain fp32 FMAs; H/4 blocks, every one resident
+        pn.form = CVAE_EVAL_LL;
+        pn.backoff = opt(OPT_LL_BACKOFF) >= 0 ? (int)opt(OPT_LL_BACKOFF) : (Brows == 1 ? 22 : 20);   // swept per row count (round 4, after the prefetch reordering: profiles/r04_notes.md; round 2: 18 / 16)
+    } else if (exact && !unfit && !hoisted && i6 && Bp % 32 == 0 && cus >= m.H / 8 && (long)m.nch * mtot * 80 < (1L << 31)) {
+        // exact fp32 operands as fp16 triples: 32-row tiles, 8-unit octets, H/8 blocks per tile, every block resident
+        pn.form = CVAE_EVAL_V6;
+        pn.k6 = i6->fn;
+        pn.rts = row_tiles_per_block(cus, m.H / 8, Bp / 32);
+        // One row tile per block (B <= 64 at hu1024): nothing can be published before the other blocks' front-ends are through, and
+        // 256 waves polling through that window slow the publishes and operand loads they wait for.  The decoder's front-end is a
+        // quarter shorter than the encoder's (KFW 6 vs 8), so its blocks arrive at the poll earlier: swept on MI355X
+        // (tools/ab_eval_exp.sh, round 5), 64-cycle units -- decoder pass 421.7 (0) / 405.8 (4) / 397.1 (8) / 401.0 (12) / 409.0 us
+        // (16), encoder pass 412.3 / 411.0 / 416.6 / 423.9 / 434.5 us.
+        pn.backoff = opt(OPT_V6_BACKOFF) >= 0 ? (int)opt(OPT_V6_BACKOFF) : (m.H == 1024 ? (m.KFW <= 6 ? 8 : 2) : 0);
+    } else if (persistent && !generic && (m.H == 1024 || m.H == 64) && cus >= m.nch && (long)m.nch * mtot * 64 < (1L << 31)) {
+        // the 16-row dataflow kernels (H/16 blocks per tile, every block resident): front-end fused where an instance exists for
+        // the front-end width -- on fp16 pairs (V5) or the fp32 MFMA (V4) -- else behind a hoisted GEMM (V2)
+        pn.form = hoisted || !i16 ? CVAE_EVAL_V2 : ((flags & CVAE_FLAG_SPLIT_F16) ? CVAE_EVAL_V5 : CVAE_EVAL_V4);
+        if (i16) pn.k5 = i16->v5, pn.k4 = i16->v4;
+        pn.rts = row_tiles_per_block(cus, m.nch, Bp / 16);
+    } else {
+        // the any-H kernel: one launch behind a grid barrier when its H/4 blocks are resident, else one launch per step
+        pn.form = persistent && generic_resident(m, cus) ? CVAE_EVAL_GENERIC : CVAE_EVAL_PER_STEP;
+    }
+    const bool v6 = pn.form == CVAE_EVAL_V6;
+    pn.limbs = v6 || pn.form == CVAE_EVAL_V5;
+    // the pair copies are written whenever SPLIT_F16 is set off V6, but only k_gru_steps_v5 reads them: a pass that ends up on
+    // k_gru_steps_ll or on an fp32-operand kernel has nothing to report (limbs)
+    pn.pairs = !v6 && (flags & CVAE_FLAG_SPLIT_F16);
+    pn.gx0_ready = v6 && !f.h_in;
+    // the fp32 state copy of a V6 pass is only read by the raw projection (y_last), k_hlast and the projections off the limb triples
+    pn.want_f32 = v6 && (i6->limbs != 3 || f.y_last || f.h_last || (opt(OPT_EXP) & 16));      // (exp bit 4: always write it, for A/B measurements)
+    pn.prologue = v6 ? PRO_TILES : (f.many_draws ? PRO_DRAWS : PRO_ROWS);
+    const int ntn = m.Cop / 16;
+    if (!f.y_last && v6 && i6->limbs == 3) {
+        pn.proj = PROJ_V6;      // the pass left the state as limb triples in the exchange buffer: project from there, same exact arithmetic
+        for (const Out6Inst& o : g_out6_inst)
+            if (o.H == m.H) pn.kout6 = o.fn;
+    } else {
+        pn.proj = !f.y_last && (ntn == 1 || ntn == 4 || ntn == 8) ? PROJ_FUSED : PROJ_GEMM;
+    }
+    return pn;
 }
 
 bool prof_begin(hipStream_t st, int rows = 0, int cin = 0) {
@@ -379,21 +502,20 @@ struct Cell {
     float* h_last;       // [B][H] or null
 };
 
+// plan, prologue, the recurrence (one switch on the planned form), projection, k_hlast
 int run_pass(const Dims& m, const cvae_net_desc* d, const float* P, const Cell* cells, int ncell, int B, int T,
              int clamp_lat_dim, float* ws, int* status, int flags, hipStream_t st, bool clear_status = false) {
     const Prep pl = prep_layout(m, d->has_scale_in != 0, d->has_scale_out != 0);
     const int Brows = ncell * B;
     const Work wl = work_layout(m, Brows, T);
     int* const ws_status = status;
-    // an image whose folded weights do not fit the limb images (cvae_net_prepared_in_range) runs on the fp32-operand kernels
-    const bool unfit = image_known_unfit(P);
-    if (unfit) flags &= ~CVAE_FLAG_SPLIT_F16;
     if (cx().status_sink) status = cx().status_sink;    // host-visible sticky word: a time-out is seen without reading the workspace back
     for (int c = 0; c < ncell; ++c) {
         const cvae_pass_input* in = cells[c].in;
         const int w_in = in->seg0.width + (in->lat ? in->lat_dim : in->seg1.width);
         if (w_in != m.C) return fail(-1, "pass input width %d != in_dim %d", w_in, m.C);
     }
+    if (ncell > CVAE_MAX_CELLS) return fail(-1, "at most %d stacked cells per pass", CVAE_MAX_CELLS);
     unsigned* bar = (unsigned*)(ws + wl.status) + 8;  // status words themselves are sticky: zeroed by the entry point
     float* xnp = ws + wl.xnp;
     float* gx = ws + wl.gx;
@@ -401,26 +523,17 @@ int run_pass(const Dims& m, const cvae_net_desc* d, const float* P, const Cell* 
     float* y = ws + wl.y;
     float* dy = ws + wl.dy;
     unsigned* hflags = (unsigned*)(ws + wl.flags);
-    const int nrt = wl.Bp / 16;
-    if (ncell > CVAE_MAX_CELLS) return fail(-1, "at most %d stacked cells per pass", CVAE_MAX_CELLS);
+    long long* const step_prof = (flags & CVAE_FLAG_STEP_TIMING) ? (long long*)(ws + wl.prof) : nullptr;
     const int cus = cu_count();
-    // k_gru_steps_v6 (exact fp32 operands as fp16 triples): 32-row tiles, 8-unit octets, every block resident
-    const bool use_exact3 = !unfit && (flags & CVAE_FLAG_PERSISTENT) && (flags & CVAE_FLAG_EXACT3) && !(flags & CVAE_FLAG_GENERIC_STEP) &&
-                            !(flags & CVAE_FLAG_HOISTED_FRONTEND) && T > 1 && exact3_ok(m) && wl.Bp % 32 == 0 &&
-                            cus >= m.H / 8 && (long)m.nch * wl.mtot * 80 < (1L << 31);
+    PassFacts facts = {};
+    for (int c = 0; c < ncell; ++c) {
+        facts.h_in = facts.h_in || cells[c].h_in != nullptr;
+        facts.y_last = facts.y_last || cells[c].y_last != nullptr;
+        facts.h_last = facts.h_last || cells[c].h_last != nullptr;
+        facts.many_draws = facts.many_draws || (cells[c].in->lat && cells[c].in->n_draws > 1);
+    }
+    const EvalPlan pn = plan_eval_pass(m, Brows, T, flags, cus, image_known_unfit(P), facts);
 
-    // k_gru_steps_ll (at most three rows: a step is one store + one polled load per unit, plain fp32 FMAs): every block resident
-    const bool use_ll = (flags & CVAE_FLAG_PERSISTENT) && (flags & CVAE_FLAG_EXACT3) && !(flags & CVAE_FLAG_GENERIC_STEP) && T > 1 &&
-                        Brows <= 3 && T < 65536 && m.H % 64 == 0 && m.H <= 1024 && cus >= m.H / 4 && !opt(OPT_NO_LL);
-
-    // k_gru_steps_v5 (fp16 pairs): the geometries it is built for, when neither kernel above takes the pass (the same conditions
-    // as at its launch below; the range guard checks the pair copies only when this kernel will read them)
-    const bool use_split5 = !use_exact3 && !use_ll && (flags & CVAE_FLAG_PERSISTENT) && T > 1 && (flags & CVAE_FLAG_SPLIT_F16) &&
-                            !(flags & CVAE_FLAG_GENERIC_STEP) && !(flags & CVAE_FLAG_HOISTED_FRONTEND) &&
-                            (long)m.nch * wl.mtot * 64 < (1L << 31) && cus >= m.nch &&
-                            ((m.H == 1024 && (m.KFW == 8 || m.KFW == 6)) || (m.H == 64 && (m.KFW == 2 || m.KFW == 1)));
-
-    bool gx0_ready = false;
     {   // one prologue launch: assemble + scale_in + padding, slot-0 init, frame-0 feedback correction, zeroing
         ProParams pp;
         memset(&pp, 0, sizeof(pp));
@@ -445,8 +558,6 @@ int run_pass(const Dims& m, const cvae_net_desc* d, const float* P, const Cell* 
                 return fail(-1, "cell %d: windows of a longer utterance (ctx_before / ctx_after / draw_frame0) are single-row cells, B=%d", c, B);
             if (in->lat) pp.L = in->lat_dim;
         }
-        bool many_draws = false;
-        for (int c = 0; c < ncell; ++c) many_draws = many_draws || (cells[c].in->lat && cells[c].in->n_draws > 1);
         pp.ncell = ncell;
         pp.frame0 = (uint64_t)cx().draw_row0 * (uint64_t)T;
         pp.sin_w = d->has_scale_in ? P + pl.sin_w : nullptr;
@@ -456,231 +567,161 @@ int run_pass(const Dims& m, const cvae_net_desc* d, const float* P, const Cell* 
         pp.nslack = 64 * m.KFW + 64;
         pp.mtot = wl.mtot;
         pp.xnp = xnp; pp.hbuf = hbuf; pp.dy = dy;
-        // (k_gru_steps_v6 reads the fp32 buffers themselves and splits in registers: no limb copies)
-        pp.hx = use_exact3 ? ws + wl.hs : nullptr;    // (the pair buffer's space: same size, never both in one pass)
-        pp.xt = use_exact3 ? ws + wl.xt : nullptr;
+        const bool triples = pn.form == CVAE_EVAL_V6;      // k_gru_steps_v6 reads limb triples, every other kernel the fp32 buffers
+        pp.hx = triples ? ws + wl.hs : nullptr;    // (the pair buffer's space: same size, never both in one pass)
+        pp.xt = triples ? ws + wl.xt : nullptr;
         pp.nxt_slack = (int)wl.xt_slack;
-        pp.hs = (!use_exact3 && (flags & CVAE_FLAG_SPLIT_F16)) ? ws + wl.hs : nullptr;
-        pp.xs = pp.hs ? ws + wl.xs : nullptr;
+        pp.hs = pn.pairs ? ws + wl.hs : nullptr;
+        pp.xs = pn.pairs ? ws + wl.xs : nullptr;
         pp.xs_plane = wl.xs_plane;
         // bar (8 words) ... flags are not adjacent: zero the flags here, the barrier words with the status block
-        pp.zero_words = hflags; pp.nzero = nrt * m.nch;
+        pp.zero_words = hflags; pp.nzero = wl.Bp / 16 * m.nch;
         pp.zero_status = clear_status ? status : nullptr;     // (the recurrent kernel, the first writer of these words, runs behind the prologue)
         pp.zero_status_n = cx().status_sink ? 4 : 8;          // (a sink is int32[4]: eight words ran over the end of the caller's buffer)
-        pp.ll_counter = use_ll ? (unsigned*)(ws + wl.status) + 16 : nullptr;
-        pp.nA = (use_exact3 ? wl.Bp / 32 : Brows) * wl.Tp;      // v6: one block per (32-row tile, padded frame)
+        pp.ll_counter = pn.form == CVAE_EVAL_LL ? (unsigned*)(ws + wl.status) + 16 : nullptr;
+        pp.nA = (pn.prologue == PRO_TILES ? wl.Bp / 32 : Brows) * wl.Tp;      // PRO_TILES: one block per (32-row tile, padded frame)
         pp.nH = (int)nblk((long)wl.Bp * m.H, 1024);
         pp.nD = (int)nblk((long)Brows * m.Co, 64);
-        bool any_h_in = false;
-        for (int c = 0; c < ncell; ++c) any_h_in = any_h_in || cells[c].h_in != nullptr;
-        gx0_ready = use_exact3 && !any_h_in && m.H3 % 4 == 0 && !opt(OPT_T0_IN_KERNEL);
-        pp.nG = gx0_ready ? (int)nblk((long)Brows * m.H3 / 4, 256) : 0;
+        pp.nG = pn.gx0_ready ? (int)nblk((long)Brows * m.H3 / 4, 256) : 0;
         pp.gx0 = ws + wl.gx0; pp.wyT = P + pl.wyT;
-        // (the pair copies are written whenever SPLIT_F16 is set, but only k_gru_steps_v5 reads them: a pass that ends up on
-        // k_gru_steps_ll or on an fp32-operand kernel has nothing to report)
-        range_params(pp, ws_status, use_exact3 || use_split5, clear_status, P, pl);
-        if (use_exact3)
-            hipLaunchKernelGGL((k_prologue), dim3(pp.nA + pp.nH + pp.nD + pp.nG + 1), dim3(256),
+        range_params(pp, ws_status, pn.limbs, clear_status, P, pl);
+        const dim3 gp(pp.nA + pp.nH + pp.nD + pp.nG + 1);
+        if (pn.prologue == PRO_TILES)
+            hipLaunchKernelGGL((k_prologue), gp, dim3(256),
                                (size_t)32 * (m.C + 1) * sizeof(float) + (size_t)(m.Cp / 8) * 1280 + (size_t)32 * pp.L * sizeof(float), st, pp);
-        else if (many_draws)     // 256 threads per block: the draws of a frame are summed in parallel slices
-            hipLaunchKernelGGL((k_prologue), dim3(pp.nA + pp.nH + pp.nD + 1), dim3(256), (size_t)(m.C + 1024 + 256) * sizeof(float), st, pp);
+        else if (pn.prologue == PRO_DRAWS)     // 256 threads per block: the draws of a frame are summed in parallel slices
+            hipLaunchKernelGGL((k_prologue), gp, dim3(256), (size_t)(m.C + 1024 + 256) * sizeof(float), st, pp);
         else
-            hipLaunchKernelGGL((k_prologue), dim3(pp.nA + pp.nH + pp.nD + 1), dim3(64), m.C * sizeof(float), st, pp);
+            hipLaunchKernelGGL((k_prologue), gp, dim3(64), m.C * sizeof(float), st, pp);
     }
-    // (the barrier counter of the any-H persistent kernel is zeroed where that kernel is launched: the dataflow kernels do
-    // not use it, and a memset is a launch of its own)
-    const size_t step_lds = 4 * 64 * 20 * sizeof(float);
-    const bool want_persistent = (flags & CVAE_FLAG_PERSISTENT) && T > 1;
-    const bool small = (long)m.nch * wl.mtot * 64 < (1L << 31);
-    const bool tuned_ok = want_persistent && !(flags & CVAE_FLAG_GENERIC_STEP) && small &&
-                          (m.H == 1024 || m.H == 64) && cus >= m.nch;
-    int RT = m.nch > 0 ? cus / m.nch : 1;
-    RT = RT < 1 ? 1 : (RT > nrt ? nrt : RT);
-    if (opt(OPT_MAX_RT) >= 1 && opt(OPT_MAX_RT) < RT) RT = (int)opt(OPT_MAX_RT);   // tests: several row tiles per block on small problems
+
     const size_t lds2 = (4 * 16 * 84 + 16 * 16) * sizeof(float);
     const bool prof = (flags & CVAE_FLAG_PROFILE) && prof_begin(st, ncell * B, m.C);
-    bool launched = false;
-    // ---- at most three rows: input-side GEMM for all frames, then the word-exchange kernel
-    if (use_ll) {
+    // gx[b*Tp + t] = afold . xnp[b, t:t+R, :] + cfold for all frames: one GEMM over overlapping rows (lda = Cp), in front of every
+    // form whose kernel has no front-end of its own
+    const auto front_end_gemm = [&]() {
         const int M = Brows * wl.Tp, N = m.H3;
         hipLaunchKernelGGL((k_gemm_nt<4, 4, 2, 2, false>), dim3(nblk(N, 128), nblk(M, 128)), dim3(256), 0, st,
                            (const float*)xnp, (long)m.Cp, 0L, P + pl.afold, (long)m.Kfe, P + pl.cfold, gx, (long)m.H3,
                            M, N, m.Kfe);
+    };
+    // a refused cooperative launch (error handling, not selection: the plan only names kernels that exist)
+    const auto refused = [](hipError_t e) {
+        if (e == hipSuccess) return false;
+        (void)hipGetLastError();
+        return true;
+    };
+    int form = pn.form;      // steps down where a launch is refused
+    if (form == CVAE_EVAL_LL || form <= CVAE_EVAL_V2) front_end_gemm();
+    switch (form) {
+    case CVAE_EVAL_LL: {
         StepLLParams q;
         q.hbuf = hbuf; q.mtot = wl.mtot; q.xbuf = ws + wl.hs; q.wrec2 = P + pl.wrec2; q.gx = gx; q.gx_bstride = (long)wl.Tp * m.H3;
         q.bhn = P + pl.bhn; q.B = Brows; q.Bp = wl.Bp; q.H = m.H; q.T = T; q.status = status;
-        q.prof = (flags & CVAE_FLAG_STEP_TIMING) ? (long long*)(ws + wl.prof) : nullptr;
+        q.prof = step_prof;
         q.wyT = P + pl.wyT; q.dy = dy; q.Co = m.Co;
         q.dbg = (int*)(ws + wl.status);
-        q.backoff = opt(OPT_LL_BACKOFF) >= 0 ? (int)opt(OPT_LL_BACKOFF) : (Brows == 1 ? 22 : 20);   // swept per row count (round 4, after the prefetch reordering: profiles/r04_notes.md; round 2: 18 / 16)
+        q.backoff = pn.backoff;
         q.nonce_src = (const unsigned*)(ws + wl.status) + 16;
         const dim3 gl(m.H / 4);
         const size_t ldsl = (size_t)(2 * 64 * 49 + 4 * 48) * sizeof(float);
-        hipError_t e = Brows == 1 ? cvae_launch_coop(k_gru_steps_ll<1>, gl, dim3(256), ldsl, st, q)
-                     : Brows == 2 ? cvae_launch_coop(k_gru_steps_ll<2>, gl, dim3(256), ldsl, st, q)
-                                  : cvae_launch_coop(k_gru_steps_ll<3>, gl, dim3(256), ldsl, st, q);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(-3, "small-batch recurrent kernel failed to launch: %s", hipGetErrorString(e));
-        }
-        launched = true;
+        const hipError_t e = cvae_launch_coop(Brows == 1 ? k_gru_steps_ll<1> : Brows == 2 ? k_gru_steps_ll<2> : k_gru_steps_ll<3>, gl,
+                                              dim3(256), ldsl, st, q);
+        if (refused(e)) return fail(-3, "small-batch recurrent kernel failed to launch: %s", hipGetErrorString(e));
+        break;
     }
-    // ---- exact-operand fused kernel (fp16 triples, six MFMAs per product)
-    if (use_exact3) {
+    case CVAE_EVAL_V6: {
         Step6Params q;
         q.hbuf = hbuf; q.mtot = wl.mtot; q.hx = ws + wl.hs; q.wrec3 = P + pl.wrec_t; q.afold3 = P + pl.afold_t; q.w2s = P + pl.wrec_l2b;
         q.cfold = P + pl.cfold; q.bhn = P + pl.bhn; q.xt = ws + wl.xt; q.Tp = wl.Tp; q.Cp = m.Cp;
         q.B = Brows; q.Bp = wl.Bp; q.H = m.H; q.T = T; q.flags = hflags; q.status = status;
-        q.prof = (flags & CVAE_FLAG_STEP_TIMING) ? (long long*)(ws + wl.prof) : nullptr;
+        q.prof = step_prof;
         q.wyT = P + pl.wyT; q.dy = dy; q.Co = m.Co;
-        q.gx0 = gx0_ready ? ws + wl.gx0 : nullptr;
-        {   // the fp32 state copy is only read by the raw projection (y_last), k_hlast and the fallback projection kernels
-            bool need = v6_limbs(m) != 3 || opt(OPT_OLD_OUTPROJ);
-            for (int c = 0; c < ncell; ++c) need = need || cells[c].y_last != nullptr || cells[c].h_last != nullptr;
-            q.want_f32 = (need || (opt(OPT_EXP) & 16)) ? 1 : 0;     // (exp bit 4: always write it, for A/B measurements)
-        }
-        const int NB = m.H / 8, nrt32 = wl.Bp / 32;
-        int RT6 = cus / NB;
-        RT6 = RT6 < 1 ? 1 : (RT6 > nrt32 ? nrt32 : RT6);
-        if (opt(OPT_MAX_RT) >= 1 && opt(OPT_MAX_RT) < RT6) RT6 = (int)opt(OPT_MAX_RT);
-        q.rts = RT6;
+        q.gx0 = pn.gx0_ready ? ws + wl.gx0 : nullptr;
+        q.want_f32 = pn.want_f32 ? 1 : 0;
+        q.rts = pn.rts;
         q.exp = (int)opt(OPT_EXP);   // measurement switches only
-        // One row tile per block (B <= 64 at hu1024): nothing can be published before the other blocks' front-ends are through, and
-        // 256 waves polling through that window slow the publishes and operand loads they wait for.  The decoder's front-end is a
-        // quarter shorter than the encoder's (KFW 6 vs 8), so its blocks arrive at the poll earlier: swept on MI355X
-        // (tools/ab_eval_exp.sh, round 5), 64-cycle units -- decoder pass 421.7 (0) / 405.8 (4) / 397.1 (8) / 401.0 (12) / 409.0 us
-        // (16), encoder pass 412.3 / 411.0 / 416.6 / 423.9 / 434.5 us.
-        q.backoff = opt(OPT_V6_BACKOFF) >= 0 ? (int)opt(OPT_V6_BACKOFF) : (m.H == 1024 ? (m.KFW <= 6 ? 8 : 2) : 0);
+        q.backoff = pn.backoff;
         const size_t lds6 = (size_t)(4 * 32 * 40 + 32 * 8 + 384 + 4 * m.KFW * v6_limbs(m) * 256) * sizeof(float);
-        const dim3 g6(NB * RT6);
-        hipError_t e = hipErrorUnknown;
-        if (m.H == 1024 && m.KFW == 8) e = cvae_launch_coop(k_gru_steps_v6<16, 8>, g6, dim3(256), lds6, st, q);
-        else if (m.H == 1024 && m.KFW == 6) e = cvae_launch_coop(k_gru_steps_v6<16, 6>, g6, dim3(256), lds6, st, q);
-        else if (m.H == 2048 && v6_limbs(m) == 2 && m.KFW == 8) e = cvae_launch_coop(k_gru_steps_v6<32, 8, 2>, g6, dim3(256), lds6, st, q);
-        else if (m.H == 2048 && v6_limbs(m) == 2 && m.KFW == 11) e = cvae_launch_coop(k_gru_steps_v6<32, 11, 2>, g6, dim3(256), lds6, st, q);
-        else if (m.H == 2048 && m.KFW == 8) e = cvae_launch_coop(k_gru_steps_v6<32, 8, 3, true>, g6, dim3(256), lds6, st, q);
-        else if (m.H == 2048 && m.KFW == 11) e = cvae_launch_coop(k_gru_steps_v6<32, 11, 3, true>, g6, dim3(256), lds6, st, q);
-        else if (m.H == 64 && v6_w2s(m) && m.KFW == 3) e = cvae_launch_coop(k_gru_steps_v6<1, 3, 3, true>, g6, dim3(256), lds6, st, q);
-        else if (m.H == 64 && v6_w2s(m) && m.KFW == 2) e = cvae_launch_coop(k_gru_steps_v6<1, 2, 3, true>, g6, dim3(256), lds6, st, q);
-        else if (m.H == 64 && v6_w2s(m) && m.KFW == 1) e = cvae_launch_coop(k_gru_steps_v6<1, 1, 3, true>, g6, dim3(256), lds6, st, q);
-        else if (m.H == 64 && v6_limbs(m) == 2 && m.KFW == 3) e = cvae_launch_coop(k_gru_steps_v6<1, 3, 2>, g6, dim3(256), lds6, st, q);
-        else if (m.H == 64 && v6_limbs(m) == 2 && m.KFW == 2) e = cvae_launch_coop(k_gru_steps_v6<1, 2, 2>, g6, dim3(256), lds6, st, q);
-        else if (m.H == 64 && v6_limbs(m) == 2 && m.KFW == 1) e = cvae_launch_coop(k_gru_steps_v6<1, 1, 2>, g6, dim3(256), lds6, st, q);
-        else if (m.H == 64 && m.KFW == 3) e = cvae_launch_coop(k_gru_steps_v6<1, 3>, g6, dim3(256), lds6, st, q);
-        else if (m.H == 64 && m.KFW == 2) e = cvae_launch_coop(k_gru_steps_v6<1, 2>, g6, dim3(256), lds6, st, q);
-        else if (m.H == 64 && m.KFW == 1) e = cvae_launch_coop(k_gru_steps_v6<1, 1>, g6, dim3(256), lds6, st, q);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(-3, "exact-operand recurrent kernel failed to launch: %s", hipGetErrorString(e));
-        }
-        launched = true;
+        const hipError_t e = cvae_launch_coop(pn.k6, dim3(m.H / 8 * pn.rts), dim3(256), lds6, st, q);
+        if (refused(e)) return fail(-3, "exact-operand recurrent kernel failed to launch: %s", hipGetErrorString(e));
+        break;
     }
-    // ---- fused kernel: front-end + recurrence in one cooperative launch (no gx buffer, no GEMM launch)
-    if (!launched && tuned_ok && !(flags & CVAE_FLAG_HOISTED_FRONTEND) && (m.KFW == 8 || m.KFW == 6 || m.KFW <= 2)) {
+    case CVAE_EVAL_V5:
+    case CVAE_EVAL_V4: {      // front-end + recurrence in one launch (no gx buffer, no GEMM launch), block = (16 hidden units) x (row tiles)
         Step3Params q;
-        q.hbuf = hbuf; q.mtot = wl.mtot; q.wrec2 = P + pl.wrec2; q.afold2 = nullptr; q.cfold = P + pl.cfold;
+        q.hbuf = hbuf; q.mtot = wl.mtot; q.wrec2 = P + pl.wrec2; q.cfold = P + pl.cfold;
         q.xnp = xnp; q.Tp = wl.Tp; q.Cp = m.Cp; q.bhn = P + pl.bhn; q.B = Brows; q.Bp = wl.Bp; q.H = m.H; q.T = T;
         q.flags = hflags; q.status = status;
-        q.prof = (flags & CVAE_FLAG_STEP_TIMING) ? (long long*)(ws + wl.prof) : nullptr;
+        q.prof = step_prof;
         q.wyT = P + pl.wyT; q.dy = dy; q.Co = m.Co;
-        hipError_t e = hipErrorUnknown;
-        q.rts = RT;
+        q.rts = pn.rts;
         q.hs = ws + wl.hs; q.wrec_h = P + pl.wrec_h; q.xs = ws + wl.xs; q.xs_plane = wl.xs_plane;
-        if ((flags & CVAE_FLAG_SPLIT_F16) && m.H % 32 == 0) {
-            // v5: v4 with the recurrent product as three fp16 MFMAs on (hi, lo) pairs
-            Step3Params q5 = q;
-            q5.afold2 = P + pl.afold_h;
-            q5.exp = (int)opt(OPT_EXP);   // measurement switches only
+        q.exp = (int)opt(OPT_EXP);   // measurement switches only
+        const dim3 g(m.nch * pn.rts);
+        if (form == CVAE_EVAL_V5) {   // v4 with the recurrent product as three fp16 MFMAs on (hi, lo) pairs
+            q.afold2 = P + pl.afold_h;
             const size_t lds5 = lds2 + (size_t)4 * ((m.KFW + 1) / 2) * 6 * 256 * sizeof(float);
-            const dim3 g5(m.nch * RT);
-            if (m.H == 1024 && m.KFW == 8) e = cvae_launch_coop(k_gru_steps_v5<16, 8>, g5, dim3(256), lds5, st, q5);
-            else if (m.H == 1024 && m.KFW == 6) e = cvae_launch_coop(k_gru_steps_v5<16, 6>, g5, dim3(256), lds5, st, q5);
-            else if (m.H == 64 && m.KFW == 2) e = cvae_launch_coop(k_gru_steps_v5<1, 2>, g5, dim3(256), lds5, st, q5);
-            else if (m.H == 64 && m.KFW == 1) e = cvae_launch_coop(k_gru_steps_v5<1, 1>, g5, dim3(256), lds5, st, q5);
-            if (e == hipSuccess) launched = true; else (void)hipGetLastError();
+            if (!refused(cvae_launch_coop(pn.k5, g, dim3(256), lds5, st, q))) break;
         }
-        if (!launched) {
-            // v4: front-end weights in LDS, double-buffered h operands
-            Step3Params q4 = q;
-            q4.afold2 = P + pl.afold3;
-            q4.exp = (int)opt(OPT_EXP);   // measurement switches only
-            const size_t lds4 = lds2 + (size_t)4 * m.KFW * 3 * 256 * sizeof(float);
-            const dim3 g4(m.nch * RT);
-            if (m.H == 1024 && m.KFW == 8) e = cvae_launch_coop(k_gru_steps_v4<16, 8>, g4, dim3(256), lds4, st, q4);
-            else if (m.H == 1024 && m.KFW == 6) e = cvae_launch_coop(k_gru_steps_v4<16, 6>, g4, dim3(256), lds4, st, q4);
-            else if (m.H == 64 && m.KFW == 2) e = cvae_launch_coop(k_gru_steps_v4<1, 2>, g4, dim3(256), lds4, st, q4);
-            else if (m.H == 64 && m.KFW == 1) e = cvae_launch_coop(k_gru_steps_v4<1, 1>, g4, dim3(256), lds4, st, q4);
-            if (e == hipSuccess) launched = true; else (void)hipGetLastError();
-        }
+        q.afold2 = P + pl.afold3;     // v4: front-end weights in LDS, double-buffered h operands
+        const size_t lds4 = lds2 + (size_t)4 * m.KFW * 3 * 256 * sizeof(float);
+        if (!refused(cvae_launch_coop(pn.k4, g, dim3(256), lds4, st, q))) break;
+        front_end_gemm();
+        form = CVAE_EVAL_V2;
     }
-    if (!launched) {
-        // gx[b*Tp + t] = afold . xnp[b, t:t+R, :] + cfold : one GEMM over overlapping rows (lda = Cp)
-        const int M = Brows * wl.Tp, N = m.H3;
-        hipLaunchKernelGGL((k_gemm_nt<4, 4, 2, 2, false>), dim3(nblk(N, 128), nblk(M, 128)), dim3(256), 0, st,
-                           (const float*)xnp, (long)m.Cp, 0L, P + pl.afold, (long)m.Kfe, P + pl.cfold, gx, (long)m.H3,
-                           M, N, m.Kfe);
-    }
-    // ---- tuned 2-D kernel with a hoisted front-end GEMM: block = (16 hidden units) x (row tiles i0, i0+RT, ...)
-    if (!launched && tuned_ok) {
+        [[fallthrough]];
+    case CVAE_EVAL_V2: {      // the same block geometry behind the hoisted front-end GEMM
         Step2Params q;
         q.hbuf = hbuf; q.mtot = wl.mtot; q.wrec2 = P + pl.wrec2; q.gx = gx; q.gx_bstride = (long)wl.Tp * m.H3;
         q.bhn = P + pl.bhn; q.B = Brows; q.Bp = wl.Bp; q.H = m.H; q.T = T; q.flags = hflags; q.status = status;
-        q.prof = (flags & CVAE_FLAG_STEP_TIMING) ? (long long*)(ws + wl.prof) : nullptr;
+        q.prof = step_prof;
         q.wyT = P + pl.wyT; q.dy = dy; q.Co = m.Co;
-        hipError_t e = m.H == 1024 ? cvae_launch_coop(k_gru_steps_v2<16>, dim3(m.nch, RT), dim3(256), lds2, st, q)
-                                   : cvae_launch_coop(k_gru_steps_v2<1>, dim3(m.nch, RT), dim3(256), lds2, st, q);
-        if (e == hipSuccess) launched = true; else (void)hipGetLastError();
+        if (!refused(cvae_launch_coop(m.H == 1024 ? k_gru_steps_v2<16> : k_gru_steps_v2<1>, dim3(m.nch, pn.rts), dim3(256), lds2, st, q))) break;
+        form = generic_resident(m, cus) ? CVAE_EVAL_GENERIC : CVAE_EVAL_PER_STEP;
     }
-    if (!launched) {
+        [[fallthrough]];
+    default: {                // CVAE_EVAL_GENERIC, CVAE_EVAL_PER_STEP: the any-H kernel
+        const size_t step_lds = 4 * 64 * 20 * sizeof(float);
         StepParams sp;
         sp.hbuf = hbuf; sp.mtot = wl.mtot; sp.wrec = P + pl.wrec; sp.gx = gx; sp.gx_bstride = (long)wl.Tp * m.H3;
         sp.bhn = P + pl.bhn; sp.B = Brows; sp.Bp = wl.Bp; sp.H = m.H; sp.T = T; sp.t0 = 0; sp.bar = bar; sp.status = status;
         sp.nwg = (unsigned)(m.H / 4);
         sp.prof = nullptr;
         sp.wyT = P + pl.wyT; sp.dy = dy; sp.Co = m.Co;
-        // every block of a persistent launch must be resident: one 256-thread block per CU is always admitted
-        if (want_persistent && (cus <= 0 || (int)sp.nwg <= cus)) {
+        if (form == CVAE_EVAL_GENERIC) {
+            // (the barrier counter is zeroed here, where its only user is launched: a memset is a launch of its own)
             CVAE_HIP_OK(hipMemsetAsync(bar, 0, 8 * sizeof(unsigned), st));
-            hipError_t e = hipSuccess;
-            e = cvae_launch_coop(k_gru_steps<true>, dim3(sp.nwg), dim3(256), step_lds, st, sp);
-            if (e == hipSuccess) launched = true; else (void)hipGetLastError();
+            if (!refused(cvae_launch_coop(k_gru_steps<true>, dim3(sp.nwg), dim3(256), step_lds, st, sp))) break;
         }
-        if (!launched) {
-            for (int t = 0; t < T; ++t) {
-                sp.t0 = t;
-                hipLaunchKernelGGL((k_gru_steps<false>), dim3(sp.nwg), dim3(256), step_lds, st, sp);
-            }
+        for (int t = 0; t < T; ++t) {
+            sp.t0 = t;
+            hipLaunchKernelGGL((k_gru_steps<false>), dim3(sp.nwg), dim3(256), step_lds, st, sp);
         }
+    }
     }
     if (prof) prof_end(st);
 
-    bool want_raw = false;
-    for (int c = 0; c < ncell; ++c) want_raw = want_raw || cells[c].y_last != nullptr;
-    const int ntn = m.Cop / 16;
-    if (!want_raw && use_exact3 && v6_limbs(m) == 3 && !opt(OPT_OLD_OUTPROJ)) {
-        // the v6 pass left the state as limb triples in the exchange buffer: project from there, same exact arithmetic
+    if (pn.proj == PROJ_V6) {
         Out6Params op;
         op.hx = ws + wl.hs; op.mtot = wl.mtot; op.wo3 = P + pl.wo3; op.bo2 = P + pl.bo2; op.H = m.H; op.Bp = wl.Bp; op.T = T;
         op.B = B; op.ncell = ncell; op.Co = m.Co; op.clamp_from = d->has_scale_out ? -1 : clamp_dim(clamp_lat_dim);
         op.clamp_min = clamp_floor(clamp_lat_dim);
         for (int c = 0; c < CVAE_MAX_CELLS; ++c) op.out[c] = c < ncell ? cells[c].trj_out : nullptr;
         const dim3 g((unsigned)((long)T * wl.Bp / 32), (unsigned)((m.Cop + 31) / 32));
-        const size_t lds = (size_t)4 * 32 * 36 * sizeof(float);
-        if (m.H == 1024) hipLaunchKernelGGL((k_outproj_v6<16>), g, dim3(256), lds, st, op);
-        else if (m.H == 2048) hipLaunchKernelGGL((k_outproj_v6<32>), g, dim3(256), lds, st, op);
-        else hipLaunchKernelGGL((k_outproj_v6<1>), g, dim3(256), lds, st, op);
-    } else if (!want_raw && (ntn == 1 || ntn == 4 || ntn == 8)) {
+        hipLaunchKernelGGL(pn.kout6, g, dim3(256), (size_t)4 * 32 * 36 * sizeof(float), st, op);
+    } else if (pn.proj == PROJ_FUSED) {
         // fused projection: scale_out folded in, clamp, written straight into [B][T][Co]
         OutParams op;
         op.hbuf = hbuf; op.mtot = wl.mtot; op.wo2 = P + pl.wo2; op.bo2 = P + pl.bo2; op.H = m.H; op.Bp = wl.Bp; op.T = T;
         op.B = B; op.ncell = ncell; op.Co = m.Co; op.clamp_from = d->has_scale_out ? -1 : clamp_dim(clamp_lat_dim);
         op.clamp_min = clamp_floor(clamp_lat_dim);
         for (int c = 0; c < CVAE_MAX_CELLS; ++c) op.out[c] = c < ncell ? cells[c].trj_out : nullptr;
+        const int ntn = m.Cop / 16;
         const unsigned nb = (unsigned)((long)T * wl.Bp / 16);
         const size_t lds = (size_t)4 * 16 * (m.Cop + 4) * sizeof(float);
-        if (ntn == 1) hipLaunchKernelGGL((k_outproj<1>), dim3(nb), dim3(256), lds, st, op);
-        else if (ntn == 4) hipLaunchKernelGGL((k_outproj<4>), dim3(nb), dim3(256), lds, st, op);
-        else hipLaunchKernelGGL((k_outproj<8>), dim3(nb), dim3(256), lds, st, op);
+        void (*const kout)(OutParams) = ntn == 1 ? k_outproj<1> : ntn == 4 ? k_outproj<4> : k_outproj<8>;
+        hipLaunchKernelGGL(kout, dim3(nb), dim3(256), lds, st, op);
     } else {
         // y[t*Bp + b] = out_1(h_t): A = hbuf slots 1..T (chunk-major), rows offset by Bp; then the epilogue kernel
         const int M = T * wl.Bp, N = m.Co;
@@ -907,6 +948,14 @@ size_t cvae_pass_workspace_bytes(cvae_ctx* ctx, const cvae_net_desc* d, int B, i
     Dims m;
     if (make_dims(d, &m) || B < 1 || T < 1) return 0;
     return (size_t)work_layout(m, B, T).total * sizeof(float);
+}
+
+int cvae_plan_pass(cvae_ctx* ctx, const cvae_net_desc* d, int rows, int T, int flags) {
+    CVAE_ENTER(ctx);
+    Dims m;
+    if (int rc = make_dims(d, &m)) return rc;
+    if (rows < 1 || T < 1) return fail(-1, "bad sizes: rows=%d T=%d", rows, T);
+    return plan_eval_pass(m, rows, T, flags, cu_count(), false, PassFacts{}).form;
 }
 
 int cvae_gru_rnn_forward(cvae_ctx* ctx, const cvae_net_desc* d, const void* prepared, const cvae_pass_input* in, const float* y_in,
@@ -1145,8 +1194,10 @@ int cvae_step_timing(cvae_ctx* ctx, const cvae_net_desc* d, int B, int T, const 
     if (int rc = make_dims(d, &m)) return rc;
     if (!workspace || !out || B < 1 || T < 1) return fail(-1, "bad argument");
     const Work wl = work_layout(m, B, T);
-    const int nrt = wl.Bp / 16;
-    const int nwg = m.nch * (nrt < 4 ? nrt : 4) > 256 ? 256 : m.nch * (nrt < 4 ? nrt : 4);
+    // one counter block per workgroup of the tuned kernel the documented flags select (the 16-row dataflow kernels; k_gru_steps_v6
+    // launches as many at H = 1024), as far as the workspace's counter area reaches
+    const EvalPlan pn = plan_eval_pass(m, B, T, CVAE_FLAG_PERSISTENT, cu_count(), false, PassFacts{});
+    const int nwg = pn.rts < 1 ? 1 : (m.nch * pn.rts > wl.prof_blocks ? wl.prof_blocks : m.nch * pn.rts);
     std::vector<long long> h((size_t)nwg * 4);
     CVAE_HIP_OK(hipMemcpyAsync(h.data(), (const float*)workspace + wl.prof, h.size() * sizeof(long long),
                                hipMemcpyDeviceToHost, (hipStream_t)stream));

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CVAE_ABI_VERSION 8
+#define CVAE_ABI_VERSION 9
 
 /* Shape of one reference GRU_RNN (src/nets/gru_vae.py:282-320). */
 typedef struct cvae_net_desc {
@@ -166,7 +166,6 @@ int cvae_set_draw_parts(cvae_ctx* ctx, int32_t parts);
  *   "no_ll"             0        1: passes of <= 3 rows run the dataflow kernel instead of the word-exchange kernel k_gru_steps_ll
  *   "ll_backoff"        -1       >= 0: s_sleep units before the first poll of a step in k_gru_steps_ll (-1: swept default)
  *   "v6_limbs_h64"      3        2: the two-limb form of k_gru_steps_v6 (what H = 2048 runs) at H = 64, for the emulator tests
- *   "old_outproj"       0        1: projection of an exact-operand pass from the fp32 state copy instead of the limb triples
  *   "exp"               0        measurement switches of the dataflow kernels (bit layout: Step6Params::exp)
  *   "train_kernel"      0        training recurrences: 0 exact fp32 operands (three fp16 limbs), non-zero fp16 pairs (22 bits)
  *   "bwd_overflow_at"   60000    |gate gradient * 2^8| from which the persistent reverse recurrences raise status 5 (tests lower it)
@@ -183,7 +182,6 @@ int cvae_set_draw_parts(cvae_ctx* ctx, int32_t parts);
  *                                with the third weight limb streamed from L2
  *   "v6_w2s_h64"        0        1: that streamed form at H = 64, for the emulator tests
  *   "step_col_tiles"    0        per-step forward training kernel (any-H path): 16-column tiles per block, 0 = pick, 1 / 2 = force
- *   "t0_in_kernel"      0        1: k_gru_steps_v6 forms the frame-0 feedback correction itself instead of reading the prologue's
  *   "coop_launch"       0        1: the all-resident recurrent kernels are launched with hipLaunchCooperativeKernel (residency
  *                                checked by the runtime at every launch, ~27 us of idle GPU around each one on MI355X);
  *                                0: residency checked once per kernel through the occupancy query, then plain launches
@@ -272,6 +270,24 @@ size_t cvae_pass_workspace_bytes(cvae_ctx* ctx, const cvae_net_desc* d, int B, i
 
 #define CVAE_STATUS_RANGE 7        /* status code of an operand outside the window of the limb form (cvae_set_status_sink, ABI 8) */
 #define CVAE_STATUS_RANGE_WORD 3   /* the status word that carries it */
+
+/*
+ * ABI 9: the recurrence an eval pass of a one-layer network with `rows` batch rows in all (cells x B of the stacked entry points)
+ * would take on the current device under this context's options -- the one-layer counterpart of cvae_plan_pass_deep; the rule
+ * table is DESIGN.md 4.1.  Negative = error.  Like the deep query it sees no image and no per-call pointers: a pass on an image
+ * the context knows to be unfit (cvae_net_prepared_in_range) takes what this reports for flags & ~CVAE_FLAG_SPLIT_F16, with
+ * CVAE_FLAG_EXACT3 ignored for passes of more than three rows.
+ */
+typedef enum cvae_eval_form {
+    CVAE_EVAL_PER_STEP = 0, /* k_gru_steps<false>, one launch per step, behind the front-end GEMM                       */
+    CVAE_EVAL_GENERIC = 1,  /* k_gru_steps<true>: the any-H kernel as one launch behind a grid barrier, front-end GEMM   */
+    CVAE_EVAL_V2 = 2,       /* k_gru_steps_v2: 16-row dataflow kernel behind the front-end GEMM                          */
+    CVAE_EVAL_V4 = 3,       /* k_gru_steps_v4: front-end fused, fp32 MFMA                                                */
+    CVAE_EVAL_V5 = 4,       /* k_gru_steps_v5: front-end fused, fp16 pairs                                               */
+    CVAE_EVAL_V6 = 5,       /* k_gru_steps_v6: 32-row tiles, exact fp32 operands as fp16 limbs                           */
+    CVAE_EVAL_LL = 6        /* k_gru_steps_ll: at most three rows, word exchange, behind the front-end GEMM              */
+} cvae_eval_form;
+int cvae_plan_pass(cvae_ctx* ctx, const cvae_net_desc* d, int rows, int T, int flags);
 
 /*
  * One GRU_RNN.forward in eval mode (gru_vae.py:322-455, live branch: res/noise/softmax/... flags off).
