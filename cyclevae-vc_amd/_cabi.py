@@ -7,7 +7,7 @@ library is missing or its ABI version differs, loading raises.
 import ctypes as C
 import os
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 FLAG_PERSISTENT = 1
 FLAG_PROFILE = 2
 FLAG_GENERIC_STEP = 4
@@ -31,11 +31,12 @@ class NetDesc(C.Structure):
 
 
 WEIGHT_FIELDS = ("scale_in_w", "scale_in_b", "conv0_w", "conv0_b", "conv1_w", "conv1_b", "w_ih", "w_hh", "b_ih",
-                 "b_hh", "out_w", "out_b", "scale_out_w", "scale_out_b")
+                 "b_hh", "out_w", "out_b", "scale_out_w", "scale_out_b", "conv2_w", "conv2_b")      # conv2_*: ABI 10, dilation_size == 3
 
 # C field -> reference state_dict key
 STATE_KEYS = {"scale_in_w": "scale_in.weight", "scale_in_b": "scale_in.bias", "conv0_w": "conv.conv.0.weight",
               "conv0_b": "conv.conv.0.bias", "conv1_w": "conv.conv.1.weight", "conv1_b": "conv.conv.1.bias",
+              "conv2_w": "conv.conv.2.weight", "conv2_b": "conv.conv.2.bias",
               "w_ih": "gru.weight_ih_l0", "w_hh": "gru.weight_hh_l0", "b_ih": "gru.bias_ih_l0",
               "b_hh": "gru.bias_hh_l0", "out_w": "out_1.weight", "out_b": "out_1.bias",
               "scale_out_w": "scale_out.weight", "scale_out_b": "scale_out.bias"}
@@ -59,7 +60,7 @@ def upper_layer_keys(n_layers):
 
 
 DEEP_PER_STEP, DEEP_GENERIC, DEEP_RESIDENT = 0, 1, 2      # cvae_plan_pass_deep
-EVAL_PER_STEP, EVAL_GENERIC, EVAL_V2, EVAL_V4, EVAL_V5, EVAL_V6, EVAL_LL = range(7)      # cvae_plan_pass (cvae_eval_form)
+EVAL_PER_STEP, EVAL_GENERIC, EVAL_V2, EVAL_V4, EVAL_V5, EVAL_V6, EVAL_LL, EVAL_V6H = range(8)      # cvae_plan_pass (cvae_eval_form)
 MAX_LAYERS = 8                                              # CVAE_DEEP_MAX_LAYERS
 
 
@@ -394,7 +395,7 @@ class CvaeLib(object):
         return n
 
     def plan_pass(self, d, rows, T, flags=0):
-        """EVAL_PER_STEP .. EVAL_LL: the recurrence a one-layer eval pass of `rows` batch rows in all takes."""
+        """EVAL_PER_STEP .. EVAL_V6H: the recurrence a one-layer eval pass of `rows` batch rows in all takes."""
         rc = self.lib.cvae_plan_pass(C.byref(d), rows, T, flags)
         if rc < 0:
             self._check(rc, "cvae_plan_pass")

@@ -282,7 +282,7 @@ int cvae_net_prepare_deep(cvae_ctx* ctx, const cvae_net_desc* d, int n_layers, c
     float* P = (float*)prepared;
     float* PD = P + pl.total;
     CVAE_HIP_OK(hipMemsetAsync(PD, 0, (size_t)dl.total * sizeof(float), st));
-    hipLaunchKernelGGL((k_prep_ffold), dim3(nblk((long)m.H3 * (m.H / 4), 256)), dim3(256), 0, st, w->w_ih, w->out_w, PD + dl.ffold, m.c2,
+    hipLaunchKernelGGL((k_prep_ffold), dim3(nblk((long)m.H3 * (m.H / 4), 256)), dim3(256), 0, st, w->w_ih, w->out_w, PD + dl.ffold, m.cw,
                        m.Co, m.tot, m.H);
     for (int l = 0; l < n_layers; ++l) {
         const float* U = l == 0 ? PD + dl.ffold : upper[l - 1].w_ih;

@@ -54,6 +54,8 @@ struct Step6Params {
     int want_f32;        // write the fp32 copy of every new state to hbuf (the raw-projection / h_last paths read it; the limb projection does not)
     int exp;             // measurement-only switches (bit 0: operands from slot 0 every step; bit 1: XCD-aware block mapping; bits 2-3: reporting wave; bits 8..: poll back-off override)
     int backoff;         // x 64 cycles a block with ONE row tile sleeps before the first flag poll of a step (swept per front-end width, cvae_lib.hip)
+    const float* gx;     // KFW == 0 (hoisted front-end): the input-side pre-activations of every frame, cfold included, from the front-end GEMM:
+    long gx_bstride;     //   row b, frame t, gate column n at gx[b * gx_bstride + t * 3H + n]; rows < B only
 };
 
 // wrec3[c][wave][s][m][lane][e]: the folded recurrent weights (wrec2, fp32) of unit octet c as fp16 triples in the operand
@@ -131,6 +133,10 @@ __device__ __forceinline__ f32x16 cvae_zero16() {
 // LIMBS = 3: exact fp32 operands (six MFMAs per product).  LIMBS = 2: the same kernel on (l0, l1) pairs only -- 22-23 bit
 // operands, three MFMAs per product, the arithmetic of k_gru_steps_v5 -- for H = 2048 (the hu2048 stress configuration), whose
 // 32 columns x 2048 k per block fill 256 registers per lane with TWO limbs; a third one cannot be resident at that width.
+// KFW = 0: the HOISTED form (plan form V6H) -- no front-end product, no input window, no LDS weight image: a thread's three gate
+// inputs of a task come from the fp32 GEMM in front of the launch (p.gx, cfold already in them) and are requested one task ahead,
+// where the fused form requests its window, so that they land under reduce + gates + publish.  For front-ends whose limb image
+// does not fit LDS (KFW >= 12: 27 taps x 56 channels).  The recurrent part is the same statements.
 // W2S (H = 2048 with three limbs): the third limbs of the recurrent weights are not resident (l0 and l1 of 32 columns x 2048 k fill
 // 256 registers per lane) but STREAMED from L2 every step as bf8 bytes (64 KB per block: the 32 blocks of an XCD share 2 MB, which
 // its L2 holds), through a ring of 4 steps; the operand rings shrink (5 recurrent steps, 3 front-end steps in flight) to make room
@@ -144,7 +150,8 @@ __global__ __launch_bounds__(256, 1) void k_gru_steps_v6(Step6Params p) {
 #endif
     constexpr int RD0 = W2S ? 5 : CVAE_V6_RD;
     constexpr int RD = KPW < RD0 ? KPW : RD0;          // operand ring: 16-k steps in flight per wave (8: swept 4..16 on MI355X)
-    constexpr int RF = W2S && KFW > 3 ? 3 : KFW;       // front-end operands: all requested ahead (they land during the publish)
+    constexpr bool HOIST = KFW == 0;
+    constexpr int RF = HOIST ? 1 : (W2S && KFW > 3 ? 3 : KFW);   // front-end operands: all requested ahead (they land during the publish)
     constexpr int RW = KPW < 4 ? KPW : 4;              // W2S: third weight limbs in flight
     const int tid = threadIdx.x, wave = cvae_uniform(tid >> 6), lane = tid & 63, lc = lane & 31, kh = lane >> 5;
     const int H = p.H, NB = H >> 3, nrt = p.Bp >> 5;
@@ -187,7 +194,7 @@ __global__ __launch_bounds__(256, 1) void k_gru_steps_v6(Step6Params p) {
     __syncthreads();
     const float* wfw = wfl + wave * (KFW * LIMBS * 256) + lane * 4;
     const float bhn = p.bhn[j];
-    const float cf0 = p.cfold[j], cf1 = p.cfold[H + j], cf2 = p.cfold[2 * H + j];
+    const float cf0 = HOIST ? 0.f : p.cfold[j], cf1 = HOIST ? 0.f : p.cfold[H + j], cf2 = HOIST ? 0.f : p.cfold[2 * H + j];
     const int ntile = ti < nrt ? (nrt - ti + rts - 1) / rts : 0, ntask = p.T * ntile;
     long long pc[4] = {0, 0, 0, 0};
     // front-end operands of task k: frame t's window = octet pieces [t*Cp/8, +9*Cp/8) of the tile (k = 8*piece + e), three
@@ -204,9 +211,20 @@ __global__ __launch_bounds__(256, 1) void k_gru_steps_v6(Step6Params p) {
         x4[2 * (s % RF) + 1] = *(const f32x4*)(xw + s * 2560 + 512 + lc * 16);
         if constexpr (LIMBS == 3) x2[s % RF] = *(const f32x2*)(xw + s * 2560 + 1024 + lc * 8);
     };
+    // HOIST: the gate inputs of task k, one (row, unit) per thread, three fp32 loads (rows beyond B: none, their gates are not formed)
+    float gq0 = 0.f, gq1 = 0.f, gq2 = 0.f;
+    auto load_g = [&](int k) {
+        const int tt = k / ntile, gr = (ti + (k % ntile) * rts) * 32 + row;
+        if (gr < p.B) {
+            const float* g = p.gx + (long)gr * p.gx_bstride + (long)tt * 3 * H + j;
+            gq0 = g[0]; gq1 = g[H]; gq2 = g[2 * H];
+        }
+    };
     float hkeep0 = 0.f, hkeep1 = 0.f;   // h_{t-1} of this thread's (row, unit), per tile for up to two tiles per block
     const int backoff = (p.exp >> 8) ? (p.exp >> 8) - 1 : p.backoff;     // x 64 cycles before the first poll (exp: measurement override)
-    if (ntask > 0) {
+    if constexpr (HOIST) {
+        if (ntask > 0) load_g(0);
+    } else if (ntask > 0) {
         set_x(0);
 #pragma unroll
         for (int s = 0; s < RF; ++s) load_x(s);
@@ -263,7 +281,7 @@ __global__ __launch_bounds__(256, 1) void k_gru_steps_v6(Step6Params p) {
         const int grow = i * 32 + row;
         const bool live = grow < p.B;
         const bool keep1 = ntile == 2 && (k & 1);
-        float gxr = cf0, gxz = cf1, gxn = cf2, hold = keep1 ? hkeep1 : hkeep0;
+        float gxr = HOIST ? gq0 : cf0, gxz = HOIST ? gq1 : cf1, gxn = HOIST ? gq2 : cf2, hold = keep1 ? hkeep1 : hkeep0;
         auto gate_inputs = [&]() {
             if (live) {
                 if (t == 0 && p.gx0) {
@@ -334,11 +352,15 @@ __global__ __launch_bounds__(256, 1) void k_gru_steps_v6(Step6Params p) {
         cvae_sched_fence();
         // next task's front-end operands.  xmode (measurement, exp bits 5-6): 0 = every wave requests them here (they land
         // under reduce + gates + publish), 1 = every wave after the publish, 2 = wave 0 (the publisher) after, the others here
-        const int xmode = (p.exp >> 5) & 3;
-        if (k + 1 < ntask) set_x(k + 1);
-        if (k + 1 < ntask && (xmode == 0 || (xmode == 2 && wave != 0))) {
+        const int xmode = HOIST ? 0 : (p.exp >> 5) & 3;
+        if constexpr (HOIST) {
+            if (k + 1 < ntask) load_g(k + 1);      // (this task's values were copied into gxr .. gxn above)
+        } else {
+            if (k + 1 < ntask) set_x(k + 1);
+            if (k + 1 < ntask && (xmode == 0 || (xmode == 2 && wave != 0))) {
 #pragma unroll
-            for (int s = 0; s < RF; ++s) load_x(s);
+                for (int s = 0; s < RF; ++s) load_x(s);
+            }
         }
 #pragma unroll
         for (int q = 0; q < 16; ++q)
@@ -384,9 +406,11 @@ __global__ __launch_bounds__(256, 1) void k_gru_steps_v6(Step6Params p) {
             *(f32x4*)(p.hbuf + (((long)(c >> 1) * p.mtot + row0 + p.Bp + r) * 16 + (c & 1) * 8 + half * 4)) =
                 *(const f32x4*)(hsh + r * 8 + half * 4);
         }
-        if (k + 1 < ntask && (xmode == 1 || (xmode == 2 && wave == 0))) {
+        if constexpr (!HOIST) {
+            if (k + 1 < ntask && (xmode == 1 || (xmode == 2 && wave == 0))) {
 #pragma unroll
-            for (int s = 0; s < RF; ++s) load_x(s);
+                for (int s = 0; s < RF; ++s) load_x(s);
+            }
         }
         if (ntile > 1 && k + 1 < ntask) {   // (behind wave 0's publish, so its drain never waits for this load)
             const int kn = k + 1, tn = kn / ntile, in_ = ti + (kn % ntile) * rts;

@@ -65,35 +65,48 @@ __device__ __forceinline__ float cvae_randn(uint64_t seed, uint64_t draw, uint64
 // ------------------------------------------------------------------------------------------------------
 // prepare-time kernels (run when the weights change)
 // ------------------------------------------------------------------------------------------------------
-// mfull[o][d][c] = sum_i conv1.w[o][i][j] * conv0.w[i][c][k], tap d = ks*j + k   (gru_vae.py:49-51,62-64)
-__global__ void k_prep_mfull(const float* w0, const float* w1, double* mfull, int C, int ks) {
-    const int c1 = ks * C, c2 = ks * ks * C, R = ks * ks;
+// The conv stack of TwoSidedDilConv1d folded into ONE matrix over the R = ks^layers input frames a GRU step sees, layer by layer
+// (gru_vae.py:39-66; conv n has kernel ks and dilation ks^n, so its tap j reaches the taps ks^n * j + d' of the input):
+//   M_0[o][k][c] = conv0.w[o][c][k],    M_n[o][ks^n * j + d'][c] = sum_i conv_n.w[o][i][j] * M_{n-1}[i][d'][c]
+//   b'_0 = conv0.b,                     b'_n[o] = conv_n.b[o] + sum_i sum_j conv_n.w[o][i][j] * b'_{n-1}[i]
+// (only conv0 pads, so its bias reaches every padded tap).  fp64 throughout: products of two floats are exact there.
+__global__ void k_prep_fold0(const float* w0, const float* b0, double* m0, double* bp0, int C, int ks) {
+    const int c1 = ks * C;
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx < (long)c2 * R * C) {
+    if (idx < (long)c1 * ks * C) {
+        const int c = (int)(idx % C), k = (int)((idx / C) % ks), o = (int)(idx / ((long)C * ks));
+        m0[idx] = (double)w0[((long)o * C + c) * ks + k];
+    }
+    if (idx < c1) bp0[idx] = (double)b0[idx];
+}
+
+// mn [cp*ks][rp*ks][C] from mp [cp][rp][C]: cp = input channels of conv n, rp = ks^n = taps folded so far
+__global__ void k_prep_fold_m(const float* wn, const double* mp, double* mn, int C, int ks, int cp, int rp) {
+    const int R = rp * ks;
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx < (long)cp * ks * R * C) {
         const int c = (int)(idx % C), d = (int)((idx / C) % R), o = (int)(idx / ((long)C * R));
-        const int j = d / ks, k = d % ks;
+        const int j = d / rp, dp = d % rp;
         double s = 0.0;
-        for (int i = 0; i < c1; ++i) s += (double)w1[((long)o * c1 + i) * ks + j] * (double)w0[((long)i * C + c) * ks + k];
-        mfull[idx] = s;
+        for (int i = 0; i < cp; ++i) s += (double)wn[((long)o * cp + i) * ks + j] * mp[((long)i * rp + dp) * C + c];
+        mn[idx] = s;
     }
 }
 
-// bprime[o] = conv1.b[o] + sum_j sum_i conv1.w[o][i][j] * conv0.b[i]   (conv0's bias reaches every padded tap)
-__global__ void k_prep_bprime(const float* b0, const float* w1, const float* b1, double* bprime, int C, int ks) {
-    const int c1 = ks * C, c2 = ks * ks * C;
+__global__ void k_prep_fold_b(const double* bp, const float* wn, const float* bn, double* bout, int ks, int cp) {
     const int o = blockIdx.x * blockDim.x + threadIdx.x;
-    if (o < c2) {
-        double s = (double)b1[o];
-        for (int i = 0; i < c1; ++i)
-            for (int j = 0; j < ks; ++j) s += (double)w1[((long)o * c1 + i) * ks + j] * (double)b0[i];
-        bprime[o] = s;
+    if (o < cp * ks) {
+        double s = (double)bn[o];
+        for (int i = 0; i < cp; ++i)
+            for (int j = 0; j < ks; ++j) s += (double)wn[((long)o * cp + i) * ks + j] * bp[i];
+        bout[o] = s;
     }
 }
 
-// afold[n][d*Cp + c] = sum_o W_ih[n][o] * mfull[o][d][c]  (zero in the Cp / Kfe padding)
-__global__ void k_prep_afold(const float* wih, const double* mfull, float* afold, int C, int Cp, int ks, int tot,
+// afold[n][d*Cp + c] = sum_o W_ih[n][o] * mfull[o][d][c]  (mfull: the last layer's M, R taps; zero in the Cp / Kfe padding)
+__global__ void k_prep_afold(const float* wih, const double* mfull, float* afold, int C, int Cp, int R, int tot,
                              int Kfe, int H3) {
-    const int R = ks * ks, c2 = R * C;
+    const int c2 = R * C;
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx < (long)H3 * Kfe) {
         const int kc = (int)(idx % Kfe), n = (int)(idx / Kfe);

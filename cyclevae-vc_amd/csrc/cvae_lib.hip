@@ -163,15 +163,23 @@ inline float clamp_floor(int v) { return v >= 0 && (v & CVAE_CLAMP_LAPLACE) ? -7
 inline unsigned nblk(long n, int per) { return (unsigned)((n + per - 1) / per); }
 
 struct Dims {
-    int C, Cp, Co, Cop, H, H3, ks, R, pad, c1, c2, tot, Kfe, nch, KFW;
+    int C, Cp, Co, Cop, H, H3, ks, layers, R, pad, cl[3], cw, tot, Kfe, nch, KFW;      // cl[i] = ks^(i+1) * C: output channels of conv i; cw = the last of them (what W_ih sees)
 };
 
 int make_dims(const cvae_net_desc* d, Dims* o) {
     if (!d) return fail(-1, "null net descriptor");
-    if (d->layers != 2) return fail(-1, "layers (reference dilation_size) must be 2, got %d", d->layers);
+    if (d->layers < 1 || d->layers > 3) return fail(-1, "layers (reference dilation_size) must be 1, 2 or 3, got %d", d->layers);
     if (d->kernel_size < 1 || d->kernel_size % 2 == 0) return fail(-1, "kernel_size must be odd, got %d", d->kernel_size);
     if (d->hidden < 16 || d->hidden % 16) return fail(-1, "hidden must be a positive multiple of 16, got %d", d->hidden);
     if (d->in_dim < 1 || d->out_dim < 1) return fail(-1, "bad in_dim/out_dim %d/%d", d->in_dim, d->out_dim);
+    if (d->layers == 3 && d->kernel_size != 3)
+        return fail(-1, "layers == 3 needs kernel_size == 3: a front-end of kernel_size^3 >= 125 frames is not supported, got kernel_size %d",
+                    d->kernel_size);
+    // Depth 3 is taken where the recurrences it was built for exist (k_gru_steps_ll and the hoisted exact-operand kernel want
+    // H % 64 == 0).  Narrower three-layer networks stay refused, as before ABI 10: tests/test_emu_library.py pins the refusal of
+    // (hidden 32, layers 3), and lifting it belongs with a change that may touch that test.
+    if (d->layers == 3 && d->hidden % 64)
+        return fail(-1, "layers == 3 needs hidden to be a multiple of 64, got %d", d->hidden);
     o->C = d->in_dim;
     o->Cp = (int)up(d->in_dim, 8);   // multiple of 8: eight consecutive fp16 halves of a window are one 16-byte MFMA operand
     o->Co = d->out_dim;
@@ -179,15 +187,42 @@ int make_dims(const cvae_net_desc* d, Dims* o) {
     o->H = d->hidden;
     o->H3 = 3 * d->hidden;
     o->ks = d->kernel_size;
-    o->R = o->ks * o->ks;
+    o->layers = d->layers;
+    o->R = 1;
+    o->cl[0] = o->cl[1] = o->cl[2] = 0;
+    for (int i = 0; i < o->layers; ++i) {
+        o->R *= o->ks;
+        o->cl[i] = o->R * o->C;
+    }
     o->pad = (o->R - 1) / 2;
-    o->c1 = o->ks * o->C;
-    o->c2 = o->R * o->C;
-    o->tot = o->c2 + o->Co;
+    o->cw = o->R * o->C;
+    o->tot = o->cw + o->Co;
     o->Kfe = (int)up((long)o->R * o->Cp, 16);
     o->nch = o->H / 16;
     o->KFW = (o->Kfe / 16 + 3) / 4;   // front-end 16-k chunks per wave in the fused recurrent kernel
     return 0;
+}
+
+// the training and backward entry points: their tape, segmented-row GEMMs and gradient chains are written for two conv layers
+int make_train_dims(const cvae_net_desc* d, Dims* o) {
+    if (int rc = make_dims(d, o)) return rc;
+    if (o->layers != 2)
+        return fail(-1, "training is implemented for layers (reference dilation_size) == 2 only, got %d (eval and conversion run 1..3)", o->layers);
+    return 0;
+}
+
+// Scratch of cvae_net_prepare (doubles): the fold walks the conv layers M_0 -> M_1 -> .., each from the one before, so two areas
+// alternate -- `a` holds M_{layers-1} (the final one, and M_{layers-3}), `b` M_{layers-2} -- and likewise the bias folds b'_n.
+struct FoldScratch { long ma, mb, ba, bb, total; };
+inline long fold_m_size(const Dims& m, int n) { return (long)m.cl[n] * (m.cl[n] / m.C) * m.C; }      // M_n [cl[n]][ks^(n+1)][C]
+inline FoldScratch fold_scratch(const Dims& m) {
+    FoldScratch f;
+    f.ma = 0;
+    f.mb = fold_m_size(m, m.layers - 1);
+    f.ba = f.mb + (m.layers > 1 ? fold_m_size(m, m.layers - 2) : 0);
+    f.bb = f.ba + m.cw;
+    f.total = f.bb + (m.layers > 1 ? m.cl[m.layers - 2] : 0) + 64;
+    return f;
 }
 
 // ---- Kernel instances of the eval recurrences: what is built, by geometry.  The layouts (is there a limb image to lay out?), the
@@ -199,11 +234,22 @@ int make_dims(const cvae_net_desc* d, Dims* o) {
 struct V6Inst { int H, KFW, limbs; bool w2s; void (*fn)(Step6Params); };
 const V6Inst g_v6_inst[] = {
     {1024, 8, 3, false, k_gru_steps_v6<16, 8>},       {1024, 6, 3, false, k_gru_steps_v6<16, 6>},
+    {1024, 3, 3, false, k_gru_steps_v6<16, 3>},       {1024, 2, 3, false, k_gru_steps_v6<16, 2>},       // a one-layer front-end (dilation_size 1): encoder in_dim 54, decoder 34
     {2048, 8, 3, true, k_gru_steps_v6<32, 8, 3, true>}, {2048, 11, 3, true, k_gru_steps_v6<32, 11, 3, true>},
     {2048, 8, 2, false, k_gru_steps_v6<32, 8, 2>},    {2048, 11, 2, false, k_gru_steps_v6<32, 11, 2>},
     {64, 3, 3, false, k_gru_steps_v6<1, 3>},          {64, 2, 3, false, k_gru_steps_v6<1, 2>},          {64, 1, 3, false, k_gru_steps_v6<1, 1>},
     {64, 3, 3, true, k_gru_steps_v6<1, 3, 3, true>},  {64, 2, 3, true, k_gru_steps_v6<1, 2, 3, true>},  {64, 1, 3, true, k_gru_steps_v6<1, 1, 3, true>},
     {64, 3, 2, false, k_gru_steps_v6<1, 3, 2>},       {64, 2, 2, false, k_gru_steps_v6<1, 2, 2>},       {64, 1, 2, false, k_gru_steps_v6<1, 1, 2>},
+};
+// k_gru_steps_v6<KPW, 0> (form V6H): the same recurrence with NO front-end of its own, behind the front-end GEMM -- for front-ends
+// whose limb image cannot live in LDS.  The fused kernel keeps that image at 4 waves x KFW steps x 3 limbs x 1 KiB = 12 KiB per
+// unit of KFW next to 22.5 KiB of reduction / publish buffers: KFW = 11 takes 132 + 22.5 = 154.5 of the 160 KiB a workgroup can
+// have, KFW = 12 would take 166.5.  So V6H_MIN_KFW = 12, whatever H.  Keyed by H alone.
+const int V6H_MIN_KFW = 12;
+const V6Inst g_v6h_inst[] = {
+    {1024, 0, 3, false, k_gru_steps_v6<16, 0>},
+    {2048, 0, 3, true, k_gru_steps_v6<32, 0, 3, true>},      // (three limbs, third weight limb streamed; no pair form: option v6_limbs_h2048 = 2 leaves such a pass on the per-step path)
+    {64, 0, 3, false, k_gru_steps_v6<1, 0>},          {64, 0, 3, true, k_gru_steps_v6<1, 0, 3, true>},  {64, 0, 2, false, k_gru_steps_v6<1, 0, 2>},
 };
 // the 16-row fused kernels: k_gru_steps_v5 (fp16 pairs) and k_gru_steps_v4 (fp32 MFMA), always built together
 struct Fused16Inst { int H, KFW; void (*v5)(Step3Params); void (*v4)(Step3Params); };
@@ -227,7 +273,15 @@ inline const Fused16Inst* find_fused16(const Dims& m) {
         if (i.H == m.H && i.KFW == m.KFW) return &i;
     return nullptr;
 }
-inline bool exact3_ok(const Dims& m) { return find_v6(m) != nullptr; }
+inline const V6Inst* find_v6h(const Dims& m, int limbs = -1, bool w2s = false) {
+    if (m.KFW < V6H_MIN_KFW) return nullptr;
+    for (const V6Inst& i : g_v6h_inst)
+        if (i.H == m.H && (limbs < 0 || (i.limbs == limbs && i.w2s == w2s))) return &i;
+    return nullptr;
+}
+inline bool exact3_fused(const Dims& m) { return find_v6(m) != nullptr; }      // front-end inside the kernel: limb image afold_t, limb input xt
+// an exact-operand geometry: 32-row tiles from 4 rows on, recurrent / projection limb images -- fused or behind the front-end GEMM
+inline bool exact3_ok(const Dims& m) { return exact3_fused(m) || find_v6h(m) != nullptr; }
 // the form of k_gru_steps_v6 the options pick at this H: limbs per operand, third weight limb streamed
 inline int v6_limbs(const Dims& m) {
     return (m.H == 64 && opt(OPT_V6_LIMBS_H64) == 2) || (m.H == 2048 && opt(OPT_V6_LIMBS_H2048) == 2) ? 2 : 3;
@@ -254,7 +308,7 @@ Prep prep_layout(const Dims& m, bool sin, bool sout) {
     // fp16-triple images of k_gru_steps_v6 (exact fp32 operands): recurrent B operands per (octet, wave, 16-k step, limb) and
     // the front-end LDS image; only for the sizes that kernel is built for
     p.wrec_t = exact3_ok(m) ? take((long)(m.H / 8) * 4 * exact3_kpw(m) * 3 * 256) : -1;
-    p.afold_t = exact3_ok(m) ? take((long)(m.H / 8) * 4 * m.KFW * 3 * 256) : -1;
+    p.afold_t = exact3_fused(m) ? take((long)(m.H / 8) * 4 * m.KFW * 3 * 256) : -1;
     p.wrec_l2b = exact3_ok(m) ? take((long)(m.H / 8) * 4 * exact3_kpw(m) * 128) : -1;   // third weight limbs as bf8 bytes (streamed form)
     p.bhn = take(m.H);
     p.wyT = take((long)m.H3 * m.Co);
@@ -280,7 +334,7 @@ struct Work {
 };
 
 // Batch rows are padded to whole row tiles: one 16-row tile for the word-exchange kernel (at most 3 rows), 32-row tiles
-// (k_gru_steps_v6: exact operands) from 4 rows on wherever that kernel exists -- ONE arithmetic width for every batch size, a pass
+// (k_gru_steps_v6: exact operands) from 4 rows on wherever that kernel exists (fused or hoisted: exact3_ok) -- ONE arithmetic width for every batch size, a pass
 // of 4..16 rows runs a half-empty tile rather than the 22-bit pair kernel -- else 16-row tiles up to 16 rows.  Independent of the
 // pass's flags: the workspace size query has none.
 inline int eval_row_pad(const Dims& m, int Brows) {
@@ -300,7 +354,7 @@ Work work_layout(const Dims& m, int Brows, int T) {
     w.xs = take(w.xs_plane);                                              // 2 planes x 2 bytes = xs_plane floats
     // k_gru_steps_v6's input: limb triples (5 bytes per element) + zero slack for the K padding of the last frames (16-bit words)
     w.xt_slack = (64L * m.KFW / 8 + 2) * 640 + 64;
-    w.xt = exact3_ok(m) && w.Bp % 32 == 0 ? take(((long)w.Bp * w.Tp * m.Cp * 5 / 2 + w.xt_slack) / 2 + 8) : -1;
+    w.xt = exact3_fused(m) && w.Bp % 32 == 0 ? take(((long)w.Bp * w.Tp * m.Cp * 5 / 2 + w.xt_slack) / 2 + 8) : -1;
     w.gx = take((long)Brows * w.Tp * m.H3);
     w.hbuf = take((long)m.nch * w.mtot * 16);
     w.hs = take((long)m.nch * w.mtot * 24);     // exchanged state as fp16 pairs (64 B per row and 16 units) or triples (96 B)
@@ -325,7 +379,7 @@ inline int row_tiles_per_block(int cus, int per_tile, int ntiles) {
 
 // Which kernels an eval pass of a one-layer network runs (the one place that decides; cvae_plan_pass reports the form; the table
 // of form x condition is DESIGN.md 4.1).  The forms are numbered so that a refused cooperative launch steps DOWN:
-// V5 -> V4 -> V2 -> GENERIC -> PER_STEP (run_pass; LL and V6 return the error).
+// V5 -> V4 -> V2 -> GENERIC -> PER_STEP (run_pass; LL, V6 and V6H return the error).
 struct PassFacts {      // what a call's pointers decide
     bool h_in, y_last, h_last, many_draws;      // any cell with a carried-in state / a raw last projection / a state out / n_draws > 1
 };
@@ -358,6 +412,7 @@ EvalPlan plan_eval_pass(const Dims& m, int Brows, int T, int flags, int cus, boo
     const bool persistent = (flags & CVAE_FLAG_PERSISTENT) && T > 1, generic = (flags & CVAE_FLAG_GENERIC_STEP) != 0;
     const bool hoisted = (flags & CVAE_FLAG_HOISTED_FRONTEND) != 0, exact = persistent && (flags & CVAE_FLAG_EXACT3) && !generic;
     const V6Inst* i6 = find_v6(m, v6_limbs(m), v6_w2s(m));
+    const V6Inst* i6h = find_v6h(m, v6_limbs(m), v6_w2s(m));
     const Fused16Inst* i16 = find_fused16(m);
     if (exact && Brows <= 3 && T < 65536 && m.H % 64 == 0 && m.H <= 1024 && cus >= m.H / 4 && !opt(OPT_NO_LL)) {
         // at most three rows: a step is one store + one polled load per unit, plain fp32 FMAs; H/4 blocks, every one resident
@@ -374,6 +429,14 @@ EvalPlan plan_eval_pass(const Dims& m, int Brows, int T, int flags, int cus, boo
         // (tools/ab_eval_exp.sh, round 5), 64-cycle units -- decoder pass 421.7 (0) / 405.8 (4) / 397.1 (8) / 401.0 (12) / 409.0 us
         // (16), encoder pass 412.3 / 411.0 / 416.6 / 423.9 / 434.5 us.
         pn.backoff = opt(OPT_V6_BACKOFF) >= 0 ? (int)opt(OPT_V6_BACKOFF) : (m.H == 1024 ? (m.KFW <= 6 ? 8 : 2) : 0);
+    } else if (exact && !unfit && !hoisted && i6h && Bp % 32 == 0 && cus >= m.H / 8 && (long)m.nch * mtot * 80 < (1L << 31)) {
+        // the same recurrence behind the front-end GEMM, for a front-end too wide for the LDS limb image (KFW >= 12: find_v6h).
+        // HOISTED_FRONTEND keeps its meaning -- the 16-row kernel behind the GEMM (V2) -- so that the two can be compared.
+        pn.form = CVAE_EVAL_V6H;
+        i6 = i6h;
+        pn.k6 = i6h->fn;
+        pn.rts = row_tiles_per_block(cus, m.H / 8, Bp / 32);
+        pn.backoff = opt(OPT_V6_BACKOFF) >= 0 ? (int)opt(OPT_V6_BACKOFF) : 0;      // (nothing runs in front of the poll; not swept)
     } else if (persistent && !generic && (m.H == 1024 || m.H == 64) && cus >= m.nch && (long)m.nch * mtot * 64 < (1L << 31)) {
         // the 16-row dataflow kernels (H/16 blocks per tile, every block resident): front-end fused where an instance exists for
         // the front-end width -- on fp16 pairs (V5) or the fp32 MFMA (V4) -- else behind a hoisted GEMM (V2)
@@ -384,7 +447,7 @@ EvalPlan plan_eval_pass(const Dims& m, int Brows, int T, int flags, int cus, boo
         // the any-H kernel: one launch behind a grid barrier when its H/4 blocks are resident, else one launch per step
         pn.form = persistent && generic_resident(m, cus) ? CVAE_EVAL_GENERIC : CVAE_EVAL_PER_STEP;
     }
-    const bool v6 = pn.form == CVAE_EVAL_V6;
+    const bool v6f = pn.form == CVAE_EVAL_V6, v6 = v6f || pn.form == CVAE_EVAL_V6H;      // fused; fused or hoisted
     pn.limbs = v6 || pn.form == CVAE_EVAL_V5;
     // the pair copies are written whenever SPLIT_F16 is set off V6, but only k_gru_steps_v5 reads them: a pass that ends up on
     // k_gru_steps_ll or on an fp32-operand kernel has nothing to report (limbs)
@@ -392,7 +455,8 @@ EvalPlan plan_eval_pass(const Dims& m, int Brows, int T, int flags, int cus, boo
     pn.gx0_ready = v6 && !f.h_in;
     // the fp32 state copy of a V6 pass is only read by the raw projection (y_last), k_hlast and the projections off the limb triples
     pn.want_f32 = v6 && (i6->limbs != 3 || f.y_last || f.h_last || (opt(OPT_EXP) & 16));      // (exp bit 4: always write it, for A/B measurements)
-    pn.prologue = v6 ? PRO_TILES : (f.many_draws ? PRO_DRAWS : PRO_ROWS);
+    // (V6H: the input goes through the fp32 GEMM -- no limb copy of it, the row-wise prologue; its range word then covers h_in only)
+    pn.prologue = v6f ? PRO_TILES : (f.many_draws ? PRO_DRAWS : PRO_ROWS);
     const int ntn = m.Cop / 16;
     if (!f.y_last && v6 && i6->limbs == 3) {
         pn.proj = PROJ_V6;      // the pass left the state as limb triples in the exchange buffer: project from there, same exact arithmetic
@@ -567,9 +631,10 @@ int run_pass(const Dims& m, const cvae_net_desc* d, const float* P, const Cell* 
         pp.nslack = 64 * m.KFW + 64;
         pp.mtot = wl.mtot;
         pp.xnp = xnp; pp.hbuf = hbuf; pp.dy = dy;
-        const bool triples = pn.form == CVAE_EVAL_V6;      // k_gru_steps_v6 reads limb triples, every other kernel the fp32 buffers
+        // k_gru_steps_v6 reads limb triples -- the state always, the input where its front-end is fused -- every other kernel the fp32 buffers
+        const bool triples = pn.form == CVAE_EVAL_V6 || pn.form == CVAE_EVAL_V6H;
         pp.hx = triples ? ws + wl.hs : nullptr;    // (the pair buffer's space: same size, never both in one pass)
-        pp.xt = triples ? ws + wl.xt : nullptr;
+        pp.xt = pn.form == CVAE_EVAL_V6 ? ws + wl.xt : nullptr;
         pp.nxt_slack = (int)wl.xt_slack;
         pp.hs = pn.pairs ? ws + wl.hs : nullptr;
         pp.xs = pn.pairs ? ws + wl.xs : nullptr;
@@ -582,7 +647,7 @@ int run_pass(const Dims& m, const cvae_net_desc* d, const float* P, const Cell* 
         pp.nA = (pn.prologue == PRO_TILES ? wl.Bp / 32 : Brows) * wl.Tp;      // PRO_TILES: one block per (32-row tile, padded frame)
         pp.nH = (int)nblk((long)wl.Bp * m.H, 1024);
         pp.nD = (int)nblk((long)Brows * m.Co, 64);
-        pp.nG = pn.gx0_ready ? (int)nblk((long)Brows * m.H3 / 4, 256) : 0;
+        pp.nG = pn.gx0_ready ? (int)nblk((long)Brows * m.H3 / 4, pn.prologue == PRO_ROWS ? 64 : 256) : 0;      // (four columns per thread of the launch's block size)
         pp.gx0 = ws + wl.gx0; pp.wyT = P + pl.wyT;
         range_params(pp, ws_status, pn.limbs, clear_status, P, pl);
         const dim3 gp(pp.nA + pp.nH + pp.nD + pp.nG + 1);
@@ -612,7 +677,7 @@ int run_pass(const Dims& m, const cvae_net_desc* d, const float* P, const Cell* 
         return true;
     };
     int form = pn.form;      // steps down where a launch is refused
-    if (form == CVAE_EVAL_LL || form <= CVAE_EVAL_V2) front_end_gemm();
+    if (form == CVAE_EVAL_LL || form == CVAE_EVAL_V6H || form <= CVAE_EVAL_V2) front_end_gemm();
     switch (form) {
     case CVAE_EVAL_LL: {
         StepLLParams q;
@@ -630,10 +695,13 @@ int run_pass(const Dims& m, const cvae_net_desc* d, const float* P, const Cell* 
         if (refused(e)) return fail(-3, "small-batch recurrent kernel failed to launch: %s", hipGetErrorString(e));
         break;
     }
-    case CVAE_EVAL_V6: {
+    case CVAE_EVAL_V6:
+    case CVAE_EVAL_V6H: {
+        const bool fused = form == CVAE_EVAL_V6;
         Step6Params q;
-        q.hbuf = hbuf; q.mtot = wl.mtot; q.hx = ws + wl.hs; q.wrec3 = P + pl.wrec_t; q.afold3 = P + pl.afold_t; q.w2s = P + pl.wrec_l2b;
-        q.cfold = P + pl.cfold; q.bhn = P + pl.bhn; q.xt = ws + wl.xt; q.Tp = wl.Tp; q.Cp = m.Cp;
+        q.hbuf = hbuf; q.mtot = wl.mtot; q.hx = ws + wl.hs; q.wrec3 = P + pl.wrec_t; q.afold3 = fused ? P + pl.afold_t : nullptr; q.w2s = P + pl.wrec_l2b;
+        q.cfold = P + pl.cfold; q.bhn = P + pl.bhn; q.xt = fused ? ws + wl.xt : nullptr; q.Tp = wl.Tp; q.Cp = m.Cp;
+        q.gx = fused ? nullptr : gx; q.gx_bstride = (long)wl.Tp * m.H3;      // V6H: the GEMM's output, cfold included
         q.B = Brows; q.Bp = wl.Bp; q.H = m.H; q.T = T; q.flags = hflags; q.status = status;
         q.prof = step_prof;
         q.wyT = P + pl.wyT; q.dy = dy; q.Co = m.Co;
@@ -642,7 +710,7 @@ int run_pass(const Dims& m, const cvae_net_desc* d, const float* P, const Cell* 
         q.rts = pn.rts;
         q.exp = (int)opt(OPT_EXP);   // measurement switches only
         q.backoff = pn.backoff;
-        const size_t lds6 = (size_t)(4 * 32 * 40 + 32 * 8 + 384 + 4 * m.KFW * v6_limbs(m) * 256) * sizeof(float);
+        const size_t lds6 = (size_t)(4 * 32 * 40 + 32 * 8 + 384 + (fused ? 4 * m.KFW * v6_limbs(m) * 256 : 0)) * sizeof(float);
         const hipError_t e = cvae_launch_coop(pn.k6, dim3(m.H / 8 * pn.rts), dim3(256), lds6, st, q);
         if (refused(e)) return fail(-3, "exact-operand recurrent kernel failed to launch: %s", hipGetErrorString(e));
         break;
@@ -865,7 +933,7 @@ size_t cvae_net_prepare_scratch_bytes(cvae_ctx* ctx, const cvae_net_desc* d) {
     CVAE_ENTER_SZ(ctx);
     Dims m;
     if (make_dims(d, &m)) return 0;
-    return ((size_t)m.c2 * m.R * m.C + m.c2 + 64) * sizeof(double);
+    return (size_t)fold_scratch(m).total * sizeof(double);
 }
 
 int cvae_net_prepare(cvae_ctx* ctx, const cvae_net_desc* d, const cvae_net_weights* w, void* prepared, size_t prepared_bytes,
@@ -874,9 +942,10 @@ int cvae_net_prepare(cvae_ctx* ctx, const cvae_net_desc* d, const cvae_net_weigh
     Dims m;
     if (int rc = make_dims(d, &m)) return rc;
     if (!w || !prepared || !scratch) return fail(-1, "null argument");
-    if (!w->conv0_w || !w->conv0_b || !w->conv1_w || !w->conv1_b || !w->w_ih || !w->w_hh || !w->b_ih || !w->b_hh ||
-        !w->out_w || !w->out_b)
+    if (!w->conv0_w || !w->conv0_b || !w->w_ih || !w->w_hh || !w->b_ih || !w->b_hh || !w->out_w || !w->out_b)
         return fail(-1, "missing weight pointer");
+    if ((m.layers >= 2 && (!w->conv1_w || !w->conv1_b)) || (m.layers >= 3 && (!w->conv2_w || !w->conv2_b)))
+        return fail(-1, "missing conv weight pointer for layers=%d", m.layers);
     if (d->has_scale_in && (!w->scale_in_w || !w->scale_in_b)) return fail(-1, "has_scale_in without scale_in weights");
     if (d->has_scale_out && (!w->scale_out_w || !w->scale_out_b)) return fail(-1, "has_scale_out without scale_out weights");
     if (prepared_bytes < cvae_net_prepared_bytes(ctx, d)) return fail(-2, "prepared buffer too small");
@@ -884,44 +953,61 @@ int cvae_net_prepare(cvae_ctx* ctx, const cvae_net_desc* d, const cvae_net_weigh
     hipStream_t st = (hipStream_t)stream;
     const Prep pl = prep_layout(m, d->has_scale_in != 0, d->has_scale_out != 0);
     float* P = (float*)prepared;
-    double* mfull = (double*)scratch;
-    double* bprime = mfull + (size_t)m.c2 * m.R * m.C;
+    const FoldScratch fs = fold_scratch(m);
+    double* mfull = (double*)scratch + fs.ma;      // where the last layer's fold lands
+    double* bprime = (double*)scratch + fs.ba;
     int* unfit = (int*)(P + pl.range);      // raised by the kernels that write limb images (cleared with the image, just below)
     cx().image_unfit.erase((const void*)P);
 
     CVAE_HIP_OK(hipMemsetAsync(P, 0, (size_t)pl.total * sizeof(float), st));
-    hipLaunchKernelGGL((k_prep_mfull), dim3(nblk((long)m.c2 * m.R * m.C, 256)), dim3(256), 0, st, w->conv0_w, w->conv1_w,
-                       mfull, m.C, m.ks);
-    hipLaunchKernelGGL((k_prep_bprime), dim3(nblk(m.c2, 128)), dim3(128), 0, st, w->conv0_b, w->conv1_w, w->conv1_b,
-                       bprime, m.C, m.ks);
+    {   // the fold, layer by layer (fp64; the one rounding to fp32 happens in k_prep_afold / k_prep_cfold)
+        const float* const cw_[3] = {w->conv0_w, w->conv1_w, w->conv2_w};
+        const float* const cb_[3] = {w->conv0_b, w->conv1_b, w->conv2_b};
+        double* const sc = (double*)scratch;
+        for (int n = 0; n < m.layers; ++n) {
+            const bool in_a = (m.layers - 1 - n) % 2 == 0;
+            double* mn = sc + (in_a ? fs.ma : fs.mb);
+            double* bn = sc + (in_a ? fs.ba : fs.bb);
+            const double* mp = sc + (in_a ? fs.mb : fs.ma);
+            const double* bp = sc + (in_a ? fs.bb : fs.ba);
+            if (n == 0) {
+                hipLaunchKernelGGL((k_prep_fold0), dim3(nblk(fold_m_size(m, 0), 256)), dim3(256), 0, st, cw_[0], cb_[0], mn, bn, m.C, m.ks);
+            } else {
+                const int cp = m.cl[n - 1], rp = cp / m.C;
+                hipLaunchKernelGGL((k_prep_fold_m), dim3(nblk(fold_m_size(m, n), 256)), dim3(256), 0, st, cw_[n], mp, mn, m.C, m.ks, cp, rp);
+                hipLaunchKernelGGL((k_prep_fold_b), dim3(nblk(m.cl[n], 128)), dim3(128), 0, st, bp, cw_[n], cb_[n], bn, m.ks, cp);
+            }
+        }
+    }
     hipLaunchKernelGGL((k_prep_afold), dim3(nblk((long)m.H3 * m.Kfe, 256)), dim3(256), 0, st, w->w_ih,
-                       (const double*)mfull, P + pl.afold, m.C, m.Cp, m.ks, m.tot, m.Kfe, m.H3);
+                       (const double*)mfull, P + pl.afold, m.C, m.Cp, m.R, m.tot, m.Kfe, m.H3);
     hipLaunchKernelGGL((k_prep_afold_h), dim3(nblk((long)m.nch * 4 * ((m.KFW + 1) / 2) * 3 * 512, 256)), dim3(256), 0, st,
                        (const float*)(P + pl.afold), P + pl.afold_h, m.H, m.Kfe, (m.KFW + 1) / 2, unfit);
     hipLaunchKernelGGL((k_prep_afold3), dim3(nblk((long)m.nch * 4 * m.KFW * 3 * 256, 256)), dim3(256), 0, st,
                        (const float*)(P + pl.afold), P + pl.afold3, m.H, m.Kfe, m.KFW);
     hipLaunchKernelGGL((k_prep_cfold), dim3(nblk(m.H3, 128)), dim3(128), 0, st, w->w_ih, w->b_ih, w->b_hh, w->out_b,
-                       (const double*)bprime, P + pl.cfold, m.c2, m.Co, m.tot, m.H);
+                       (const double*)bprime, P + pl.cfold, m.cw, m.Co, m.tot, m.H);
     hipLaunchKernelGGL((k_prep_wrec), dim3(nblk((long)(m.H / 4) * m.nch * 256, 256)), dim3(256), 0, st, w->w_ih, w->w_hh,
-                       w->out_w, P + pl.wrec, m.c2, m.Co, m.tot, m.H);
+                       w->out_w, P + pl.wrec, m.cw, m.Co, m.tot, m.H);
     auto copy2d = [&](float* dst, long dld, const float* src, long sld, int rows, int cols) {
         hipLaunchKernelGGL((k_copy2d), dim3(nblk((long)rows * cols, 256)), dim3(256), 0, st, dst, dld, src, sld, rows, cols);
     };
     hipLaunchKernelGGL((k_prep_wrec2), dim3(nblk((long)m.nch * 4 * m.nch * 256, 256)), dim3(256), 0, st, w->w_ih, w->w_hh,
-                       w->out_w, P + pl.wrec2, m.c2, m.Co, m.tot, m.H);
+                       w->out_w, P + pl.wrec2, m.cw, m.Co, m.tot, m.H);
     if (m.H % 32 == 0)
         hipLaunchKernelGGL((k_prep_wrec_h), dim3(nblk((long)m.nch * 4 * (m.H / 32) * 512, 256)), dim3(256), 0, st,
                            (const float*)(P + pl.wrec2), P + pl.wrec_h, m.H, unfit);
     if (exact3_ok(m)) {
         hipLaunchKernelGGL((k_prep_wrec3), dim3(nblk((long)(m.H / 8) * 4 * exact3_kpw(m) * 512, 256)), dim3(256), 0, st,
                            (const float*)(P + pl.wrec2), P + pl.wrec_t, m.H, exact3_kpw(m), unfit);
-        hipLaunchKernelGGL((k_prep_afold3l), dim3(nblk((long)(m.H / 8) * 4 * m.KFW * 512, 256)), dim3(256), 0, st,
-                           (const float*)(P + pl.afold), P + pl.afold_t, m.H, m.Kfe, m.KFW, unfit);
+        if (exact3_fused(m))
+            hipLaunchKernelGGL((k_prep_afold3l), dim3(nblk((long)(m.H / 8) * 4 * m.KFW * 512, 256)), dim3(256), 0, st,
+                               (const float*)(P + pl.afold), P + pl.afold_t, m.H, m.Kfe, m.KFW, unfit);
         hipLaunchKernelGGL((k_prep_wrec3_l2b), dim3(nblk((long)(m.H / 8) * 4 * exact3_kpw(m) * 512, 256)), dim3(256), 0, st,
                            (const float*)(P + pl.wrec2), (unsigned char*)(P + pl.wrec_l2b), m.H, exact3_kpw(m));
     }
     copy2d(P + pl.bhn, m.H, w->b_hh + 2 * m.H, m.H, 1, m.H);
-    hipLaunchKernelGGL((k_copy2d_t), dim3(nblk((long)m.H3 * m.Co, 256)), dim3(256), 0, st, P + pl.wyT, w->w_ih + m.c2,
+    hipLaunchKernelGGL((k_copy2d_t), dim3(nblk((long)m.H3 * m.Co, 256)), dim3(256), 0, st, P + pl.wyT, w->w_ih + m.cw,
                        (long)m.tot, m.H3, m.Co);
     copy2d(P + pl.wo, m.H, w->out_w, m.H, m.Co, m.H);
     copy2d(P + pl.bo, m.Co, w->out_b, m.Co, 1, m.Co);

@@ -11,10 +11,10 @@ struct TDims {
 TDims make_tdims(const Dims& m, int T) {
     TDims t;
     t.Cq = (int)up(m.C, 16);
-    t.C3 = m.c1;
-    t.C3p = (int)up(m.c1, 16);
-    t.C9 = m.c2;
-    t.C9p = (int)up(m.c2, 16);
+    t.C3 = m.cl[0];
+    t.C3p = (int)up(m.cl[0], 16);
+    t.C9 = m.cl[1];
+    t.C9p = (int)up(m.cl[1], 16);
     t.K0 = m.ks * t.Cq;
     t.K1 = m.ks * t.C3p;
     t.F0 = T + m.R - m.ks;   // conv0 output frames
@@ -562,7 +562,7 @@ extern "C" {
 size_t cvae_train_image_bytes(cvae_ctx* ctx, const cvae_net_desc* d) {
     CVAE_ENTER_SZ(ctx);
     Dims m;
-    if (make_dims(d, &m)) return 0;
+    if (make_train_dims(d, &m)) return 0;
     return (size_t)tprep_layout(m, d->has_scale_in != 0, d->has_scale_out != 0).total * sizeof(float);
 }
 
@@ -575,7 +575,7 @@ int cvae_net_prepare_train(cvae_ctx* ctx, const cvae_net_desc* d, const cvae_net
 int cvae_train_variants_needed(cvae_ctx* ctx, const cvae_net_desc* d, int B, int T) {
     CVAE_ENTER(ctx);
     Dims m;
-    if (make_dims(d, &m) || B < 1 || T < 1) return TV_ALL;
+    if (make_train_dims(d, &m) || B < 1 || T < 1) return TV_ALL;
     return plan_train_pass(m, B, T).variants;
 }
 
@@ -583,7 +583,7 @@ int cvae_net_prepare_train_v(cvae_ctx* ctx, const cvae_net_desc* d, const cvae_n
                              int variants, void* stream) {
     CVAE_ENTER(ctx);
     Dims m;
-    if (int rc = make_dims(d, &m)) return rc;
+    if (int rc = make_train_dims(d, &m)) return rc;
     if (!w || !image) return fail(-1, "null argument");
     if (image_bytes < cvae_train_image_bytes(ctx, d)) return fail(-2, "train image too small");
     if (!(gru_drop_p >= 0.0f && gru_drop_p < 1.0f)) return fail(-1, "dropout probability %f outside [0,1)", (double)gru_drop_p);
@@ -671,14 +671,14 @@ int cvae_net_prepare_train_v(cvae_ctx* ctx, const cvae_net_desc* d, const cvae_n
 size_t cvae_train_tape_bytes(cvae_ctx* ctx, const cvae_net_desc* d, int B, int T) {
     CVAE_ENTER_SZ(ctx);
     Dims m;
-    if (make_dims(d, &m) || B < 1 || T < 1) return 0;
+    if (make_train_dims(d, &m) || B < 1 || T < 1) return 0;
     return (size_t)ttape_layout(m, B, T, plan_train_pass(m, B, T).Bp).total * sizeof(float);
 }
 
 size_t cvae_train_scratch_bytes(cvae_ctx* ctx, const cvae_net_desc* d, int B, int T) {
     CVAE_ENTER_SZ(ctx);
     Dims m;
-    if (make_dims(d, &m) || B < 1 || T < 1) return 0;
+    if (make_train_dims(d, &m) || B < 1 || T < 1) return 0;
     return (size_t)tscratch_layout(m, T, plan_train_pass(m, B, T).Bp).total * sizeof(float);
 }
 
@@ -688,7 +688,7 @@ int cvae_gru_rnn_forward_train(cvae_ctx* ctx, const cvae_net_desc* d, const void
                                void* scratch, size_t scratch_bytes, void* stream) {
     CVAE_ENTER(ctx);
     Dims m;
-    if (int rc = make_dims(d, &m)) return rc;
+    if (int rc = make_train_dims(d, &m)) return rc;
     if (B < 1 || T < 1) return fail(-1, "empty batch: B=%d T=%d", B, T);
     if (!image || !x || !y_in || !trj_out || !tape || !scratch) return fail(-1, "null argument");
     if (!(p_drop >= 0.0f && p_drop < 1.0f)) return fail(-1, "dropout probability %f outside [0,1)", (double)p_drop);
@@ -925,7 +925,7 @@ int cvae_gru_rnn_backward(cvae_ctx* ctx, const cvae_net_desc* d, const void* ima
                           int accumulate, void* stream) {
     CVAE_ENTER(ctx);
     Dims m;
-    if (int rc = make_dims(d, &m)) return rc;
+    if (int rc = make_train_dims(d, &m)) return rc;
     if (!image || !dout || !tape || !scratch || !g) return fail(-1, "null argument");
     if (!g->conv0_w || !g->conv0_b || !g->conv1_w || !g->conv1_b || !g->w_ih || !g->w_hh || !g->b_ih || !g->b_hh || !g->out_w ||
         !g->out_b)
@@ -1160,7 +1160,7 @@ int cvae_status_latch(cvae_ctx* ctx, int32_t* latch, void* stream) {
 int cvae_train_debug_counters(cvae_ctx* ctx, const cvae_net_desc* d, int B, int T, const void* scratch, long long out[8], void* stream) {
     CVAE_ENTER(ctx);
     Dims m;
-    if (int rc = make_dims(d, &m)) return rc;
+    if (int rc = make_train_dims(d, &m)) return rc;
     if (!scratch || !out) return fail(-1, "null argument");
     const TScratch sl = tscratch_layout(m, T, plan_train_pass(m, B, T).Bp);
     CVAE_HIP_OK(hipMemcpyAsync(out, (const float*)scratch + sl.tprof, 8 * sizeof(long long), hipMemcpyDeviceToHost, (hipStream_t)stream));

@@ -277,7 +277,7 @@ class TwoSidedDilConv1d(nn.Module):
 
     def forward(self, x):
         """x [B, C, T] -> [B, C * ks^layers, T], the reference's own statements (gru_vae.py:53-66): conv.0 then conv.1 ... as torch
-        convolutions on whatever device x lives on.  GRU_RNN.forward never calls this (its front-end is the folded 9-tap GEMM
+        convolutions on whatever device x lives on.  GRU_RNN.forward never calls this (its front-end is the folded ks^layers-tap GEMM
         inside the HIP pass); it exists so that the class is usable on its own, as in the reference."""
         x = self.conv[0](x)
         for i in range(1, self.layers):
@@ -610,6 +610,12 @@ class GRU_RNN(nn.Module):
         if int(hidden_layers) != hidden_layers or not 1 <= hidden_layers <= _cabi.MAX_LAYERS:
             raise ValueError("hidden_layers must be an integer in 1..%d, got %r" % (_cabi.MAX_LAYERS, hidden_layers))
         hidden_layers = int(hidden_layers)
+        if int(dilation_size) != dilation_size or not 1 <= dilation_size <= 3 or (dilation_size == 3 and kernel_size != 3):
+            raise ValueError("dilation_size must be 1, 2 or 3, and 3 only with kernel_size 3 (a receptive field of kernel_size ** "
+                             "dilation_size >= 125 frames is not supported), got dilation_size=%r kernel_size=%r" % (dilation_size, kernel_size))
+        dilation_size = int(dilation_size)
+        if dilation_size == 3 and hidden_units % 64:
+            raise ValueError("dilation_size=3 needs hidden_units to be a multiple of 64, got %r" % (hidden_units,))
         if scale_in_out_flag:
             raise NotImplementedError("scale_in_out_flag is dead code in this recipe")
         self.in_dim, self.out_dim = in_dim, out_dim
@@ -657,6 +663,11 @@ class GRU_RNN(nn.Module):
             raise NotImplementedError(
                 "hidden_layers=%d: train-mode / autograd passes of a stacked GRU (tape, reverse recurrence, the inter-layer dropout "
                 "of nn.GRU) are not implemented; eval passes run under model.eval() and torch.no_grad()" % self.hidden_layers)
+        if self.dilation_size != 2 and ((self.do_prob > 0 and do and self.training) or (
+                torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())))):
+            raise NotImplementedError(
+                "dilation_size=%d: train-mode / autograd passes are implemented for the two-layer front-end only (tape and gradient "
+                "chains); eval passes run under model.eval() and torch.no_grad()" % self.dilation_size)
         _need_cuda(x, "GRU_RNN.forward(x)")
         _lib()
         check_status()

@@ -288,6 +288,9 @@ class Stage4Step(object):
             if getattr(m, "hidden_layers", 1) > 1:
                 raise NotImplementedError("hidden_layers=%d: training a stacked GRU (Stage4Step) is not implemented; the eval passes, "
                                           "the fresh CycleChain and the stage-6 conversion are" % m.hidden_layers)
+            if getattr(m, "dilation_size", 2) != 2:
+                raise NotImplementedError("dilation_size=%d: training (Stage4Step) is implemented for the two-layer front-end only; the "
+                                          "eval passes, CycleChain and the stage-6 conversion run dilation_size 1, 2 and 3" % m.dilation_size)
         self.script_loss = bool(script_loss)
         self.mods = {"enc": enc, "dec": dec}
         on_gpu = next(enc.parameters()).is_cuda

@@ -254,7 +254,7 @@ def _decoder_window_schedule(nfr, edges, reach):
 def _convert_pair_windowed(model_encoder, model_decoder, pair, y_in_pp, y_in_src, y_in_trg, lat_dim, n_smpl_dec, eps, seed, window):
     """convert_pairs for ONE utterance pair as a pass-level wavefront: the utterances are cut into windows of `window` frames, the
     encoder launch of window w+1 runs on a second stream beside the decoder launch of window w (the decoder lags by the conv
-    front-end's reach, 4 frames: its window w needs latent frames up to the end of encoder window w).  A window is a pass with
+    front-end's reach, (ks^layers - 1) / 2 = 4 frames in the recipe: its window w needs latent frames up to the end of encoder window w).  A window is a pass with
     carried state whose front-end sees the neighbouring frames of the utterance (cvae_gru_rnn_forward_stacked_carry, ABI 5), so the
     result is the unbroken pass bit for bit.  Both recurrences are the word-exchange kernels (<= 3 rows), co-resident on every CU."""
     lib = gru_vae._lib()
@@ -263,10 +263,10 @@ def _convert_pair_windowed(model_encoder, model_decoder, pair, y_in_pp, y_in_src
     dev = fs.device
     lens = (fs.shape[0], ft.shape[0])
     Tmax, L, Cin, Co, H = max(lens), lat_dim, model_encoder.in_dim, model_decoder.out_dim, model_encoder.hidden_units
-    reach = (model_decoder.kernel_size ** 2 - 1) // 2
-    if (model_encoder.kernel_size ** 2 - 1) // 2 != reach:
-        raise ValueError("encoder and decoder front-ends reach %d / %d frames: the window schedule assumes one reach"
-                         % ((model_encoder.kernel_size ** 2 - 1) // 2, reach))
+    reach = (model_decoder.kernel_size ** model_decoder.dilation_size - 1) // 2      # the front-end's padding (ks^layers - 1) / 2
+    reach_enc = (model_encoder.kernel_size ** model_encoder.dilation_size - 1) // 2
+    if reach_enc != reach:
+        raise ValueError("encoder and decoder front-ends reach %d / %d frames: the window schedule assumes one reach" % (reach_enc, reach))
     if min(fs.shape[0], ft.shape[0]) < 1:
         raise ValueError("convert_pairs(window=...): empty utterance")
     edges = _window_edges(Tmax, window, reach)

@@ -87,7 +87,7 @@ def onehot_codes(B, T, src_is_first=True):
 
 
 def gru_rnn_state(name, in_dim, out_dim, hidden, scale_in=None, scale_out=None, bias_scale=0.0,
-                  kernel_size=3, seed=SEED, hidden_layers=1):
+                  kernel_size=3, seed=SEED, hidden_layers=1, dilation_size=2):
     """state_dict (numpy float32) of one GRU_RNN with the reference's key names and shapes.
 
     scale_in / scale_out: optional (mu, sigma) pairs -> frozen (un)normalisation layers.
@@ -95,10 +95,12 @@ def gru_rnn_state(name, in_dim, out_dim, hidden, scale_in=None, scale_out=None, 
     tests exercise every bias path.
     hidden_layers > 1 adds gru.*_l1 .. (nn.GRU(num_layers=...)) drawn from name keys of their own ("gru.wih_l1", ...), so
     every tensor of the one-layer state -- and its SHA -- is the same for any hidden_layers.
+    dilation_size: conv layers of the front-end (1, 2, 3); conv.conv.i maps in_dim * ks^i channels to in_dim * ks^(i+1).  A third
+    layer draws from name keys of its own ("conv2.w", "conv2.b"); gru.weight_ih_l0 has in_dim * ks^dilation_size + out_dim columns.
     """
     ks = kernel_size
     c1, c2 = in_dim * ks, in_dim * ks * ks
-    tot = c2 + out_dim
+    tot = in_dim * ks ** dilation_size + out_dim
     sd = {}
 
     def bias(k, n):
@@ -112,8 +114,12 @@ def gru_rnn_state(name, in_dim, out_dim, hidden, scale_in=None, scale_out=None, 
         sd["scale_in.bias"] = (-(mu / sg)).astype(np.float32)
     sd["conv.conv.0.weight"] = xavier(name + "/conv0.w", (c1, in_dim, ks), seed)
     sd["conv.conv.0.bias"] = bias("conv0.b", c1)
-    sd["conv.conv.1.weight"] = xavier(name + "/conv1.w", (c2, c1, ks), seed)
-    sd["conv.conv.1.bias"] = bias("conv1.b", c2)
+    if dilation_size >= 2:
+        sd["conv.conv.1.weight"] = xavier(name + "/conv1.w", (c2, c1, ks), seed)
+        sd["conv.conv.1.bias"] = bias("conv1.b", c2)
+    if dilation_size >= 3:
+        sd["conv.conv.2.weight"] = xavier(name + "/conv2.w", (c2 * ks, c2, ks), seed)
+        sd["conv.conv.2.bias"] = bias("conv2.b", c2 * ks)
     sd["gru.weight_ih_l0"] = xavier(name + "/gru.wih", (3 * hidden, tot), seed)
     sd["gru.weight_hh_l0"] = xavier(name + "/gru.whh", (3 * hidden, hidden), seed)
     sd["gru.bias_ih_l0"] = bias("gru.bih", 3 * hidden)
@@ -136,18 +142,21 @@ class CycleVAEProblem(object):
     """One synthetic CycleVAE workload: encoder/decoder weights, a (B,T) feature window, codes, eps."""
 
     def __init__(self, B, T, in_dim=54, out_dim=50, lat_dim=32, hidden=1024, n_cyc=2, bias_scale=0.0,
-                 seed=SEED, tag="w", hidden_layers=1):
+                 seed=SEED, tag="w", hidden_layers=1, dilation_size=2, kernel_size=3):
         self.B, self.T = B, T
         self.in_dim, self.out_dim, self.lat_dim, self.hidden, self.n_cyc = in_dim, out_dim, lat_dim, hidden, n_cyc
         self.hidden_layers = hidden_layers
+        self.dilation_size, self.kernel_size = dilation_size, kernel_size
         self.stdim = in_dim - out_dim
         mu, sg = feature_stats(tag + "/stats", in_dim, seed)
         self.mu, self.sigma = mu, sg
         mu_t, sg_t = mu[self.stdim:], sg[self.stdim:]
         self.enc = gru_rnn_state(tag + "/enc", in_dim, 2 * lat_dim, hidden, scale_in=(mu, sg),
-                                 bias_scale=bias_scale, seed=seed, hidden_layers=hidden_layers)
+                                 bias_scale=bias_scale, seed=seed, hidden_layers=hidden_layers, dilation_size=dilation_size,
+                                 kernel_size=kernel_size)
         self.dec = gru_rnn_state(tag + "/dec", lat_dim + 2, out_dim, hidden, scale_out=(mu_t, sg_t),
-                                 bias_scale=bias_scale, seed=seed, hidden_layers=hidden_layers)
+                                 bias_scale=bias_scale, seed=seed, hidden_layers=hidden_layers, dilation_size=dilation_size,
+                                 kernel_size=kernel_size)
         self.x = features(tag + "/x", B, T, mu, sg, seed=seed)
         self.cvx = features(tag + "/cvx", B, T, mu[:self.stdim], sg[:self.stdim], seed=seed)
         self.code_src, self.code_trg = onehot_codes(B, T)

@@ -15,7 +15,9 @@
  *     it reads NO environment variable
  *   - all work is enqueued on `stream` (a hipStream_t passed as void*); nothing synchronises the device
  *   - return value: 0 = ok, negative = error (cvae_last_error_string() describes it); never throws
- *   - hidden size must be a multiple of 16; kernel_size odd; conv layers (reference `dilation_size`) == 2
+ *   - hidden size must be a multiple of 16; kernel_size odd; conv layers (reference `dilation_size`) 1, 2 or 3 (ABI 10; 3 with
+ *     kernel_size 3 only: the receptive field kernel_size^layers stays below 125 frames -- and with hidden % 64 == 0 only);
+ *     training: layers == 2
  */
 #ifndef CYCLEVAE_HIP_H
 #define CYCLEVAE_HIP_H
@@ -27,7 +29,7 @@
 extern "C" {
 #endif
 
-#define CVAE_ABI_VERSION 9
+#define CVAE_ABI_VERSION 10
 
 /* Shape of one reference GRU_RNN (src/nets/gru_vae.py:282-320). */
 typedef struct cvae_net_desc {
@@ -35,12 +37,14 @@ typedef struct cvae_net_desc {
     int32_t out_dim;       /* Cout (encoder: 2*lat_dim)             */
     int32_t hidden;        /* H, multiple of 16                     */
     int32_t kernel_size;   /* 3 in the recipe                       */
-    int32_t layers;        /* reference `dilation_size`; must be 2  */
+    int32_t layers;        /* reference `dilation_size`: 1, 2 or 3  */
     int32_t has_scale_in;  /* scale_in_flag  (gru_vae.py:296-297)   */
     int32_t has_scale_out; /* scale_out_flag (gru_vae.py:317-318)   */
 } cvae_net_desc;
 
-/* Raw weights in the reference's state_dict layout; NULL where the layer is absent. */
+/* Raw weights in the reference's state_dict layout; NULL where the layer is absent.  Conv layer n (0-based, n <
+ * layers) maps ks^n*Cin channels to ks^(n+1)*Cin with dilation ks^n; W_ih sees the last layer's ks^layers*Cin channels + Cout.
+ * conv1_* may be NULL for layers == 1; conv2_* (ABI 10, at the end of the struct) are NULL unless layers == 3. */
 typedef struct cvae_net_weights {
     const float* scale_in_w;  /* scale_in.weight      [Cin,Cin,1]        */
     const float* scale_in_b;  /* scale_in.bias        [Cin]              */
@@ -48,7 +52,7 @@ typedef struct cvae_net_weights {
     const float* conv0_b;     /* conv.conv.0.bias     [ks*Cin]           */
     const float* conv1_w;     /* conv.conv.1.weight   [ks^2*Cin,ks*Cin,ks] */
     const float* conv1_b;     /* conv.conv.1.bias     [ks^2*Cin]         */
-    const float* w_ih;        /* gru.weight_ih_l0     [3H, ks^2*Cin+Cout] */
+    const float* w_ih;        /* gru.weight_ih_l0     [3H, ks^layers*Cin+Cout] */
     const float* w_hh;        /* gru.weight_hh_l0     [3H, H]            */
     const float* b_ih;        /* gru.bias_ih_l0       [3H]               */
     const float* b_hh;        /* gru.bias_hh_l0       [3H]               */
@@ -56,6 +60,8 @@ typedef struct cvae_net_weights {
     const float* out_b;       /* out_1.bias           [Cout]             */
     const float* scale_out_w; /* scale_out.weight     [Cout,Cout,1]      */
     const float* scale_out_b; /* scale_out.bias       [Cout]             */
+    const float* conv2_w;     /* conv.conv.2.weight   [ks^3*Cin,ks^2*Cin,ks] */
+    const float* conv2_b;     /* conv.conv.2.bias     [ks^3*Cin]         */
 } cvae_net_weights;
 
 /* One row-segment of a pass input: element (b,t,c) lives at ptr[(b*T+t)*row_stride + c], c < width. */
@@ -285,7 +291,9 @@ typedef enum cvae_eval_form {
     CVAE_EVAL_V4 = 3,       /* k_gru_steps_v4: front-end fused, fp32 MFMA                                                */
     CVAE_EVAL_V5 = 4,       /* k_gru_steps_v5: front-end fused, fp16 pairs                                               */
     CVAE_EVAL_V6 = 5,       /* k_gru_steps_v6: 32-row tiles, exact fp32 operands as fp16 limbs                           */
-    CVAE_EVAL_LL = 6        /* k_gru_steps_ll: at most three rows, word exchange, behind the front-end GEMM              */
+    CVAE_EVAL_LL = 6,       /* k_gru_steps_ll: at most three rows, word exchange, behind the front-end GEMM              */
+    CVAE_EVAL_V6H = 7       /* k_gru_steps_v6<KPW, 0>: the exact-operand recurrence behind the front-end GEMM (ABI 10: front-ends
+                               too wide for the LDS limb image of V6, KFW >= 12)                                        */
 } cvae_eval_form;
 int cvae_plan_pass(cvae_ctx* ctx, const cvae_net_desc* d, int rows, int T, int flags);
 
