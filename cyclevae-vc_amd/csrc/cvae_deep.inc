@@ -1,5 +1,8 @@
 // Host side of the eval passes of a GRU_RNN with n_layers >= 2 GRU layers (kernels: cvae_deep.h; ABI: the *_deep entry points).
-// Included at the end of cvae_lib.hip.
+// Included at the end of cvae_lib.hip.  Its own: the deep part of the prepared image, the workspace layout (one state buffer per
+// layer), plan_deep_pass, k_deep_slot0 and the two recurrences (k_gru_steps_deep3 / k_gru_steps_deep).  Everything else of a pass is
+// the stages of cvae_lib.hip (check_cells, run_prologue, run_front_end_gemm, run_projection, run_last_states), called as one cell on
+// the top layer.
 //
 // Prepared image = [ the one-layer image of cvae_net_prepare built from layer 0 (front-end fold, cfold, out_1 / scale images:
 // everything of it that does not involve W_hh is used as it is) | the deep part below ].  n_layers == 1 delegates every entry point
@@ -102,69 +105,33 @@ int run_pass_deep(const Dims& m, const cvae_net_desc* d, int L, const float* P, 
     if (image_known_unfit(P)) flags |= CVAE_FLAG_GENERIC_STEP;
     const DeepPlan pn = plan_deep_pass(m, L, B, T, flags);
     int* status = cx().status_sink ? cx().status_sink : (int*)ws;
-    const int w_in = in->seg0.width + (in->lat ? in->lat_dim : in->seg1.width);
-    if (w_in != m.C) return fail(-1, "pass input width %d != in_dim %d", w_in, m.C);
-    if (in->frames < 0 || in->frames > T) return fail(-1, "frames %d outside [0, T=%d]", in->frames, T);
-    if (in->ctx_before < 0 || in->ctx_after < 0 || in->draw_frame0 < 0 || in->eps_draw_stride < 0)
-        return fail(-1, "negative window context / draw origin");
-    if ((in->ctx_before || in->ctx_after || in->draw_frame0) && B != 1)
-        return fail(-1, "windows of a longer utterance (ctx_before / ctx_after / draw_frame0) are single-row passes, B=%d", B);
     unsigned* bar = (unsigned*)(ws + wl.status) + 8;
     float* xnp = ws + wl.xnp;
     float* gx = ws + wl.gx;
     float* dy = ws + wl.dy;
-    float* y = ws + wl.y;
     float* hb = ws + wl.hb;
     float* hb_top = hb + (long)(L - 1) * wl.hb_ls;
     float* hx = pn.path == DEEP_RESIDENT ? ws + wl.hx : nullptr;
     unsigned* hflags = (unsigned*)(ws + wl.flags);
-    const float* h_top = h_in ? h_in + (long)(L - 1) * B * m.H : nullptr;
-    int* range_word = nullptr;      // where k_deep_slot0 reports a carried-in state the limb form cannot hold (range_params)
-    int range_val = 0;
-    float range_at = 0.0f;
-    {   // the one-layer prologue: assemble + scale_in + padding, dy from the TOP layer's h_in (the feedback is out_1 of that state),
-        // flags and status zeroed; its slot-0 role writes the top layer's buffer, k_deep_slot0 below fills every layer
-        ProParams pp;
-        memset(&pp, 0, sizeof(pp));
-        pp.cell[0].seg0 = CvaeSeg{in->seg0.ptr, in->seg0.width, in->seg0.row_stride};
-        pp.cell[0].seg1 = CvaeSeg{in->seg1.ptr, in->seg1.width, in->seg1.row_stride};
-        pp.cell[0].lat = in->lat; pp.cell[0].eps = in->eps; pp.cell[0].seed = in->seed; pp.cell[0].draw = in->draw_id;
-        pp.cell[0].y_in = y_in; pp.cell[0].h_in = h_top; pp.cell[0].frames = in->frames; pp.cell[0].n_draws = in->n_draws;
-        pp.cell[0].ctx_before = in->ctx_before; pp.cell[0].ctx_after = in->ctx_after;
-        pp.cell[0].draw_frame0 = (long)in->draw_frame0; pp.cell[0].eps_stride = (long)in->eps_draw_stride;
-        if (in->lat) pp.L = in->lat_dim;
-        const bool many_draws = in->lat && in->n_draws > 1;
-        pp.ncell = 1;
-        pp.frame0 = (uint64_t)cx().draw_row0 * (uint64_t)T;
-        pp.sin_w = d->has_scale_in ? P + pl.sin_w : nullptr;
-        pp.sin_b = d->has_scale_in ? P + pl.sin_b : nullptr;
-        pp.wo = P + pl.wo; pp.bo = P + pl.bo;
-        pp.B = B; pp.T = T; pp.C = m.C; pp.Cp = m.Cp; pp.pad = m.pad; pp.Co = m.Co; pp.H = m.H; pp.Bp = wl.Bp;
-        pp.nslack = 64 * m.KFW + 64;
-        pp.mtot = wl.mtot;
-        pp.xnp = xnp; pp.hbuf = hb_top; pp.dy = dy;
-        pp.zero_words = hflags; pp.nzero = L * (wl.Bp / 32) * (m.H / 8);
-        pp.zero_status = (int*)ws;      // the pass's own status words; a status sink stays sticky (the caller clears it)
-        pp.zero_status_n = 8;
-        pp.nA = B * wl.Tp;
-        pp.nH = (int)nblk((long)wl.Bp * m.H, 1024);
-        pp.nD = (int)nblk((long)B * m.Co, 64);
-        pp.wyT = P + pl.wyT;
-        // (layer 0's input side is an fp32 GEMM: of the exchanged values only the carried-in states take the limb form, k_deep_slot0)
-        range_params(pp, (int*)ws, pn.path == DEEP_RESIDENT, true, P, pl);
-        range_word = pp.range_word; range_val = pp.range_val; range_at = pp.range_at;
-        if (many_draws)
-            hipLaunchKernelGGL((k_prologue), dim3(pp.nA + pp.nH + pp.nD + 1), dim3(256), (size_t)(m.C + 1024 + 256) * sizeof(float), st, pp);
-        else
-            hipLaunchKernelGGL((k_prologue), dim3(pp.nA + pp.nH + pp.nD + 1), dim3(64), m.C * sizeof(float), st, pp);
+    // the pass as ONE cell of the one-layer stages, on the TOP layer: the feedback is out_1 of that layer's state, so dy comes from
+    // its h_in and the projection reads its buffer; h_last is per layer (below)
+    Cell cell = {in, y_in, h_in ? h_in + (long)(L - 1) * B * m.H : nullptr, trj_out, y_last, nullptr};
+    const PassRows rows = {&cell, 1, B, T, wl.Bp, wl.mtot};
+    if (int rc = check_cells(m, rows)) return rc;
+    RangeSlot range;      // where k_deep_slot0 reports a carried-in state the limb form cannot hold
+    {
+        ProTargets o = {};      // no limb / pair / gx0 output: layer 0's input side is an fp32 GEMM, of the exchanged values only the
+        o.slot0 = hb_top;       // carried-in states take the limb form (k_deep_slot0, which fills slot 0 of every layer)
+        o.zero_words = hflags; o.nzero = L * (wl.Bp / 32) * (m.H / 8);
+        o.zero_status = (int*)ws;      // the pass's own status words; a status sink stays sticky (the caller clears it)
+        o.zero_status_n = 8;
+        o.ws_status = (int*)ws; o.limbs = pn.path == DEEP_RESIDENT; o.new_call = true;
+        o.shape = in->lat && in->n_draws > 1 ? PRO_DRAWS : PRO_ROWS; o.xnp = xnp; o.dy = dy;
+        run_prologue(m, d, P, pl, rows, o, st, &range);
     }
     hipLaunchKernelGGL((k_deep_slot0), dim3(nblk((long)L * wl.Bp * m.H, 256)), dim3(256), 0, st, h_in, hb, wl.hb_ls, hx, wl.hx_ls,
-                       wl.mtot, L, B, wl.Bp, m.H, h_in && hx ? range_word : (int*)nullptr, range_val, range_at);
-    {   // layer 0's input side for all frames: gx[b*Tp + t] = afold . xnp[b, t:t+R, :] + cfold, one GEMM over overlapping rows
-        const int M = B * wl.Tp, N = m.H3;
-        hipLaunchKernelGGL((k_gemm_nt<4, 4, 2, 2, false>), dim3(nblk(N, 128), nblk(M, 128)), dim3(256), 0, st, (const float*)xnp,
-                           (long)m.Cp, 0L, P + pl.afold, (long)m.Kfe, P + pl.cfold, gx, (long)m.H3, M, N, m.Kfe);
-    }
+                       wl.mtot, L, B, wl.Bp, m.H, h_in && hx ? range.word : (int*)nullptr, range.val, range.at);
+    run_front_end_gemm(m, P, pl, xnp, gx, B, wl.Tp, st);      // layer 0's input side for all frames
     const bool prof = (flags & CVAE_FLAG_PROFILE) != 0;
     if (pn.path == DEEP_RESIDENT) {
         DeepStep3Params q;
@@ -209,39 +176,11 @@ int run_pass_deep(const Dims& m, const cvae_net_desc* d, int L, const float* P, 
                 if (pr) prof_end(st);
             }
     }
-    // projection / epilogue of the one-layer path on the top layer's states
-    const int ntn = m.Cop / 16;
-    if (!y_last && (ntn == 1 || ntn == 4 || ntn == 8)) {
-        OutParams op;
-        op.hbuf = hb_top; op.mtot = wl.mtot; op.wo2 = P + pl.wo2; op.bo2 = P + pl.bo2; op.H = m.H; op.Bp = wl.Bp; op.T = T;
-        op.B = B; op.ncell = 1; op.Co = m.Co; op.clamp_from = d->has_scale_out ? -1 : clamp_dim(clamp_lat_dim);
-        op.clamp_min = clamp_floor(clamp_lat_dim);
-        for (int c = 0; c < CVAE_MAX_CELLS; ++c) op.out[c] = c == 0 ? trj_out : nullptr;
-        const unsigned nb = (unsigned)((long)T * wl.Bp / 16);
-        const size_t lds = (size_t)4 * 16 * (m.Cop + 4) * sizeof(float);
-        if (ntn == 1) hipLaunchKernelGGL((k_outproj<1>), dim3(nb), dim3(256), lds, st, op);
-        else if (ntn == 4) hipLaunchKernelGGL((k_outproj<4>), dim3(nb), dim3(256), lds, st, op);
-        else hipLaunchKernelGGL((k_outproj<8>), dim3(nb), dim3(256), lds, st, op);
-    } else {
-        const int M = T * wl.Bp, N = m.Co;
-        hipLaunchKernelGGL((k_gemm_nt<2, 4, 4, 1, true>), dim3(nblk(N, 64), nblk(M, 128)), dim3(256), 0, st,
-                           (const float*)(hb_top + (long)wl.Bp * 16), 0L, wl.mtot, P + pl.wo, (long)m.H, P + pl.bo, y, (long)m.Cop, M, N,
-                           m.H);
-        EpiParams ep;
-        ep.y = y; ep.ldy = m.Cop;
-        ep.sout_w = d->has_scale_out ? P + pl.sout_w : nullptr;
-        ep.sout_b = d->has_scale_out ? P + pl.sout_b : nullptr;
-        ep.clamp_from = d->has_scale_out ? -1 : clamp_dim(clamp_lat_dim);
-        ep.clamp_min = clamp_floor(clamp_lat_dim);
-        ep.B = B; ep.Bp = wl.Bp; ep.T = T; ep.Co = m.Co; ep.b0 = 0;
-        ep.trj_out = trj_out; ep.y_last = y_last;
-        ep.t_last = (in->frames > 0 && in->frames < T ? in->frames : T) - 1;
-        hipLaunchKernelGGL((k_epilogue), dim3(B * T), dim3(64), m.Co * sizeof(float), st, ep);
+    run_projection(m, d, P, pl, rows, plain_projection(m, y_last != nullptr), hb_top, ws + wl.y, clamp_lat_dim, st);
+    for (int l = 0; h_last && l < L; ++l) {
+        cell.h_last = h_last + (long)l * B * m.H;
+        run_last_states(m, rows, hb + (long)l * wl.hb_ls, st);
     }
-    if (h_last)
-        for (int l = 0; l < L; ++l)     // the state behind the LAST VALID frame of every layer (slot `frames`)
-            hipLaunchKernelGGL((k_hlast), dim3(nblk((long)B * m.H, 256)), dim3(256), 0, st, (const float*)(hb + (long)l * wl.hb_ls),
-                               wl.mtot, h_last + (long)l * B * m.H, B, wl.Bp, m.H, in->frames > 0 && in->frames < T ? in->frames : T, 0);
     CVAE_HIP_OK(hipGetLastError());
     return 0;
 }

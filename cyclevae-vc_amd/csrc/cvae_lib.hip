@@ -400,6 +400,12 @@ struct EvalPlan {
     int prologue, proj;                   // PRO_*, PROJ_*
 };
 
+// projection off the fp32 states: k_outproj exists for 16, 64 and 128 padded outputs and does not leave the raw last projection
+inline int plain_projection(const Dims& m, bool y_last) {
+    const int ntn = m.Cop / 16;
+    return !y_last && (ntn == 1 || ntn == 4 || ntn == 8) ? PROJ_FUSED : PROJ_GEMM;
+}
+
 inline bool generic_resident(const Dims& m, int cus) { return cus <= 0 || m.H / 4 <= cus; }      // one 256-thread block per CU is always admitted
 
 EvalPlan plan_eval_pass(const Dims& m, int Brows, int T, int flags, int cus, bool unfit, const PassFacts& f) {
@@ -457,13 +463,12 @@ EvalPlan plan_eval_pass(const Dims& m, int Brows, int T, int flags, int cus, boo
     pn.want_f32 = v6 && (i6->limbs != 3 || f.y_last || f.h_last || (opt(OPT_EXP) & 16));      // (exp bit 4: always write it, for A/B measurements)
     // (V6H: the input goes through the fp32 GEMM -- no limb copy of it, the row-wise prologue; its range word then covers h_in only)
     pn.prologue = v6f ? PRO_TILES : (f.many_draws ? PRO_DRAWS : PRO_ROWS);
-    const int ntn = m.Cop / 16;
     if (!f.y_last && v6 && i6->limbs == 3) {
         pn.proj = PROJ_V6;      // the pass left the state as limb triples in the exchange buffer: project from there, same exact arithmetic
         for (const Out6Inst& o : g_out6_inst)
             if (o.H == m.H) pn.kout6 = o.fn;
     } else {
-        pn.proj = !f.y_last && (ntn == 1 || ntn == 4 || ntn == 8) ? PROJ_FUSED : PROJ_GEMM;
+        pn.proj = plain_projection(m, f.y_last);
     }
     return pn;
 }
@@ -566,7 +571,173 @@ struct Cell {
     float* h_last;       // [B][H] or null
 };
 
-// plan, prologue, the recurrence (one switch on the planned form), projection, k_hlast
+// ---- The stages of an eval pass.  The one-layer pass (run_pass) and the stacked pass (run_pass_deep, cvae_deep.inc) are sequences
+// of these; a stage takes pointers and sizes, never a workspace layout: the two passes keep their own (Work, DeepWork).
+
+// slot whose state a cell carries on: the one behind ITS last valid frame (slot `frames`), not behind the pass's T steps -- a cell
+// shorter than the pass keeps stepping over padding (or, for a window with ctx_after > 0, over frames that belong to the next
+// window), and continuing from slot T restarted the next window from the wrong state
+inline int last_slot(const cvae_pass_input* in, int T) { return in->frames > 0 && in->frames < T ? in->frames : T; }
+
+// The rows of a pass: ncell cells of B rows each over T frames, padded to Bp rows; mtot = (T + 1) * Bp state rows per 16-unit chunk.
+struct PassRows {
+    const Cell* cells;
+    int ncell, B, T, Bp;
+    long mtot;
+};
+
+int check_cells(const Dims& m, const PassRows& r) {
+    const Cell* cells = r.cells;
+    const int ncell = r.ncell, B = r.B, T = r.T;
+    if (ncell > CVAE_MAX_CELLS) return fail(-1, "at most %d stacked cells per pass", CVAE_MAX_CELLS);
+    for (int c = 0; c < ncell; ++c) {
+        const cvae_pass_input* in = cells[c].in;
+        const int w_in = in->seg0.width + (in->lat ? in->lat_dim : in->seg1.width);
+        if (w_in != m.C) return fail(-1, "cell %d: pass input width %d != in_dim %d", c, w_in, m.C);
+        if (in->frames < 0 || in->frames > T) return fail(-1, "cell %d: frames %d outside [0, T=%d]", c, in->frames, T);
+        if (in->ctx_before < 0 || in->ctx_after < 0 || in->draw_frame0 < 0 || in->eps_draw_stride < 0)
+            return fail(-1, "cell %d: negative window context / draw origin", c);
+        if ((in->ctx_before || in->ctx_after || in->draw_frame0) && B != 1)
+            return fail(-1, "cell %d: windows of a longer utterance (ctx_before / ctx_after / draw_frame0) are single-row cells, B=%d", c, B);
+    }
+    return 0;
+}
+
+// The launch shape of a pass's prologue and what it writes; a null pointer = the pass has no such output.
+struct ProTargets {
+    int shape;                // PRO_ROWS / PRO_DRAWS / PRO_TILES
+    float* xnp;               // the assembled, normalised, padded input
+    float* dy;                // y_in - out_1(h_in) per row
+    float* slot0;             // state buffer whose slot 0 is initialised from the cells' h_in (stacked: the top layer's buffer and h_in;
+                              //   k_deep_slot0 then fills every layer)
+    unsigned* zero_words;     // hand-off flags to zero, and how many
+    int nzero;
+    int* zero_status;         // status words to clear, and how many (never the range word)
+    int zero_status_n;
+    int* ws_status;           // the workspace's own status words: home of the range word / epoch when no sink is set
+    bool limbs, new_call;     // range_params
+    float* hx;                // slot 0 as limb triples (V6, V6H)
+    float* xt;                // the input as limb triples (V6) + nxt_slack zero words
+    int nxt_slack;
+    float* hs;                // fp16-pair copies of slot 0 and of the input (SPLIT_F16 off V6)
+    float* xs;
+    long xs_plane;
+    float* gx0;               // frame-0 feedback correction (V6 without a carried-in state)
+    unsigned* ll_counter;     // launch counter of k_gru_steps_ll
+};
+struct RangeSlot { int* word; int val; float at; };      // where and how a kernel behind the prologue reports on the same guard
+
+// One k_prologue launch in the shape the caller names (PRO_*): assemble + scale_in + padding, slot-0 init, dy (the feedback is
+// out_1 of each cell's h_in), frame-0 feedback correction, zeroing.  Brows = ncell * B rows, padded to Bp.
+void run_prologue(const Dims& m, const cvae_net_desc* d, const float* P, const Prep& pl, const PassRows& r, const ProTargets& o,
+                  hipStream_t st, RangeSlot* range = nullptr) {
+    const Cell* cells = r.cells;
+    const int ncell = r.ncell, B = r.B, T = r.T, Bp = r.Bp, shape = o.shape;
+    const int Brows = ncell * B, Tp = T + 2 * m.pad;
+    ProParams pp;
+    memset(&pp, 0, sizeof(pp));
+    for (int c = 0; c < ncell; ++c) {
+        const cvae_pass_input* in = cells[c].in;
+        pp.cell[c].seg0 = CvaeSeg{in->seg0.ptr, in->seg0.width, in->seg0.row_stride};
+        pp.cell[c].seg1 = CvaeSeg{in->seg1.ptr, in->seg1.width, in->seg1.row_stride};
+        pp.cell[c].lat = in->lat;
+        pp.cell[c].eps = in->eps;
+        pp.cell[c].seed = in->seed;
+        pp.cell[c].draw = in->draw_id;
+        pp.cell[c].y_in = cells[c].y_in;
+        pp.cell[c].h_in = cells[c].h_in;
+        pp.cell[c].frames = in->frames;
+        pp.cell[c].n_draws = in->n_draws;
+        pp.cell[c].ctx_before = in->ctx_before; pp.cell[c].ctx_after = in->ctx_after;
+        pp.cell[c].draw_frame0 = (long)in->draw_frame0; pp.cell[c].eps_stride = (long)in->eps_draw_stride;
+        if (in->lat) pp.L = in->lat_dim;
+    }
+    pp.ncell = ncell;
+    pp.frame0 = (uint64_t)cx().draw_row0 * (uint64_t)T;
+    pp.sin_w = d->has_scale_in ? P + pl.sin_w : nullptr;
+    pp.sin_b = d->has_scale_in ? P + pl.sin_b : nullptr;
+    pp.wo = P + pl.wo; pp.bo = P + pl.bo;
+    pp.B = B; pp.T = T; pp.C = m.C; pp.Cp = m.Cp; pp.pad = m.pad; pp.Co = m.Co; pp.H = m.H; pp.Bp = Bp;
+    pp.nslack = 64 * m.KFW + 64;
+    pp.mtot = r.mtot;
+    pp.xnp = o.xnp; pp.hbuf = o.slot0; pp.dy = o.dy;
+    pp.hx = o.hx; pp.xt = o.xt; pp.nxt_slack = o.nxt_slack;
+    pp.hs = o.hs; pp.xs = o.xs; pp.xs_plane = o.xs_plane;
+    pp.zero_words = o.zero_words; pp.nzero = o.nzero;
+    pp.zero_status = o.zero_status; pp.zero_status_n = o.zero_status_n;
+    pp.ll_counter = o.ll_counter;
+    pp.nA = (shape == PRO_TILES ? Bp / 32 : Brows) * Tp;      // PRO_TILES: one block per (32-row tile, padded frame)
+    pp.nH = (int)nblk((long)Bp * m.H, 1024);
+    pp.nD = (int)nblk((long)Brows * m.Co, 64);
+    pp.nG = o.gx0 ? (int)nblk((long)Brows * m.H3 / 4, shape == PRO_ROWS ? 64 : 256) : 0;      // (four columns per thread of the launch's block size)
+    pp.gx0 = o.gx0; pp.wyT = P + pl.wyT;
+    range_params(pp, o.ws_status, o.limbs, o.new_call, P, pl);
+    if (range) *range = RangeSlot{pp.range_word, pp.range_val, pp.range_at};
+    const dim3 gp(pp.nA + pp.nH + pp.nD + pp.nG + 1);
+    if (shape == PRO_TILES)
+        hipLaunchKernelGGL((k_prologue), gp, dim3(256),
+                           (size_t)32 * (m.C + 1) * sizeof(float) + (size_t)(m.Cp / 8) * 1280 + (size_t)32 * pp.L * sizeof(float), st, pp);
+    else if (shape == PRO_DRAWS)     // 256 threads per block: the draws of a frame are summed in parallel slices
+        hipLaunchKernelGGL((k_prologue), gp, dim3(256), (size_t)(m.C + 1024 + 256) * sizeof(float), st, pp);
+    else
+        hipLaunchKernelGGL((k_prologue), gp, dim3(64), m.C * sizeof(float), st, pp);
+}
+
+// gx[b*Tp + t] = afold . xnp[b, t:t+R, :] + cfold for all frames: one GEMM over overlapping rows (lda = Cp), in front of every
+// recurrence that has no front-end of its own
+void run_front_end_gemm(const Dims& m, const float* P, const Prep& pl, const float* xnp, float* gx, int rows, int Tp, hipStream_t st) {
+    const int M = rows * Tp, N = m.H3;
+    hipLaunchKernelGGL((k_gemm_nt<4, 4, 2, 2, false>), dim3(nblk(N, 128), nblk(M, 128)), dim3(256), 0, st, xnp, (long)m.Cp, 0L,
+                       P + pl.afold, (long)m.Kfe, P + pl.cfold, gx, (long)m.H3, M, N, m.Kfe);
+}
+
+// Projection of the fp32 states in hbuf (slots 1..T), as plain_projection() chose: PROJ_FUSED = k_outproj (scale_out folded in,
+// clamp, written straight into [B][T][Co]); PROJ_GEMM = y[t*Bp + b] = out_1(h_t) (A = hbuf chunk-major, rows offset by Bp) and one
+// k_epilogue per cell, which also leaves the raw last projection in y_last.
+void run_projection(const Dims& m, const cvae_net_desc* d, const float* P, const Prep& pl, const PassRows& r, int proj, const float* hbuf,
+                    float* y, int clamp_lat_dim, hipStream_t st) {
+    const Cell* cells = r.cells;
+    const int ncell = r.ncell, B = r.B, T = r.T, Bp = r.Bp;
+    const long mtot = r.mtot;
+    if (proj == PROJ_FUSED) {
+        OutParams op;
+        op.hbuf = hbuf; op.mtot = mtot; op.wo2 = P + pl.wo2; op.bo2 = P + pl.bo2; op.H = m.H; op.Bp = Bp; op.T = T;
+        op.B = B; op.ncell = ncell; op.Co = m.Co; op.clamp_from = d->has_scale_out ? -1 : clamp_dim(clamp_lat_dim);
+        op.clamp_min = clamp_floor(clamp_lat_dim);
+        for (int c = 0; c < CVAE_MAX_CELLS; ++c) op.out[c] = c < ncell ? cells[c].trj_out : nullptr;
+        const int ntn = m.Cop / 16;
+        const unsigned nb = (unsigned)((long)T * Bp / 16);
+        const size_t lds = (size_t)4 * 16 * (m.Cop + 4) * sizeof(float);
+        void (*const kout)(OutParams) = ntn == 1 ? k_outproj<1> : ntn == 4 ? k_outproj<4> : k_outproj<8>;
+        hipLaunchKernelGGL(kout, dim3(nb), dim3(256), lds, st, op);
+        return;
+    }
+    const int M = T * Bp, N = m.Co;
+    hipLaunchKernelGGL((k_gemm_nt<2, 4, 4, 1, true>), dim3(nblk(N, 64), nblk(M, 128)), dim3(256), 0, st, hbuf + (long)Bp * 16, 0L, mtot,
+                       P + pl.wo, (long)m.H, P + pl.bo, y, (long)m.Cop, M, N, m.H);
+    for (int c = 0; c < ncell; ++c) {
+        EpiParams ep;
+        ep.y = y; ep.ldy = m.Cop;
+        ep.sout_w = d->has_scale_out ? P + pl.sout_w : nullptr;
+        ep.sout_b = d->has_scale_out ? P + pl.sout_b : nullptr;
+        ep.clamp_from = d->has_scale_out ? -1 : clamp_dim(clamp_lat_dim);
+        ep.clamp_min = clamp_floor(clamp_lat_dim);
+        ep.B = B; ep.Bp = Bp; ep.T = T; ep.Co = m.Co; ep.b0 = c * B;
+        ep.trj_out = cells[c].trj_out; ep.y_last = cells[c].y_last;
+        ep.t_last = last_slot(cells[c].in, T) - 1;
+        hipLaunchKernelGGL((k_epilogue), dim3(B * T), dim3(64), m.Co * sizeof(float), st, ep);
+    }
+}
+
+// k_hlast for every cell that asks: its h_last = the state in slot last_slot() of hbuf (one layer's buffer)
+void run_last_states(const Dims& m, const PassRows& r, const float* hbuf, hipStream_t st) {
+    for (int c = 0; c < r.ncell; ++c)
+        if (r.cells[c].h_last)
+            hipLaunchKernelGGL((k_hlast), dim3(nblk((long)r.B * m.H, 256)), dim3(256), 0, st, hbuf, r.mtot, r.cells[c].h_last, r.B, r.Bp,
+                               m.H, last_slot(r.cells[c].in, r.T), c * r.B);
+}
+
+// plan, prologue, the recurrence (one switch on the planned form), projection, last states
 int run_pass(const Dims& m, const cvae_net_desc* d, const float* P, const Cell* cells, int ncell, int B, int T,
              int clamp_lat_dim, float* ws, int* status, int flags, hipStream_t st, bool clear_status = false) {
     const Prep pl = prep_layout(m, d->has_scale_in != 0, d->has_scale_out != 0);
@@ -574,17 +745,12 @@ int run_pass(const Dims& m, const cvae_net_desc* d, const float* P, const Cell* 
     const Work wl = work_layout(m, Brows, T);
     int* const ws_status = status;
     if (cx().status_sink) status = cx().status_sink;    // host-visible sticky word: a time-out is seen without reading the workspace back
-    for (int c = 0; c < ncell; ++c) {
-        const cvae_pass_input* in = cells[c].in;
-        const int w_in = in->seg0.width + (in->lat ? in->lat_dim : in->seg1.width);
-        if (w_in != m.C) return fail(-1, "pass input width %d != in_dim %d", w_in, m.C);
-    }
-    if (ncell > CVAE_MAX_CELLS) return fail(-1, "at most %d stacked cells per pass", CVAE_MAX_CELLS);
+    const PassRows rows = {cells, ncell, B, T, wl.Bp, wl.mtot};
+    if (int rc = check_cells(m, rows)) return rc;
     unsigned* bar = (unsigned*)(ws + wl.status) + 8;  // status words themselves are sticky: zeroed by the entry point
     float* xnp = ws + wl.xnp;
     float* gx = ws + wl.gx;
     float* hbuf = ws + wl.hbuf;
-    float* y = ws + wl.y;
     float* dy = ws + wl.dy;
     unsigned* hflags = (unsigned*)(ws + wl.flags);
     long long* const step_prof = (flags & CVAE_FLAG_STEP_TIMING) ? (long long*)(ws + wl.prof) : nullptr;
@@ -598,78 +764,30 @@ int run_pass(const Dims& m, const cvae_net_desc* d, const float* P, const Cell* 
     }
     const EvalPlan pn = plan_eval_pass(m, Brows, T, flags, cus, image_known_unfit(P), facts);
 
-    {   // one prologue launch: assemble + scale_in + padding, slot-0 init, frame-0 feedback correction, zeroing
-        ProParams pp;
-        memset(&pp, 0, sizeof(pp));
-        for (int c = 0; c < ncell; ++c) {
-            const cvae_pass_input* in = cells[c].in;
-            pp.cell[c].seg0 = CvaeSeg{in->seg0.ptr, in->seg0.width, in->seg0.row_stride};
-            pp.cell[c].seg1 = CvaeSeg{in->seg1.ptr, in->seg1.width, in->seg1.row_stride};
-            pp.cell[c].lat = in->lat;
-            pp.cell[c].eps = in->eps;
-            pp.cell[c].seed = in->seed;
-            pp.cell[c].draw = in->draw_id;
-            pp.cell[c].y_in = cells[c].y_in;
-            pp.cell[c].h_in = cells[c].h_in;
-            pp.cell[c].frames = in->frames;
-            pp.cell[c].n_draws = in->n_draws;
-            pp.cell[c].ctx_before = in->ctx_before; pp.cell[c].ctx_after = in->ctx_after;
-            pp.cell[c].draw_frame0 = (long)in->draw_frame0; pp.cell[c].eps_stride = (long)in->eps_draw_stride;
-            if (in->frames < 0 || in->frames > T) return fail(-1, "cell %d: frames %d outside [0, T=%d]", c, in->frames, T);
-            if (in->ctx_before < 0 || in->ctx_after < 0 || in->draw_frame0 < 0 || in->eps_draw_stride < 0)
-                return fail(-1, "cell %d: negative window context / draw origin", c);
-            if ((in->ctx_before || in->ctx_after || in->draw_frame0) && B != 1)
-                return fail(-1, "cell %d: windows of a longer utterance (ctx_before / ctx_after / draw_frame0) are single-row cells, B=%d", c, B);
-            if (in->lat) pp.L = in->lat_dim;
-        }
-        pp.ncell = ncell;
-        pp.frame0 = (uint64_t)cx().draw_row0 * (uint64_t)T;
-        pp.sin_w = d->has_scale_in ? P + pl.sin_w : nullptr;
-        pp.sin_b = d->has_scale_in ? P + pl.sin_b : nullptr;
-        pp.wo = P + pl.wo; pp.bo = P + pl.bo;
-        pp.B = B; pp.T = T; pp.C = m.C; pp.Cp = m.Cp; pp.pad = m.pad; pp.Co = m.Co; pp.H = m.H; pp.Bp = wl.Bp;
-        pp.nslack = 64 * m.KFW + 64;
-        pp.mtot = wl.mtot;
-        pp.xnp = xnp; pp.hbuf = hbuf; pp.dy = dy;
+    {
+        ProTargets o = {};
+        o.shape = pn.prologue; o.xnp = xnp; o.dy = dy;
+        o.slot0 = hbuf;
+        // bar (8 words) ... flags are not adjacent: zero the flags here, the barrier words with the status block
+        o.zero_words = hflags; o.nzero = wl.Bp / 16 * m.nch;
+        o.zero_status = clear_status ? status : nullptr;     // (the recurrent kernel, the first writer of these words, runs behind the prologue)
+        o.zero_status_n = cx().status_sink ? 4 : 8;          // (a sink is int32[4]: eight words ran over the end of the caller's buffer)
+        o.ws_status = ws_status; o.limbs = pn.limbs; o.new_call = clear_status;
         // k_gru_steps_v6 reads limb triples -- the state always, the input where its front-end is fused -- every other kernel the fp32 buffers
         const bool triples = pn.form == CVAE_EVAL_V6 || pn.form == CVAE_EVAL_V6H;
-        pp.hx = triples ? ws + wl.hs : nullptr;    // (the pair buffer's space: same size, never both in one pass)
-        pp.xt = pn.form == CVAE_EVAL_V6 ? ws + wl.xt : nullptr;
-        pp.nxt_slack = (int)wl.xt_slack;
-        pp.hs = pn.pairs ? ws + wl.hs : nullptr;
-        pp.xs = pn.pairs ? ws + wl.xs : nullptr;
-        pp.xs_plane = wl.xs_plane;
-        // bar (8 words) ... flags are not adjacent: zero the flags here, the barrier words with the status block
-        pp.zero_words = hflags; pp.nzero = wl.Bp / 16 * m.nch;
-        pp.zero_status = clear_status ? status : nullptr;     // (the recurrent kernel, the first writer of these words, runs behind the prologue)
-        pp.zero_status_n = cx().status_sink ? 4 : 8;          // (a sink is int32[4]: eight words ran over the end of the caller's buffer)
-        pp.ll_counter = pn.form == CVAE_EVAL_LL ? (unsigned*)(ws + wl.status) + 16 : nullptr;
-        pp.nA = (pn.prologue == PRO_TILES ? wl.Bp / 32 : Brows) * wl.Tp;      // PRO_TILES: one block per (32-row tile, padded frame)
-        pp.nH = (int)nblk((long)wl.Bp * m.H, 1024);
-        pp.nD = (int)nblk((long)Brows * m.Co, 64);
-        pp.nG = pn.gx0_ready ? (int)nblk((long)Brows * m.H3 / 4, pn.prologue == PRO_ROWS ? 64 : 256) : 0;      // (four columns per thread of the launch's block size)
-        pp.gx0 = ws + wl.gx0; pp.wyT = P + pl.wyT;
-        range_params(pp, ws_status, pn.limbs, clear_status, P, pl);
-        const dim3 gp(pp.nA + pp.nH + pp.nD + pp.nG + 1);
-        if (pn.prologue == PRO_TILES)
-            hipLaunchKernelGGL((k_prologue), gp, dim3(256),
-                               (size_t)32 * (m.C + 1) * sizeof(float) + (size_t)(m.Cp / 8) * 1280 + (size_t)32 * pp.L * sizeof(float), st, pp);
-        else if (pn.prologue == PRO_DRAWS)     // 256 threads per block: the draws of a frame are summed in parallel slices
-            hipLaunchKernelGGL((k_prologue), gp, dim3(256), (size_t)(m.C + 1024 + 256) * sizeof(float), st, pp);
-        else
-            hipLaunchKernelGGL((k_prologue), gp, dim3(64), m.C * sizeof(float), st, pp);
+        o.hx = triples ? ws + wl.hs : nullptr;    // (the pair buffer's space: same size, never both in one pass)
+        o.xt = pn.form == CVAE_EVAL_V6 ? ws + wl.xt : nullptr;
+        o.nxt_slack = (int)wl.xt_slack;
+        o.hs = pn.pairs ? ws + wl.hs : nullptr;
+        o.xs = pn.pairs ? ws + wl.xs : nullptr;
+        o.xs_plane = wl.xs_plane;
+        o.gx0 = pn.gx0_ready ? ws + wl.gx0 : nullptr;
+        o.ll_counter = pn.form == CVAE_EVAL_LL ? (unsigned*)(ws + wl.status) + 16 : nullptr;
+        run_prologue(m, d, P, pl, rows, o, st);
     }
 
     const size_t lds2 = (4 * 16 * 84 + 16 * 16) * sizeof(float);
     const bool prof = (flags & CVAE_FLAG_PROFILE) && prof_begin(st, ncell * B, m.C);
-    // gx[b*Tp + t] = afold . xnp[b, t:t+R, :] + cfold for all frames: one GEMM over overlapping rows (lda = Cp), in front of every
-    // form whose kernel has no front-end of its own
-    const auto front_end_gemm = [&]() {
-        const int M = Brows * wl.Tp, N = m.H3;
-        hipLaunchKernelGGL((k_gemm_nt<4, 4, 2, 2, false>), dim3(nblk(N, 128), nblk(M, 128)), dim3(256), 0, st,
-                           (const float*)xnp, (long)m.Cp, 0L, P + pl.afold, (long)m.Kfe, P + pl.cfold, gx, (long)m.H3,
-                           M, N, m.Kfe);
-    };
     // a refused cooperative launch (error handling, not selection: the plan only names kernels that exist)
     const auto refused = [](hipError_t e) {
         if (e == hipSuccess) return false;
@@ -677,7 +795,8 @@ int run_pass(const Dims& m, const cvae_net_desc* d, const float* P, const Cell* 
         return true;
     };
     int form = pn.form;      // steps down where a launch is refused
-    if (form == CVAE_EVAL_LL || form == CVAE_EVAL_V6H || form <= CVAE_EVAL_V2) front_end_gemm();
+    // the front-end GEMM in front of every form whose kernel has no front-end of its own
+    if (form == CVAE_EVAL_LL || form == CVAE_EVAL_V6H || form <= CVAE_EVAL_V2) run_front_end_gemm(m, P, pl, xnp, gx, Brows, wl.Tp, st);
     switch (form) {
     case CVAE_EVAL_LL: {
         StepLLParams q;
@@ -735,7 +854,7 @@ int run_pass(const Dims& m, const cvae_net_desc* d, const float* P, const Cell* 
         q.afold2 = P + pl.afold3;     // v4: front-end weights in LDS, double-buffered h operands
         const size_t lds4 = lds2 + (size_t)4 * m.KFW * 3 * 256 * sizeof(float);
         if (!refused(cvae_launch_coop(pn.k4, g, dim3(256), lds4, st, q))) break;
-        front_end_gemm();
+        run_front_end_gemm(m, P, pl, xnp, gx, Brows, wl.Tp, st);
         form = CVAE_EVAL_V2;
     }
         [[fallthrough]];
@@ -778,45 +897,10 @@ int run_pass(const Dims& m, const cvae_net_desc* d, const float* P, const Cell* 
         for (int c = 0; c < CVAE_MAX_CELLS; ++c) op.out[c] = c < ncell ? cells[c].trj_out : nullptr;
         const dim3 g((unsigned)((long)T * wl.Bp / 32), (unsigned)((m.Cop + 31) / 32));
         hipLaunchKernelGGL(pn.kout6, g, dim3(256), (size_t)4 * 32 * 36 * sizeof(float), st, op);
-    } else if (pn.proj == PROJ_FUSED) {
-        // fused projection: scale_out folded in, clamp, written straight into [B][T][Co]
-        OutParams op;
-        op.hbuf = hbuf; op.mtot = wl.mtot; op.wo2 = P + pl.wo2; op.bo2 = P + pl.bo2; op.H = m.H; op.Bp = wl.Bp; op.T = T;
-        op.B = B; op.ncell = ncell; op.Co = m.Co; op.clamp_from = d->has_scale_out ? -1 : clamp_dim(clamp_lat_dim);
-        op.clamp_min = clamp_floor(clamp_lat_dim);
-        for (int c = 0; c < CVAE_MAX_CELLS; ++c) op.out[c] = c < ncell ? cells[c].trj_out : nullptr;
-        const int ntn = m.Cop / 16;
-        const unsigned nb = (unsigned)((long)T * wl.Bp / 16);
-        const size_t lds = (size_t)4 * 16 * (m.Cop + 4) * sizeof(float);
-        void (*const kout)(OutParams) = ntn == 1 ? k_outproj<1> : ntn == 4 ? k_outproj<4> : k_outproj<8>;
-        hipLaunchKernelGGL(kout, dim3(nb), dim3(256), lds, st, op);
     } else {
-        // y[t*Bp + b] = out_1(h_t): A = hbuf slots 1..T (chunk-major), rows offset by Bp; then the epilogue kernel
-        const int M = T * wl.Bp, N = m.Co;
-        hipLaunchKernelGGL((k_gemm_nt<2, 4, 4, 1, true>), dim3(nblk(N, 64), nblk(M, 128)), dim3(256), 0, st,
-                           (const float*)(hbuf + (long)wl.Bp * 16), 0L, wl.mtot, P + pl.wo, (long)m.H, P + pl.bo, y,
-                           (long)m.Cop, M, N, m.H);
-        for (int c = 0; c < ncell; ++c) {
-            EpiParams ep;
-            ep.y = y; ep.ldy = m.Cop;
-            ep.sout_w = d->has_scale_out ? P + pl.sout_w : nullptr;
-            ep.sout_b = d->has_scale_out ? P + pl.sout_b : nullptr;
-            ep.clamp_from = d->has_scale_out ? -1 : clamp_dim(clamp_lat_dim);
-            ep.clamp_min = clamp_floor(clamp_lat_dim);
-            ep.B = B; ep.Bp = wl.Bp; ep.T = T; ep.Co = m.Co; ep.b0 = c * B;
-            ep.trj_out = cells[c].trj_out; ep.y_last = cells[c].y_last;
-            ep.t_last = (cells[c].in && cells[c].in->frames > 0 && cells[c].in->frames < T ? cells[c].in->frames : T) - 1;
-            hipLaunchKernelGGL((k_epilogue), dim3(B * T), dim3(64), m.Co * sizeof(float), st, ep);
-        }
+        run_projection(m, d, P, pl, rows, pn.proj, hbuf, ws + wl.y, clamp_lat_dim, st);
     }
-    for (int c = 0; c < ncell; ++c)
-        if (cells[c].h_last)
-            // the state a cell carries on is the one behind ITS last valid frame (slot `frames`), not behind the pass's T steps: a
-            // cell shorter than the pass keeps stepping over padding (or, for a window with ctx_after > 0, over frames that belong
-            // to the next window), and continuing from slot T restarted the next window from the wrong state
-            hipLaunchKernelGGL((k_hlast), dim3(nblk((long)B * m.H, 256)), dim3(256), 0, st, (const float*)hbuf, wl.mtot,
-                               cells[c].h_last, B, wl.Bp, m.H,
-                               cells[c].in && cells[c].in->frames > 0 && cells[c].in->frames < T ? cells[c].in->frames : T, c * B);
+    run_last_states(m, rows, hbuf, st);
     CVAE_HIP_OK(hipGetLastError());
     return 0;
 }

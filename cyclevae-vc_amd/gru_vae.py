@@ -226,13 +226,12 @@ def _with_range_retry(fn):
         _range_fallback -= 1
 
 
-def _deep_flags(f):
-    """Flags of a pass of a stacked module: its fp32-operand recurrence is the any-H kernel (k_gru_steps_deep)."""
-    return f | _cabi.FLAG_GENERIC_STEP if _range_fallback else f
-
-
-def _flags():
+def _flags(layers=1):
+    """Flags of an eval pass of a module with `layers` GRU layers.  While a call is repeated on the fp32-operand kernels
+    (_range_fallback) the kernel choice is fp32, which for a stacked module is the any-H recurrence (k_gru_steps_deep)."""
     f = _cabi.FLAG_PERSISTENT if _persistent else 0
+    if _range_fallback and layers > 1:
+        f |= _cabi.FLAG_GENERIC_STEP
     if _hoisted_frontend:
         f |= _cabi.FLAG_HOISTED_FRONTEND
     kern = "fp32" if _range_fallback else (_force_kernel or "exact3")
@@ -314,30 +313,14 @@ class _Prepared(object):
         self.key = None
         self.image = None
         self.desc = None
+        self.layers = 1
         self.ws = {}
 
     def get(self, mod, device):
+        """The image of cvae_net_prepare_deep (hidden_layers == 1: the one-layer image), rebuilt when a tensor of ANY layer changes."""
         lib = _lib()
         fields = _weight_fields(mod, device)
-        key = tuple((f, t.data_ptr(), t._version) for f, t in sorted(fields.items()))
         L = mod.hidden_layers
-        if L > 1:
-            return self._get_deep(mod, device, lib, fields, key, L)
-        if key != self.key:
-            d = lib.desc(mod.in_dim, mod.out_dim, mod.hidden_units, mod.kernel_size, mod.dilation_size,
-                         mod.scale_in_flag, mod.scale_out_flag)
-            image = torch.empty(lib.prepared_bytes(d), dtype=torch.uint8, device=device)
-            scratch = torch.empty(lib.prepare_scratch_bytes(d), dtype=torch.uint8, device=device)
-            lib.net_prepare(d, {f: t.data_ptr() for f, t in fields.items()}, image.data_ptr(), image.numel(),
-                            scratch.data_ptr(), scratch.numel(), _stream())
-            # once per build (synchronises): an image whose folded weights leave the fp16 range is run on the fp32-operand kernels
-            # from the start -- the library context remembers the answer by the image's address
-            self.in_range = lib.net_prepared_in_range(d, 1, image.data_ptr(), _stream())
-            self.key, self.image, self.desc, self._keep = key, image, d, (fields, scratch)
-        return self.desc, self.image
-
-    def _get_deep(self, mod, device, lib, fields, key, L):
-        """hidden_layers >= 2: the image of cvae_net_prepare_deep, rebuilt when a tensor of ANY layer changes."""
         upper = []
         for l in range(1, L):
             ts = []
@@ -347,7 +330,8 @@ class _Prepared(object):
                     raise RuntimeError("parameter gru.%s is %s/%s, expected float32 on %s" % (leaf % l, t.device, t.dtype, device))
                 ts.append(t.detach() if t.is_contiguous() else t.detach().contiguous())
             upper.append(tuple(ts))
-        key = key + tuple((l, t.data_ptr(), t._version) for l, ts in enumerate(upper) for t in ts)
+        key = tuple((f, t.data_ptr(), t._version) for f, t in sorted(fields.items()))
+        key += tuple((l, t.data_ptr(), t._version) for l, ts in enumerate(upper) for t in ts)
         if key != self.key:
             d = lib.desc(mod.in_dim, mod.out_dim, mod.hidden_units, mod.kernel_size, mod.dilation_size,
                          mod.scale_in_flag, mod.scale_out_flag)
@@ -355,16 +339,17 @@ class _Prepared(object):
             scratch = torch.empty(lib.prepare_scratch_bytes_deep(d, L), dtype=torch.uint8, device=device)
             lib.net_prepare_deep(d, L, {f: t.data_ptr() for f, t in fields.items()}, [tuple(t.data_ptr() for t in ts) for ts in upper],
                                  image.data_ptr(), image.numel(), scratch.data_ptr(), scratch.numel(), _stream())
+            # once per build (synchronises): an image whose folded weights leave the fp16 range is run on the fp32-operand kernels
+            # from the start -- the library context remembers the answer by the image's address
             self.in_range = lib.net_prepared_in_range(d, L, image.data_ptr(), _stream())
             self.key, self.image, self.desc, self._keep = key, image, d, (fields, upper, scratch)
-            self.layers = L
+        self.layers = L
         return self.desc, self.image
 
     def workspace(self, B, T, device):
         """One buffer per device, grown to the largest (B, T) seen; a replaced buffer goes back to the caching allocator, which
         orders its reuse after the work already queued on the stream that used it (the eval passes run on one stream)."""
-        L = getattr(self, "layers", 1)
-        need = _lib().pass_workspace_bytes(self.desc, B, T) if L == 1 else _lib().pass_workspace_bytes_deep(self.desc, L, B, T)
+        need = _lib().pass_workspace_bytes_deep(self.desc, self.layers, B, T)
         buf = self.ws.get(device)
         if buf is None or buf.numel() < need:
             buf = self.ws[device] = torch.empty(need, dtype=torch.uint8, device=device)
@@ -677,11 +662,10 @@ class GRU_RNN(nn.Module):
         needs_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
         if needs_grad or p_drop > 0:
             return self._forward_train(x, y_in, h_in, p_drop, clamp)
-        if self.hidden_layers > 1:
-            return _with_range_retry(lambda: self._forward_deep(x, y_in, h_in, clamp))
         return _with_range_retry(lambda: self._forward_eval(x, y_in, h_in, clamp))
 
     def _forward_eval(self, x, y_in, h_in, clamp):
+        """Eval pass (cvae_gru_rnn_forward_deep; one layer: the one-layer pass): h_in / the returned h are [hidden_layers, B, H]."""
         two_d = x.dim() == 2
         if two_d:
             x = x.unsqueeze(0)
@@ -689,56 +673,25 @@ class GRU_RNN(nn.Module):
         B, T, Cin = x.shape
         if Cin != self.in_dim:
             raise ValueError("input has %d features, network expects %d" % (Cin, self.in_dim))
-        dev = x.device
+        L, H, dev = self.hidden_layers, self.hidden_units, x.device
         d, image = self._prep.get(self, dev)
         ws = self._prep.workspace(B, T, dev)
         y0 = y_in.to(torch.float32).reshape(B, self.out_dim).contiguous()
-        h0 = None if h_in is None else h_in.to(torch.float32).reshape(B, self.hidden_units).contiguous()
+        h0 = None
+        if h_in is not None:
+            if L > 1 and h_in.numel() != L * B * H:
+                raise ValueError("h_in has shape %s, a %d-layer GRU takes [%d, %d, %d]" % (tuple(h_in.shape), L, L, B, H))
+            h0 = h_in.to(torch.float32).reshape(L, B, H).contiguous()
         trj = torch.empty(B, T, self.out_dim, dtype=torch.float32, device=dev)
         y_last = torch.empty(B, 1, self.out_dim, dtype=torch.float32, device=dev)
-        h_last = torch.empty(1, B, self.hidden_units, dtype=torch.float32, device=dev)
+        h_last = torch.empty(L, B, H, dtype=torch.float32, device=dev)
         lib = _lib()
         pin = lib.pass_input((x.data_ptr(), Cin, Cin))
-        lib.gru_rnn_forward(d, image.data_ptr(), pin, y0.data_ptr(), None if h0 is None else h0.data_ptr(), B, T,
-                            clamp, trj.data_ptr(), y_last.data_ptr(), h_last.data_ptr(),
-                            ws.data_ptr(), ws.numel(), _flags(), _stream())
+        lib.gru_rnn_forward_deep(d, L, image.data_ptr(), pin, y0.data_ptr(), None if h0 is None else h0.data_ptr(), B, T, clamp,
+                                 trj.data_ptr(), y_last.data_ptr(), h_last.data_ptr(), ws.data_ptr(), ws.numel(), _flags(L), _stream())
         if two_d:
             trj = trj.squeeze(0)
         return trj, y_last, h_last
-
-
-def _forward_deep(self, x, y_in, h_in, clamp_lat_dim):
-    """Eval pass of a module with hidden_layers >= 2 (cvae_gru_rnn_forward_deep): h_in / the returned h are [L, B, H]."""
-    two_d = x.dim() == 2
-    if two_d:
-        x = x.unsqueeze(0)
-    x = x.to(torch.float32).contiguous()
-    B, T, Cin = x.shape
-    if Cin != self.in_dim:
-        raise ValueError("input has %d features, network expects %d" % (Cin, self.in_dim))
-    L, H, dev = self.hidden_layers, self.hidden_units, x.device
-    d, image = self._prep.get(self, dev)
-    ws = self._prep.workspace(B, T, dev)
-    y0 = y_in.to(torch.float32).reshape(B, self.out_dim).contiguous()
-    h0 = None
-    if h_in is not None:
-        if h_in.numel() != L * B * H:
-            raise ValueError("h_in has shape %s, a %d-layer GRU takes [%d, %d, %d]" % (tuple(h_in.shape), L, L, B, H))
-        h0 = h_in.to(torch.float32).reshape(L, B, H).contiguous()
-    trj = torch.empty(B, T, self.out_dim, dtype=torch.float32, device=dev)
-    y_last = torch.empty(B, 1, self.out_dim, dtype=torch.float32, device=dev)
-    h_last = torch.empty(L, B, H, dtype=torch.float32, device=dev)
-    lib = _lib()
-    pin = lib.pass_input((x.data_ptr(), Cin, Cin))
-    lib.gru_rnn_forward_deep(d, L, image.data_ptr(), pin, y0.data_ptr(), None if h0 is None else h0.data_ptr(), B, T, clamp_lat_dim,
-                             trj.data_ptr(), y_last.data_ptr(), h_last.data_ptr(), ws.data_ptr(), ws.numel(), _deep_flags(_flags()),
-                             _stream())
-    if two_d:
-        trj = trj.squeeze(0)
-    return trj, y_last, h_last
-
-
-GRU_RNN._forward_deep = _forward_deep
 
 
 def run_cells(mod, d, image, pins, y_ins, T, clamp_lat_dim, trj_outs, ws, flags, stream):
@@ -751,12 +704,12 @@ def run_cells(mod, d, image, pins, y_ins, T, clamp_lat_dim, trj_outs, ws, flags,
         return
     for pin, y, out in zip(pins, y_ins, trj_outs):
         lib.gru_rnn_forward_deep(d, mod.hidden_layers, image.data_ptr(), pin, y, None, 1, T, clamp_lat_dim, out, None, None,
-                                 ws.data_ptr(), ws.numel(), _deep_flags(flags), stream)
+                                 ws.data_ptr(), ws.numel(), flags, stream)
 
 
 def cells_workspace_bytes(mod, d, ncell, T):
-    lib = _lib()
-    return lib.pass_workspace_bytes(d, ncell, T) if mod.hidden_layers == 1 else lib.pass_workspace_bytes_deep(d, mod.hidden_layers, 1, T)
+    """ncell rows for the one row-stacked pass of a one-layer module, one row for the cell-by-cell passes of a stacked one."""
+    return _lib().pass_workspace_bytes_deep(d, mod.hidden_layers, ncell if mod.hidden_layers == 1 else 1, T)
 
 
 def _forward_train(self, x, y_in, h_in, p_drop, clamp_lat_dim):
@@ -1128,11 +1081,11 @@ class CycleChain(object):
         wse, wsd = enc._prep.workspace(B, T, dev), dec._prep.workspace(B, T, dev)
         out = {k: torch.empty(n if outputs else 1, B, T, c, dtype=torch.float32, device=dev)
                for k, c in (("lat", 2 * L), ("rec", Co), ("cv", Co), ("latcv", 2 * L), ("reccyc", Co))}
-        flags, st = _flags(), _stream()
+        st = _stream()
 
         def run(mod, d_, img, ws, pin, y, clamp, dst):
             lib.gru_rnn_forward_deep(d_, mod.hidden_layers, img.data_ptr(), pin, y.data_ptr(), None, B, T, clamp, dst.data_ptr(), None,
-                                     None, ws.data_ptr(), ws.numel(), _deep_flags(flags) if mod.hidden_layers > 1 else flags, st)
+                                     None, ws.data_ptr(), ws.numel(), _flags(mod.hidden_layers), st)
 
         prev = None
         for i in range(n):

@@ -119,7 +119,7 @@ def _encode_pairs(model_encoder, pairs, y_in_pp, lat_dim):
         pins += [lib.pass_input((a.data_ptr(), Cin, Cin), frames=ta), lib.pass_input((b.data_ptr(), Cin, Cin), frames=tb)]
     # (hidden_layers >= 2: the same cells pass by pass, gru_vae.run_cells)
     gru_vae.run_cells(model_encoder, de, ie, pins, [ypp.data_ptr()] * (2 * N), T, L, [lat[r].data_ptr() for r in range(2 * N)], ws,
-                      gru_vae._flags(), st)
+                      gru_vae._flags(model_encoder.hidden_layers), st)
     return {"N": N, "lens": lens, "T": T, "lat": lat, "dev": dev, "keep": (feats, ypp, ws)}
 
 
@@ -165,7 +165,8 @@ def _decode_pairs(model_decoder, enc, y_in_src, y_in_trg, lat_dim, n_smpl_dec, e
         d0 = 2 * n * (q if pair_ids is None else int(pair_ids[q]))
         pins += [cell(1, 2 * q, es, ta, d0), cell(0, 2 * q, es, ta, d0), cell(1, 2 * q + 1, et, tb, d0 + n)]
         yins += [yt.data_ptr(), ys.data_ptr(), yt.data_ptr()]
-    gru_vae.run_cells(model_decoder, dd, idd, pins, yins, T, -1, [out[r].data_ptr() for r in range(3 * N)], ws, gru_vae._flags(), st)
+    gru_vae.run_cells(model_decoder, dd, idd, pins, yins, T, -1, [out[r].data_ptr() for r in range(3 * N)], ws,
+                      gru_vae._flags(model_decoder.hidden_layers), st)
     return out, [(out[3 * q, :ta], out[3 * q + 1, :ta], out[3 * q + 2, :tb], lat[2 * q, :ta], lat[2 * q + 1, :tb])
                  for q, (ta, tb) in enumerate(lens)]
 

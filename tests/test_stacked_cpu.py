@@ -4,6 +4,7 @@ constructor / state_dict, the refusals of what is not covered, and the helper te
 
 Bounds: the emulator's own (header of tests/test_emu_library.py): 5e-5 per pass, 3e-4 per chain.  stacked_ref (fp64) is held to
 1e-6 of the reference's fp32 outputs: ten times the 1e-7 the reference's fp32 result sits from its fp64 result on these networks."""
+import json
 import os
 import re
 
@@ -11,6 +12,7 @@ import numpy as np
 import pytest
 
 import _cabi
+import stacked_digest
 import stacked_ref
 import synth
 from emu_util import NpNet, emu_lib, ptr
@@ -106,6 +108,17 @@ def test_h64_stage6_sequence_vs_golden(lib, golden):
         d = maxdiff(v[0], G[k])
         print("emu h64 L2 stage6 %-10s max|d| = %.3e" % (k, d))
         assert d <= EMU_PASS, (k, d)
+
+
+def test_stacked_pass_bits_are_the_parents(lib):
+    """L = 2, 3 on each recurrence path: prepared images and pass outputs (carried state, injected eps, the n_draws prologue shape,
+    the fused projection) are bit-identical to what the commit before the stacked pass was rebuilt from the one-layer pass's stages
+    produced (tests/stacked_digest.py)."""
+    lib.reset_options()
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "stacked_pass_digests.json")))
+    got = stacked_digest.digests(lib)
+    assert sorted(got) == sorted(want)
+    assert [k for k in sorted(want) if got[k] != want[k]] == []
 
 
 def test_one_layer_through_deep_entry_points_is_bit_identical(lib):
