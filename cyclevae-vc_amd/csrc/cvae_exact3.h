@@ -7,7 +7,9 @@
 // registers per lane and does not fit; LDS is full of front-end weights.  v6 therefore halves the columns per block and
 // doubles the rows: block = 8 hidden units (32 gate columns: r, z, n_in, n_h) x 32 batch rows, one v_mfma_f32_32x32x16_f16
 // tile.  256 blocks at B = 64 as before (128 unit octets x 2 row tiles), the weights are replicated 2x instead of 4x over
-// the chip, and three limbs per weight take 192 registers.
+// the chip, and three limbs per weight take 192 registers.  At H = 1024 those are ACCUMULATOR registers (CVAE_V6_IN_AGPR below):
+// 192 weights + 64 accumulators are the 256 AGPRs of a lane, and the 256 architectural VGPRs (251 used in the encoder instance,
+// 243 in the decoder's) hold the operand rings, the gate inputs and two slots of front-end weights.
 //
 // Arithmetic.  Every fp32 operand x (weights, exchanged state, normalised input) is the exact sum of three halves,
 // x = l0 + l1*s + l2*s^2, s = 2^-11 (cvae_split3_f16).  A product of two such sums is accumulated in fp32 as
@@ -27,6 +29,18 @@
 // profiles/r02_notes_exact3_kernel.md.)
 #pragma once
 #include <cvae_intrin.h>
+
+// CVAE_V6_IN_AGPR(x): from here on the value lives in accumulator registers.  The MFMA takes its A / B operands from either
+// register file on gfx950, so a weight tuple that is only ever an MFMA operand needs no architectural VGPR -- but left to itself
+// the allocator fills the VGPRs first, parks what overflows in AGPRs as SPILLS and copies each back (v_accvgpr_read_b32) in front
+// of every use: 76 copies per step in the H = 1024 instances.  An empty statement with an "a" constraint makes the value an
+// accumulator-class value instead; no instruction is emitted and the builtin MFMA (cvae_mfma_32x32x16_f16) reads it in place, so
+// the compiler keeps every hazard.  Device compile only: the host-fiber build has no register classes.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define CVAE_V6_IN_AGPR(x) asm volatile("" : "+a"(x))
+#else
+#define CVAE_V6_IN_AGPR(x) ((void)0)
+#endif
 
 struct Step6Params {
     const float* gx0;     // null, or [B][3H]: the frame-0 feedback correction, ready-made by the prologue (else cvae_t0_fix forms it here)
@@ -141,8 +155,9 @@ __device__ __forceinline__ f32x16 cvae_zero16() {
 // 256 registers per lane) but STREAMED from L2 every step as bf8 bytes (64 KB per block: the 32 blocks of an XCD share 2 MB, which
 // its L2 holds), through a ring of 4 steps; the operand rings shrink (5 recurrent steps, 3 front-end steps in flight) to make room
 // for the third-limb registers and the fourth accumulator.
-template <int KPW, int KFW, int LIMBS = 3, bool W2S = false>
+template <int KPW, int KFW, int LIMBS = 3, bool W2S = false, bool PROF = false>
 __global__ __launch_bounds__(256, 1) void k_gru_steps_v6(Step6Params p) {
+    static_assert(!(W2S && PROF), "no phase counters in the W2S form: no registers to spare");
     constexpr int RS = 40;                             // row stride of the reduction buffer (conflict-free reads and writes)
     constexpr float S1 = 1.0f / 2048.0f;
 #ifndef CVAE_V6_RD
@@ -151,6 +166,13 @@ __global__ __launch_bounds__(256, 1) void k_gru_steps_v6(Step6Params p) {
     constexpr int RD0 = W2S ? 5 : CVAE_V6_RD;
     constexpr int RD = KPW < RD0 ? KPW : RD0;          // operand ring: 16-k steps in flight per wave (8: swept 4..16 on MI355X)
     constexpr bool HOIST = KFW == 0;
+#ifndef CVAE_V6_WACC
+#define CVAE_V6_WACC 1      // measurement: 0 leaves the weights to the register allocator (profiles/v6_hot_loop_notes.md)
+#endif
+#ifndef CVAE_V6_FPRE
+#define CVAE_V6_FPRE 1      // measurement: 0 reads every front-end weight in front of its MFMAs
+#endif
+    constexpr bool WACC = CVAE_V6_WACC && KPW == 16 && LIMBS == 3 && !W2S;   // H = 1024, three resident limbs: every weight register is an AGPR
     constexpr int RF = HOIST ? 1 : (W2S && KFW > 3 ? 3 : KFW);   // front-end operands: all requested ahead (they land during the publish)
     constexpr int RW = KPW < 4 ? KPW : 4;              // W2S: third weight limbs in flight
     const int tid = threadIdx.x, wave = cvae_uniform(tid >> 6), lane = tid & 63, lc = lane & 31, kh = lane >> 5;
@@ -182,6 +204,14 @@ __global__ __launch_bounds__(256, 1) void k_gru_steps_v6(Step6Params p) {
         w1[s] = *(const f32x4*)(src + 256);
         if constexpr (LIMBS == 3 && !W2S) w2[s] = *(const f32x4*)(src + 512);
     }
+    if constexpr (WACC) {
+#pragma unroll
+        for (int s = 0; s < KPW; ++s) {
+            CVAE_V6_IN_AGPR(w0[s]);
+            CVAE_V6_IN_AGPR(w1[s]);
+            CVAE_V6_IN_AGPR(w2[s]);
+        }
+    }
     {   // this wave's slice of the front-end weight limbs -> LDS (the prepared image holds three planes per step)
         const float* src = p.afold3 + ((long)c * 4 + wave) * (KFW * 3 * 256);
         float* dst = wfl + wave * (KFW * LIMBS * 256);
@@ -196,7 +226,7 @@ __global__ __launch_bounds__(256, 1) void k_gru_steps_v6(Step6Params p) {
     const float bhn = p.bhn[j];
     const float cf0 = HOIST ? 0.f : p.cfold[j], cf1 = HOIST ? 0.f : p.cfold[H + j], cf2 = HOIST ? 0.f : p.cfold[2 * H + j];
     const int ntile = ti < nrt ? (nrt - ti + rts - 1) / rts : 0, ntask = p.T * ntile;
-    long long pc[4] = {0, 0, 0, 0};
+    long long pc[PROF ? 4 : 1] = {};      // PROF: cycle sums of the four phases of a task
     // front-end operands of task k: frame t's window = octet pieces [t*Cp/8, +9*Cp/8) of the tile (k = 8*piece + e), three
     // limb planes of 512 B per piece; 16-k step s of this wave = pieces 2*(wave*KFW + s) + kh
     f32x4 x4[2 * RF];                   // ring slot s % RF: limbs 0, 1 of 16-k step s
@@ -220,6 +250,21 @@ __global__ __launch_bounds__(256, 1) void k_gru_steps_v6(Step6Params p) {
             gq0 = g[0]; gq1 = g[H]; gq2 = g[2 * H];
         }
     };
+    // front-end weights, read from LDS one 16-k step AHEAD of the MFMAs that take them: two slots of LIMBS operands.  Step 0 is read
+    // at the end of the task before (FW0_EARLY) -- except at KFW 8, the encoder, where 12 more registers live across the reduction
+    // made the kernel spill: there it is read at the task's start.  Not in the two-limb and W2S forms: H = 2048 has no registers for
+    // the second slot, and the two-limb H = 64 form would lose a wave per SIMD.
+    constexpr bool FPRE = CVAE_V6_FPRE && !HOIST && LIMBS == 3 && !W2S && KPW <= 16;
+    constexpr bool FW0_EARLY = KFW <= 6;
+    f32x4 fw[FPRE ? 2 * LIMBS : 1];
+    auto load_fw = [&](int s) {
+#pragma unroll
+        for (int m = 0; m < LIMBS; ++m) fw[(s & 1) * LIMBS + m] = *(const f32x4*)(wfw + (s * LIMBS + m) * 256);
+    };
+    auto fw_op = [&](int s, int m) -> f32x4 {
+        if constexpr (FPRE) return fw[(s & 1) * LIMBS + m];
+        else return *(const f32x4*)(wfw + (s * LIMBS + m) * 256);
+    };
     float hkeep0 = 0.f, hkeep1 = 0.f;   // h_{t-1} of this thread's (row, unit), per tile for up to two tiles per block
     const int backoff = (p.exp >> 8) ? (p.exp >> 8) - 1 : p.backoff;     // x 64 cycles before the first poll (exp: measurement override)
     if constexpr (HOIST) {
@@ -229,22 +274,29 @@ __global__ __launch_bounds__(256, 1) void k_gru_steps_v6(Step6Params p) {
 #pragma unroll
         for (int s = 0; s < RF; ++s) load_x(s);
     }
+    if constexpr (FPRE && FW0_EARLY) { if (ntask > 0) load_fw(0); }
     unsigned fpre = 0u;                 // flags of the NEXT task, read at the end of the current one (several tiles per block)
     for (int k = 0; k < ntask; ++k) {
-        long long c0 = !W2S && p.prof ? cvae_clock() : 0;      // (no phase counters in the W2S form: no registers to spare)
+        long long c0 = 0;
+        if constexpr (PROF) c0 = cvae_clock();
         const int t = k / ntile, i = ti + (k % ntile) * rts;
         const unsigned row0 = (unsigned)(t * p.Bp + i * 32), tile0 = row0 >> 5;   // (Bp is a multiple of 32)
         f32x16 a0 = cvae_zero16(), a1 = cvae_zero16(), a2 = cvae_zero16(), a3 = cvae_zero16();   // S0 | S1 | S2 (two chains)
+        if constexpr (FPRE && !FW0_EARLY) load_fw(0);
 #pragma unroll
         for (int s = 0; s < KFW; ++s) {     // front-end: independent of h, issued before the poll
             const f32x4 l0 = x4[2 * (s % RF)], l1 = x4[2 * (s % RF) + 1];
-            const f32x4 b0 = *(const f32x4*)(wfw + (s * LIMBS + 0) * 256);
-            const f32x4 b1 = *(const f32x4*)(wfw + (s * LIMBS + 1) * 256);
+            if constexpr (FPRE) {      // in flight while this step's MFMAs issue (the fence keeps the reads in front of them)
+                if (s + 1 < KFW) load_fw(s + 1);
+                cvae_sched_fence();
+            }
+            const f32x4 b0 = fw_op(s, 0);
+            const f32x4 b1 = fw_op(s, 1);
             a0 = cvae_mfma_32x32x16_f16(l0, b0, a0);
             a1 = cvae_mfma_32x32x16_f16(l0, b1, a1);
             if constexpr (LIMBS == 3) {
                 const f32x4 l2 = cvae_bf8x8_to_h8(x2[s % RF]);
-                const f32x4 b2 = *(const f32x4*)(wfw + (s * LIMBS + 2) * 256);
+                const f32x4 b2 = fw_op(s, 2);
                 a2 = cvae_mfma_32x32x16_f16(l1, b1, a2);
                 if constexpr (W2S) a2 = cvae_mfma_32x32x16_f16(l0, b2, a2);      // (W2S: one S2 chain, 16 registers fewer)
                 else a3 = cvae_mfma_32x32x16_f16(l0, b2, a3);
@@ -256,7 +308,7 @@ __global__ __launch_bounds__(256, 1) void k_gru_steps_v6(Step6Params p) {
             cvae_sched_fence();
             if (s + RF < KFW) load_x(s + RF);          // refill the slot just consumed
         }
-        if (!W2S && p.prof) { const long long c1 = cvae_clock(); pc[0] += c1 - c0; c0 = c1; }
+        if constexpr (PROF) { const long long c1 = cvae_clock(); pc[0] += c1 - c0; c0 = c1; }
         const bool pre_ok = ntile > 1 && k > 0 && cvae_wave_all(fpre >= (unsigned)t);
         if (t > 0 && !pre_ok) {   // the octets (two per 16-unit chunk) of this wave's K share are published?
             unsigned spins = 0;
@@ -274,7 +326,7 @@ __global__ __launch_bounds__(256, 1) void k_gru_steps_v6(Step6Params p) {
             }
         }
         cvae_compiler_fence();                         // operand loads stay below the poll
-        if (!W2S && p.prof) { const long long c1 = cvae_clock(); pc[1] += c1 - c0; c0 = c1; }
+        if constexpr (PROF) { const long long c1 = cvae_clock(); pc[1] += c1 - c0; c0 = c1; }
         // The thread's gate inputs.  At frame 0 the feedback correction keeps 32 registers of loads in flight: the KPW = 32 variants
         // (H = 2048, 256 weight registers) have no room for them next to the operand ring and take them BEFORE it (they spilled
         // otherwise); the others issue them behind the ring's first loads, where their latency overlaps (3 % faster per launch).
@@ -366,7 +418,7 @@ __global__ __launch_bounds__(256, 1) void k_gru_steps_v6(Step6Params p) {
         for (int q = 0; q < 16; ++q)
             red[(wave * 32 + (q & 3) + 8 * (q >> 2) + 4 * kh) * RS + lc] =
                 LIMBS == 3 ? a0[q] + (a1[q] + (a2[q] + a3[q]) * S1) * S1 : a0[q] + (a1[q] + a2[q]) * S1;
-        if (!W2S && p.prof) { const long long c1 = cvae_clock(); pc[2] += c1 - c0; c0 = c1; }
+        if constexpr (PROF) { const long long c1 = cvae_clock(); pc[2] += c1 - c0; c0 = c1; }
         __syncthreads();
         {
             float hn_ = 0.0f;
@@ -418,10 +470,13 @@ __global__ __launch_bounds__(256, 1) void k_gru_steps_v6(Step6Params p) {
             if (tn > 0 && lane < 2 * KPW && 2 * s_lo + lane < NB)
                 fpre = cvae_atomic_load_agent(p.flags + (long)in_ * NB + 2 * s_lo + lane);
         }
-        if (!W2S && p.prof) { const long long c1 = cvae_clock(); pc[3] += c1 - c0; c0 = c1; }
+        if constexpr (FPRE && FW0_EARLY) { if (k + 1 < ntask) load_fw(0); }
+        if constexpr (PROF) { const long long c1 = cvae_clock(); pc[3] += c1 - c0; c0 = c1; }
     }
-    if (p.prof && tid == 64 * ((p.exp >> 2) & 3))    // measurement: exp bits 2-3 pick the reporting wave
-        for (int q = 0; q < 4; ++q) p.prof[(long)blockIdx.x * 4 + q] = pc[q];
+    if constexpr (PROF) {
+        if (p.prof && tid == 64 * ((p.exp >> 2) & 3))    // measurement: exp bits 2-3 pick the reporting wave
+            for (int q = 0; q < 4; ++q) p.prof[(long)blockIdx.x * 4 + q] = pc[q];
+    }
 }
 
 // ------------------------------------------------------------------------------------------------------------------------

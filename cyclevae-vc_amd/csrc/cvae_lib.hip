@@ -231,15 +231,19 @@ inline FoldScratch fold_scratch(const Dims& m) {
 // k_gru_steps_v6 (exact fp32 operands): H = 1024 (16 16-k steps per wave, three limbs), H = 2048 (32 steps: three limbs with the
 // third weight limb streamed from L2, or fp16 PAIRS, option v6_limbs_h2048 -- the hu2048 stress configuration, BASELINE configs[4])
 // and H = 64 (one step; every form, picked by the options v6_limbs_h64 / v6_w2s_h64: tests at a size the host-fiber emulator runs)
-struct V6Inst { int H, KFW, limbs; bool w2s; void (*fn)(Step6Params); };
+// (fn_prof: the same instance with the phase counters of cvae_step_timing compiled in -- what a CVAE_FLAG_STEP_TIMING pass launches; the
+// streamed-third-limb forms have none)
+struct V6Inst { int H, KFW, limbs; bool w2s; void (*fn)(Step6Params); void (*fn_prof)(Step6Params); };
+#define V6_PAIR(KPW, KFW, LIMBS) k_gru_steps_v6<KPW, KFW, LIMBS>, k_gru_steps_v6<KPW, KFW, LIMBS, false, true>      // resident weights: plain, profiling
+#define V6_W2S(KPW, KFW) k_gru_steps_v6<KPW, KFW, 3, true>, nullptr                                                  // streamed third limb
 const V6Inst g_v6_inst[] = {
-    {1024, 8, 3, false, k_gru_steps_v6<16, 8>},       {1024, 6, 3, false, k_gru_steps_v6<16, 6>},
-    {1024, 3, 3, false, k_gru_steps_v6<16, 3>},       {1024, 2, 3, false, k_gru_steps_v6<16, 2>},       // a one-layer front-end (dilation_size 1): encoder in_dim 54, decoder 34
-    {2048, 8, 3, true, k_gru_steps_v6<32, 8, 3, true>}, {2048, 11, 3, true, k_gru_steps_v6<32, 11, 3, true>},
-    {2048, 8, 2, false, k_gru_steps_v6<32, 8, 2>},    {2048, 11, 2, false, k_gru_steps_v6<32, 11, 2>},
-    {64, 3, 3, false, k_gru_steps_v6<1, 3>},          {64, 2, 3, false, k_gru_steps_v6<1, 2>},          {64, 1, 3, false, k_gru_steps_v6<1, 1>},
-    {64, 3, 3, true, k_gru_steps_v6<1, 3, 3, true>},  {64, 2, 3, true, k_gru_steps_v6<1, 2, 3, true>},  {64, 1, 3, true, k_gru_steps_v6<1, 1, 3, true>},
-    {64, 3, 2, false, k_gru_steps_v6<1, 3, 2>},       {64, 2, 2, false, k_gru_steps_v6<1, 2, 2>},       {64, 1, 2, false, k_gru_steps_v6<1, 1, 2>},
+    {1024, 8, 3, false, V6_PAIR(16, 8, 3)},  {1024, 6, 3, false, V6_PAIR(16, 6, 3)},
+    {1024, 3, 3, false, V6_PAIR(16, 3, 3)},  {1024, 2, 3, false, V6_PAIR(16, 2, 3)},       // a one-layer front-end (dilation_size 1): encoder in_dim 54, decoder 34
+    {2048, 8, 3, true, V6_W2S(32, 8)},       {2048, 11, 3, true, V6_W2S(32, 11)},
+    {2048, 8, 2, false, V6_PAIR(32, 8, 2)},  {2048, 11, 2, false, V6_PAIR(32, 11, 2)},
+    {64, 3, 3, false, V6_PAIR(1, 3, 3)},     {64, 2, 3, false, V6_PAIR(1, 2, 3)},          {64, 1, 3, false, V6_PAIR(1, 1, 3)},
+    {64, 3, 3, true, V6_W2S(1, 3)},          {64, 2, 3, true, V6_W2S(1, 2)},               {64, 1, 3, true, V6_W2S(1, 1)},
+    {64, 3, 2, false, V6_PAIR(1, 3, 2)},     {64, 2, 2, false, V6_PAIR(1, 2, 2)},          {64, 1, 2, false, V6_PAIR(1, 1, 2)},
 };
 // k_gru_steps_v6<KPW, 0> (form V6H): the same recurrence with NO front-end of its own, behind the front-end GEMM -- for front-ends
 // whose limb image cannot live in LDS.  The fused kernel keeps that image at 4 waves x KFW steps x 3 limbs x 1 KiB = 12 KiB per
@@ -247,10 +251,12 @@ const V6Inst g_v6_inst[] = {
 // have, KFW = 12 would take 166.5.  So V6H_MIN_KFW = 12, whatever H.  Keyed by H alone.
 const int V6H_MIN_KFW = 12;
 const V6Inst g_v6h_inst[] = {
-    {1024, 0, 3, false, k_gru_steps_v6<16, 0>},
-    {2048, 0, 3, true, k_gru_steps_v6<32, 0, 3, true>},      // (three limbs, third weight limb streamed; no pair form: option v6_limbs_h2048 = 2 leaves such a pass on the per-step path)
-    {64, 0, 3, false, k_gru_steps_v6<1, 0>},          {64, 0, 3, true, k_gru_steps_v6<1, 0, 3, true>},  {64, 0, 2, false, k_gru_steps_v6<1, 0, 2>},
+    {1024, 0, 3, false, V6_PAIR(16, 0, 3)},
+    {2048, 0, 3, true, V6_W2S(32, 0)},       // (three limbs, third weight limb streamed; no pair form: option v6_limbs_h2048 = 2 leaves such a pass on the per-step path)
+    {64, 0, 3, false, V6_PAIR(1, 0, 3)},     {64, 0, 3, true, V6_W2S(1, 0)},               {64, 0, 2, false, V6_PAIR(1, 0, 2)},
 };
+#undef V6_PAIR
+#undef V6_W2S
 // the 16-row fused kernels: k_gru_steps_v5 (fp16 pairs) and k_gru_steps_v4 (fp32 MFMA), always built together
 struct Fused16Inst { int H, KFW; void (*v5)(Step3Params); void (*v4)(Step3Params); };
 const Fused16Inst g_fused16_inst[] = {
@@ -427,20 +433,23 @@ EvalPlan plan_eval_pass(const Dims& m, int Brows, int T, int flags, int cus, boo
     } else if (exact && !unfit && !hoisted && i6 && Bp % 32 == 0 && cus >= m.H / 8 && (long)m.nch * mtot * 80 < (1L << 31)) {
         // exact fp32 operands as fp16 triples: 32-row tiles, 8-unit octets, H/8 blocks per tile, every block resident
         pn.form = CVAE_EVAL_V6;
-        pn.k6 = i6->fn;
+        pn.k6 = (flags & CVAE_FLAG_STEP_TIMING) && i6->fn_prof ? i6->fn_prof : i6->fn;
         pn.rts = row_tiles_per_block(cus, m.H / 8, Bp / 32);
         // One row tile per block (B <= 64 at hu1024): nothing can be published before the other blocks' front-ends are through, and
         // 256 waves polling through that window slow the publishes and operand loads they wait for.  The decoder's front-end is a
         // quarter shorter than the encoder's (KFW 6 vs 8), so its blocks arrive at the poll earlier: swept on MI355X
         // (tools/ab_eval_exp.sh, round 5), 64-cycle units -- decoder pass 421.7 (0) / 405.8 (4) / 397.1 (8) / 401.0 (12) / 409.0 us
-        // (16), encoder pass 412.3 / 411.0 / 416.6 / 423.9 / 434.5 us.
-        pn.backoff = opt(OPT_V6_BACKOFF) >= 0 ? (int)opt(OPT_V6_BACKOFF) : (m.H == 1024 ? (m.KFW <= 6 ? 8 : 2) : 0);
+        // (16), encoder pass 412.3 / 411.0 / 416.6 / 423.9 / 434.5 us.  Swept again once the front-end read its weights one step ahead
+        // (1.6K instead of 2.0K cycles at KFW 8: the blocks reach the poll earlier still; profiles/v6_hot_loop_notes.md): encoder pass
+        // 424.9 (0) / 416.4 (2) / 409.9 (4) / 400.3 (8) / 398.5 (10) / 399.9 (12) / 406.3 us (16), decoder pass 478.4 (0) / 419.9 (4) /
+        // 399.2 (8) / 388.9 (10) / 386.9 (12) / 384.5 us (16).  The one-layer front-ends (KFW 3, 2) keep the earlier decoder value: not swept.
+        pn.backoff = opt(OPT_V6_BACKOFF) >= 0 ? (int)opt(OPT_V6_BACKOFF) : (m.H == 1024 ? (m.KFW > 6 ? 10 : (m.KFW == 6 ? 16 : 8)) : 0);
     } else if (exact && !unfit && !hoisted && i6h && Bp % 32 == 0 && cus >= m.H / 8 && (long)m.nch * mtot * 80 < (1L << 31)) {
         // the same recurrence behind the front-end GEMM, for a front-end too wide for the LDS limb image (KFW >= 12: find_v6h).
         // HOISTED_FRONTEND keeps its meaning -- the 16-row kernel behind the GEMM (V2) -- so that the two can be compared.
         pn.form = CVAE_EVAL_V6H;
         i6 = i6h;
-        pn.k6 = i6h->fn;
+        pn.k6 = (flags & CVAE_FLAG_STEP_TIMING) && i6h->fn_prof ? i6h->fn_prof : i6h->fn;
         pn.rts = row_tiles_per_block(cus, m.H / 8, Bp / 32);
         pn.backoff = opt(OPT_V6_BACKOFF) >= 0 ? (int)opt(OPT_V6_BACKOFF) : 0;      // (nothing runs in front of the poll; not swept)
     } else if (persistent && !generic && (m.H == 1024 || m.H == 64) && cus >= m.nch && (long)m.nch * mtot * 64 < (1L << 31)) {
