@@ -78,6 +78,22 @@ class PassInput(C.Structure):
                 ("ctx_before", C.c_int32), ("ctx_after", C.c_int32), ("draw_frame0", C.c_int64), ("eps_draw_stride", C.c_int64)]
 
 
+class DtwProblem(C.Structure):
+    """cvae_dtw_problem: one alignment of cvae_dtw_batch (device addresses; aligned may be None)."""
+    _fields_ = [("org", _fp), ("trg", _fp), ("ld_org", C.c_int64), ("ld_trg", C.c_int64), ("T1", C.c_int32), ("T2", C.c_int32),
+                ("D", C.c_int32), ("mcd", C.c_int32), ("aligned", _fp), ("twf", _fp), ("frames", _fp), ("mean_out", _fp)]
+
+
+STAT_GV, STAT_MCD_SPC, STAT_MCD_L1, STAT_KL, STAT_GATHER64, STAT_LATDIST = range(6)      # cvae_stat_job.kind
+
+
+class StatJob(C.Structure):
+    """cvae_stat_job: one reduction of cvae_eval_stats."""
+    _fields_ = [("kind", C.c_int32), ("rows", C.c_int32), ("c0", C.c_int32), ("c1", C.c_int32), ("src_rows", C.c_int32),
+                ("pad_", C.c_int32), ("a", _fp), ("b", _fp), ("lda", C.c_int64), ("ldb", C.c_int64), ("idx", _fp), ("dst", _fp),
+                ("out_off", C.c_int64)]
+
+
 class CvaeError(RuntimeError):
     pass
 
@@ -250,6 +266,12 @@ class CvaeLib(object):
         L.cvae_dtw_work_bytes.argtypes = [C.c_int, C.c_int]
         L.cvae_dtw_org_to_trg.restype = C.c_int
         L.cvae_dtw_org_to_trg.argtypes = [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, C.c_size_t, _fp]
+        L.cvae_dtw_batch_work_bytes.restype = C.c_size_t
+        L.cvae_dtw_batch_work_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+        L.cvae_dtw_batch.restype = C.c_int
+        L.cvae_dtw_batch.argtypes = [C.POINTER(DtwProblem), C.c_int, _fp, C.c_size_t, _fp]
+        L.cvae_eval_stats.restype = C.c_int
+        L.cvae_eval_stats.argtypes = [_fp, C.c_int, _fp, _fp]
         L.cvae_step_timing.restype = C.c_int
         L.cvae_step_timing.argtypes = [C.POINTER(NetDesc), C.c_int, C.c_int, _fp, C.POINTER(C.c_double * 8), _fp]
         L.cvae_profile_collect.restype = C.c_int
@@ -549,6 +571,18 @@ class CvaeLib(object):
         self._check(self.lib.cvae_dtw_org_to_trg(org, trg, T1, T2, D, mcd, aligned, twf, frames, mean_out, work, work_bytes,
                                                  stream or None), "cvae_dtw_org_to_trg")
 
+    def dtw_batch_work_bytes(self, P, T1max, T2max):
+        return self.lib.cvae_dtw_batch_work_bytes(P, T1max, T2max)
+
+    def dtw_batch(self, problems, work, work_bytes, stream=0):
+        """problems: list of DtwProblem (a host list; the library copies it)."""
+        arr = (DtwProblem * len(problems))(*problems)
+        self._check(self.lib.cvae_dtw_batch(arr, len(problems), work, work_bytes, stream or None), "cvae_dtw_batch")
+
+    def eval_stats(self, jobs, n, out, stream=0):
+        """jobs: DEVICE-visible address of n StatJob descriptors."""
+        self._check(self.lib.cvae_eval_stats(jobs, n, out, stream or None), "cvae_eval_stats")
+
     def step_timing(self, d, B, T, ws, stream=0):
         out = (C.c_double * 8)()
         self._check(self.lib.cvae_step_timing(C.byref(d), B, T, ws, C.byref(out), stream or None), "cvae_step_timing")
@@ -626,5 +660,6 @@ EXPORTS = ("cvae_last_error_string", "cvae_abi_version", "cvae_ctx_create", "cva
            "cvae_sample_cat", "cvae_sample_cat_backward", "cvae_stage4_loss", "cvae_mcd_l1", "cvae_mcd_l1_backward", "cvae_kl_gauss",
            "cvae_kl_gauss_backward",
            "cvae_gv_postfilter", "cvae_mcd_aligned", "cvae_mc2e", "cvae_dtw_work_bytes", "cvae_dtw_org_to_trg",
+           "cvae_dtw_batch_work_bytes", "cvae_dtw_batch", "cvae_eval_stats",
            "cvae_net_prepared_bytes_deep", "cvae_net_prepare_scratch_bytes_deep", "cvae_net_prepare_deep", "cvae_pass_workspace_bytes_deep",
            "cvae_plan_pass", "cvae_plan_pass_deep", "cvae_gru_rnn_forward_deep", "cvae_net_prepared_in_range")

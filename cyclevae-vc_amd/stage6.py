@@ -7,6 +7,7 @@ through `cvae_gv_postfilter` / `cvae_mcd_aligned` of libcyclevae_hip.so.  HIP de
 """
 import torch
 
+import _cabi
 import gru_vae
 
 
@@ -93,6 +94,36 @@ def dtw_org_to_trg(org, trg, mcd=-1):
     lib.dtw_org_to_trg(a.data_ptr(), b.data_ptr(), T1, T2, D, int(mcd), aligned.data_ptr(), twf.data_ptr(), frames.data_ptr(),
                        mean.data_ptr(), work.data_ptr(), nb, gru_vae._stream())
     return aligned, twf, mean[0], frames
+
+
+def dtw_many(problems):
+    """dtw_org_to_trg for a LIST of (org, trg, mcd) in one call of cvae_dtw_batch: one block per alignment, all of them in flight at
+    once, a launch count that does not depend on the length of the list (validation.ValidationPass aligns twelve pairs per
+    utterance this way).  Returns one (aligned_org, twf, mean local cost, per-frame costs) per problem, bit for bit what
+    dtw_org_to_trg returns for it.  PARITY UNPINNED, as there."""
+    if not problems:
+        return []
+    lib = gru_vae._lib()
+    gru_vae._need_cuda(problems[0][0], "dtw_many(org)")
+    dev = problems[0][0].device
+    keep, probs, outs = [], [], []
+    for org, trg, mcd in problems:
+        a, b = org.to(torch.float64).contiguous(), trg.to(torch.float64).contiguous()
+        if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1] or a.shape[0] < 1 or b.shape[0] < 1:
+            raise ValueError("dtw_many needs [T1, D] and [T2, D] with T1, T2 >= 1, got %s and %s" % (tuple(a.shape), tuple(b.shape)))
+        T1, T2, D = a.shape[0], b.shape[0], a.shape[1]
+        aligned = torch.empty(T2, D, dtype=torch.float64, device=dev)
+        twf = torch.empty(T2, dtype=torch.int64, device=dev)
+        frames = torch.empty(T2, dtype=torch.float64, device=dev)
+        mean = torch.empty(1, dtype=torch.float64, device=dev)
+        keep += [a, b]
+        probs.append(_cabi.DtwProblem(a.data_ptr(), b.data_ptr(), D, D, T1, T2, D, int(mcd), aligned.data_ptr(), twf.data_ptr(),
+                                      frames.data_ptr(), mean.data_ptr()))
+        outs.append((aligned, twf, mean[0], frames))
+    nb = lib.dtw_batch_work_bytes(len(probs), max(p.T1 for p in probs), max(p.T2 for p in probs))
+    work = torch.empty(nb, dtype=torch.uint8, device=dev)
+    lib.dtw_batch(probs, work.data_ptr(), nb, gru_vae._stream())
+    return outs
 
 
 def _encode_pairs(model_encoder, pairs, y_in_pp, lat_dim):

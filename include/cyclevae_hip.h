@@ -213,6 +213,9 @@ int cvae_set_draw_parts(cvae_ctx* ctx, int32_t parts);
  *                                raises CVAE_STATUS_RANGE.  65504 (default, the largest finite half): the first limb overflows and the
  *                                result is unusable.  2048: the bound below which the (fp16, fp16, bf8) triple is EXACT; in between
  *                                the clamped bf8 limb costs at most 2^-23 relative.  Clamped to 1 .. 65504.
+ *   "dtw_batch_cost"    1        cvae_dtw_batch: 1 = local costs written first by one grid-wide kernel over all problems of a chunk (a
+ *                                T1 x T2 f64 slab per problem), 0 = computed inside the path kernel, cell by cell (one byte of work memory
+ *                                per cell).  Same bits either way; profiles/validation_notes.md holds the measurement.
  *   "masks_on_side"     1        train-mode forward with a side stream set: the dropout mask of the recurrence's feedback operand is
  *                                drawn on the side stream, beside the prologue and the front-end GEMMs (0: on the launch stream)
  */
@@ -617,6 +620,70 @@ int cvae_mcd_aligned(cvae_ctx* ctx, const float* a, long lda, const float* b, lo
 size_t cvae_dtw_work_bytes(cvae_ctx* ctx, int T1, int T2);
 int cvae_dtw_org_to_trg(cvae_ctx* ctx, const double* org, const double* trg, int T1, int T2, int D, int mcd, double* aligned, long long* twf,
                         double* frames, double* mean_out, void* work, size_t work_bytes, void* stream);
+
+/*
+ * Batched DTW (the per-epoch validation pass, train_gru_cyclevae_gauss_batch.py:895-951: twelve alignments per utterance pair).
+ * P problems of cvae_dtw_org_to_trg in ONE call whose launch count does not depend on P: per chunk one copy of the problem
+ * list into the head of `work`, (option dtw_batch_cost = 1) one grid-wide local-cost kernel, and one path kernel with ONE BLOCK
+ * PER PROBLEM.  A block keeps the two previous anti-diagonals of the accumulated cost in LDS (three rotating rows of T1 doubles;
+ * T1 > CVAE_DTW_LDS_ROWS: in `work`), stores one back-pointer byte per cell, follows the bytes back from (T1-1, T2-1), and warps.
+ * Blocks are independent ordinary kernels: no cooperative launch, no flags between blocks.
+ * Semantics and bits are those of cvae_dtw_org_to_trg (oracle/cyclevae_oracle.py::dtw_org_to_trg; PARITY UNPINNED as there): steps
+ * (i-1,j-1), (i-1,j), (i,j-1), unit weights, strict "<" in that order; target frame j takes the path's org frame of smallest local
+ * cost, "<=" walking backwards; mean_out = mean of those costs.  The local cost is k_dtw_cost's expression in k_dtw_cost's
+ * summation order.
+ * probs: HOST array (read before the call returns).  org [T1][ld_org], trg [T2][ld_trg] f64 device; aligned NULL or [T2][D];
+ * twf [T2]; frames [T2]; mean_out [1].  Outputs of different problems must not overlap; inputs may be shared.
+ * work: cvae_dtw_batch_work_bytes(P, max T1, max T2) bytes of device memory, which is the need of all P problems at once or
+ * CVAE_DTW_BATCH_WORK_CAP, whichever is smaller (never less than ONE problem needs): cvae_dtw_batch splits P into consecutive
+ * chunks that fit `work_bytes` and runs them one behind the other on `stream`.
+ */
+#define CVAE_DTW_BATCH_WORK_CAP ((size_t)1 << 30)
+#define CVAE_DTW_LDS_ROWS 2048
+typedef struct cvae_dtw_problem {
+    const double* org;
+    const double* trg;
+    int64_t ld_org, ld_trg;      /* row strides in doubles, >= D */
+    int32_t T1, T2, D;
+    int32_t mcd;                 /* non-zero: mel-cd local cost [dB]; 0: cosine distance */
+    double* aligned;             /* NULL: not wanted */
+    long long* twf;
+    double* frames;
+    double* mean_out;
+} cvae_dtw_problem;
+size_t cvae_dtw_batch_work_bytes(cvae_ctx* ctx, int P, int T1max, int T2max);
+int cvae_dtw_batch(cvae_ctx* ctx, const cvae_dtw_problem* probs, int P, void* work, size_t work_bytes, void* stream);
+
+/*
+ * Batched utterance statistics of the validation pass: ONE launch, one block per job, f64 arithmetic on fp32 inputs, every
+ * reduction a fixed-order tree (the result does not depend on the grid).  jobs: n descriptors in DEVICE-visible memory (the
+ * caller uploads the list it built on the host; bad descriptors cannot be refused from the host side -- a row index outside
+ * 0 .. src_rows-1 makes the job's results NaN instead of reading there).  Results of kinds other than GATHER64 go to
+ * out[out_off ...].
+ *   CVAE_STAT_GV        out[c - c0] = population variance (two-pass) over rows 0 .. rows-1 of column c of a, c0 <= c < c1
+ *                       (np.var(traj[:flen, 1:], axis=0) with c0 = 1, c1 = D: train...:888-893, there in float32)
+ *   CVAE_STAT_MCD_SPC   out[0] = mean over k < rows of (10/ln10) sqrt(2 sum_{c0 <= c < c1} (a[idx[k]][c] - b[idx[k]][c])^2)
+ *                       (dtw_c.calc_mcd on the speech frames, :932-948; a and b are given at their first compared column's origin)
+ *   CVAE_STAT_MCD_L1    out[0] = mean over t < rows of (10/ln10) sqrt2 sum_{c < c1} |a[t][c] - b[t][c]|     (criterion_mcd(L2=False,
+ *                       GV=False)'s mean, :1006-1013; cvae_mcd_l1's second output, here in f64)
+ *   CVAE_STAT_KL        out[0] = mean over t < rows of 0.5 sum_{l < c1} (exp(s) + mu^2 - s - 1), a[t] = [mu (c1) | s (c1)]
+ *                       (loss_vae, :1015-1019; cvae_kl_gauss in f64)
+ *   CVAE_STAT_GATHER64  dst[k][c - c0] = (double)a[idx[k]][c], k < rows, c0 <= c < c1: the packed f64 DTW operands of :895-951
+ *   CVAE_STAT_LATDIST   out[0] = mean_c sqrt(mean_t (a[t][c] - b[t][c])^2), a and b F64 [rows][lda / ldb], c < c1      (:898)
+ */
+enum { CVAE_STAT_GV = 0, CVAE_STAT_MCD_SPC = 1, CVAE_STAT_MCD_L1 = 2, CVAE_STAT_KL = 3, CVAE_STAT_GATHER64 = 4, CVAE_STAT_LATDIST = 5 };
+typedef struct cvae_stat_job {
+    int32_t kind, rows;          /* rows: flen, n_spc, or the rows of the aligned pair */
+    int32_t c0, c1;
+    int32_t src_rows, pad_;      /* rows of a (and b) that idx may address */
+    const void* a;
+    const void* b;
+    int64_t lda, ldb;            /* row strides in elements */
+    const int64_t* idx;          /* MCD_SPC, GATHER64: rows int64 frame indices */
+    double* dst;                 /* GATHER64: [rows][c1 - c0] */
+    int64_t out_off;
+} cvae_stat_job;
+int cvae_eval_stats(cvae_ctx* ctx, const cvae_stat_job* jobs, int n, double* out, void* stream);
 
 /* Copy status words (int32[4]) of a workspace to the host; synchronises `stream`.  status[0]!=0 = barrier timeout;
  * status[3] == CVAE_STATUS_RANGE: the latest call on this workspace met an operand outside the limb window (no sink set). */
