@@ -85,6 +85,7 @@ class DtwProblem(C.Structure):
 
 
 STAT_GV, STAT_MCD_SPC, STAT_MCD_L1, STAT_KL, STAT_GATHER64, STAT_LATDIST = range(6)      # cvae_stat_job.kind
+STAT_MEANSTD64, STAT_MCD64 = 6, 7       # stage 5: (np.mean, np.std) of an f64 vector / of the frame-wise mel-cd of two f64 matrices
 
 
 class StatJob(C.Structure):
@@ -92,6 +93,11 @@ class StatJob(C.Structure):
     _fields_ = [("kind", C.c_int32), ("rows", C.c_int32), ("c0", C.c_int32), ("c1", C.c_int32), ("src_rows", C.c_int32),
                 ("pad_", C.c_int32), ("a", _fp), ("b", _fp), ("lda", C.c_int64), ("ldb", C.c_int64), ("idx", _fp), ("dst", _fp),
                 ("out_off", C.c_int64)]
+
+
+class LatMeanJob(C.Structure):
+    """cvae_latmean_job: one latent mean of cvae_latent_mean (device addresses; eps may be None)."""
+    _fields_ = [("lat", _fp), ("eps", _fp), ("draw_id", C.c_uint64), ("frames", C.c_int32), ("pad_", C.c_int32), ("out", _fp)]
 
 
 class CvaeError(RuntimeError):
@@ -272,6 +278,8 @@ class CvaeLib(object):
         L.cvae_dtw_batch.argtypes = [C.POINTER(DtwProblem), C.c_int, _fp, C.c_size_t, _fp]
         L.cvae_eval_stats.restype = C.c_int
         L.cvae_eval_stats.argtypes = [_fp, C.c_int, _fp, _fp]
+        L.cvae_latent_mean.restype = C.c_int
+        L.cvae_latent_mean.argtypes = [C.POINTER(LatMeanJob), C.c_int, C.c_int, C.c_int, C.c_uint64, _fp]
         L.cvae_step_timing.restype = C.c_int
         L.cvae_step_timing.argtypes = [C.POINTER(NetDesc), C.c_int, C.c_int, _fp, C.POINTER(C.c_double * 8), _fp]
         L.cvae_profile_collect.restype = C.c_int
@@ -583,6 +591,11 @@ class CvaeLib(object):
         """jobs: DEVICE-visible address of n StatJob descriptors."""
         self._check(self.lib.cvae_eval_stats(jobs, n, out, stream or None), "cvae_eval_stats")
 
+    def latent_mean(self, jobs, lat_dim, n_draws, seed=0, stream=0):
+        """jobs: list of LatMeanJob (a host list; the library reads it before it returns)."""
+        arr = (LatMeanJob * max(1, len(jobs)))(*jobs)
+        self._check(self.lib.cvae_latent_mean(arr, len(jobs), lat_dim, n_draws, seed, stream or None), "cvae_latent_mean")
+
     def step_timing(self, d, B, T, ws, stream=0):
         out = (C.c_double * 8)()
         self._check(self.lib.cvae_step_timing(C.byref(d), B, T, ws, C.byref(out), stream or None), "cvae_step_timing")
@@ -660,6 +673,6 @@ EXPORTS = ("cvae_last_error_string", "cvae_abi_version", "cvae_ctx_create", "cva
            "cvae_sample_cat", "cvae_sample_cat_backward", "cvae_stage4_loss", "cvae_mcd_l1", "cvae_mcd_l1_backward", "cvae_kl_gauss",
            "cvae_kl_gauss_backward",
            "cvae_gv_postfilter", "cvae_mcd_aligned", "cvae_mc2e", "cvae_dtw_work_bytes", "cvae_dtw_org_to_trg",
-           "cvae_dtw_batch_work_bytes", "cvae_dtw_batch", "cvae_eval_stats",
+           "cvae_dtw_batch_work_bytes", "cvae_dtw_batch", "cvae_eval_stats", "cvae_latent_mean",
            "cvae_net_prepared_bytes_deep", "cvae_net_prepare_scratch_bytes_deep", "cvae_net_prepare_deep", "cvae_pass_workspace_bytes_deep",
            "cvae_plan_pass", "cvae_plan_pass_deep", "cvae_gru_rnn_forward_deep", "cvae_net_prepared_in_range")

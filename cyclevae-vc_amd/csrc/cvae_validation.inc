@@ -167,6 +167,13 @@ __device__ __forceinline__ double block_sum256(double v, double* red) {
     return red[0];
 }
 
+// sum over columns c0 .. c1-1 of (x - y)^2, in column order
+__device__ __forceinline__ double sqdist64(const double* x, const double* y, int c0, int c1) {
+    double s = 0.0;
+    for (int c = c0; c < c1; ++c) s += (x[c] - y[c]) * (x[c] - y[c]);
+    return s;
+}
+
 __global__ __launch_bounds__(256) void k_eval_stats(const cvae_stat_job* jobs, double* out) {
     double* red = (double*)CVAE_SMEM;     // [256]
     const cvae_stat_job& jb = jobs[blockIdx.x];
@@ -254,6 +261,28 @@ __global__ __launch_bounds__(256) void k_eval_stats(const cvae_stat_job* jobs, d
         }
         const double tot = block_sum256(acc, red);
         if (tid == 0) o[0] = tot / (double)c1;
+    } else if (kind == CVAE_STAT_MEANSTD64 || kind == CVAE_STAT_MCD64) {
+        // mean and population standard deviation of a per-frame array (stage 5): np.std's two passes
+        const double* a = (const double*)jb.a;
+        const double* b = (const double*)jb.b;
+        const bool mcd = kind == CVAE_STAT_MCD64;
+        if (rows < 1 || rows > jb.src_rows) {      // (the whole block: nobody reaches a barrier)
+            if (tid == 0) o[0] = o[1] = NaN;
+            return;
+        }
+        double s = 0.0;
+        for (int t = tid; t < rows; t += 256) s += mcd ? K * sqrt(2.0 * sqdist64(a + t * lda, b + t * ldb, c0, c1)) : a[t * lda];
+        const double m = block_sum256(s, red) / (double)rows;
+        double q = 0.0;
+        for (int t = tid; t < rows; t += 256) {
+            const double d = (mcd ? K * sqrt(2.0 * sqdist64(a + t * lda, b + t * ldb, c0, c1)) : a[t * lda]) - m;
+            q += d * d;
+        }
+        const double v = block_sum256(q, red) / (double)rows;
+        if (tid == 0) {
+            o[0] = m;
+            o[1] = sqrt(v);
+        }
     } else if (tid == 0) {
         o[0] = NaN;
     }

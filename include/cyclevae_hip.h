@@ -684,6 +684,34 @@ typedef struct cvae_stat_job {
     int64_t out_off;
 } cvae_stat_job;
 int cvae_eval_stats(cvae_ctx* ctx, const cvae_stat_job* jobs, int n, double* out, void* stream);
+/*
+ * Two further job kinds (stage 5, calc_cvgv_gru-cyclevae_gauss.py:210-249), F64 operands; out[0] = np.mean, out[1] = np.std
+ * (population, two-pass) of a per-frame array.  src_rows: the rows the operands hold -- rows outside 1 .. src_rows give NaN, NaN
+ * instead of a read behind them.
+ *   CVAE_STAT_MEANSTD64 the array is a[t * lda], t < rows: the per-frame costs a DTW problem leaves in `frames` (lda = 1)   (:212-215)
+ *   CVAE_STAT_MCD64     the array is (10/ln10) sqrt(2 sum_{c0 <= c < c1} (a[t][c] - b[t][c])^2), t < rows, a and b [rows][lda / ldb]
+ *                       given at column 0: dtw_c.calc_mcd's frame array as oracle.mcd_aligned defines it (PARITY UNPINNED)   (:224-229)
+ */
+enum { CVAE_STAT_MEANSTD64 = 6, CVAE_STAT_MCD64 = 7 };
+
+/*
+ * The n_draws-draw latent mean of stage 5 / 6 as an array of its own (calc_cvgv_gru-cyclevae_gauss.py:180-184: lat_feat, which the
+ * script feeds to the decoder AND aligns with DTW; inside the pass prologue the same mean is never written out).  One launch per
+ * 32 jobs of a HOST list (read before the call returns):
+ *   out[t][l] = lat[t][l] + exp(lat[t][L + l] / 2) * (sum_{k < n_draws} eps_k[t][l]) / n_draws,   t < frames, l < L = lat_dim
+ * lat [frames][2L], out [frames][L] fp32 device; eps NULL, or [n_draws][frames][L] fp32 device.  eps NULL: draw k of frame t is keyed
+ * (seed, draw_id + k, t, l) through cvae_randn4, as the pass prologue keys the draws of a single-row cell (the data-parallel draw
+ * origin does not enter).  The draws are added in the order k = 0, 1, ... by one thread per (frame, four dims), with either source
+ * of eps: the result does not depend on the grid.  Any lat_dim >= 1 (not only multiples of 4), n_draws >= 1, frames >= 1.
+ */
+typedef struct cvae_latmean_job {
+    const float* lat;
+    const float* eps;
+    uint64_t draw_id;
+    int32_t frames, pad_;
+    float* out;
+} cvae_latmean_job;
+int cvae_latent_mean(cvae_ctx* ctx, const cvae_latmean_job* jobs, int n_jobs, int lat_dim, int n_draws, uint64_t seed, void* stream);
 
 /* Copy status words (int32[4]) of a workspace to the host; synchronises `stream`.  status[0]!=0 = barrier timeout;
  * status[3] == CVAE_STATUS_RANGE: the latest call on this workspace met an operand outside the limb window (no sink set). */
