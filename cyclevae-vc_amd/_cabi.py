@@ -100,6 +100,22 @@ class LatMeanJob(C.Structure):
     _fields_ = [("lat", _fp), ("eps", _fp), ("draw_id", C.c_uint64), ("frames", C.c_int32), ("pad_", C.c_int32), ("out", _fp)]
 
 
+class Mc2eJob(C.Structure):
+    """cvae_mc2e_job: one matrix of cvae_mc2e_batch (device addresses)."""
+    _fields_ = [("mc", _fp), ("is_f64", C.c_int32), ("T", C.c_int32), ("D", C.c_int32), ("pad_", C.c_int32), ("ld", C.c_int64), ("e_out", _fp)]
+
+
+DEC_MODPOW, DEC_GATHER = 0, 1       # cvae_decode_job.kind
+
+
+class DecodeJob(C.Structure):
+    """cvae_decode_job: one mod_pow / GV post-filter / difference, or one f64 gather, of cvae_decode_jobs (device addresses)."""
+    _fields_ = [("kind", C.c_int32), ("T", C.c_int32), ("D", C.c_int32), ("c_f64", C.c_int32), ("ref_f64", C.c_int32),
+                ("src_rows", C.c_int32), ("c0", C.c_int32), ("c1", C.c_int32), ("c", _fp), ("ldc", C.c_int64), ("e_ref", _fp), ("e_c", _fp),
+                ("gv", _fp), ("cvgv", _fp), ("x", _fp), ("g", _fp), ("var", _fp), ("dpow", _fp), ("ref", _fp), ("ldref", C.c_int64),
+                ("diff", _fp), ("idx", _fp)]
+
+
 class CvaeError(RuntimeError):
     pass
 
@@ -280,6 +296,12 @@ class CvaeLib(object):
         L.cvae_eval_stats.argtypes = [_fp, C.c_int, _fp, _fp]
         L.cvae_latent_mean.restype = C.c_int
         L.cvae_latent_mean.argtypes = [C.POINTER(LatMeanJob), C.c_int, C.c_int, C.c_int, C.c_uint64, _fp]
+        L.cvae_mc2e_batch_work_bytes.restype = C.c_size_t
+        L.cvae_mc2e_batch_work_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+        L.cvae_mc2e_batch.restype = C.c_int
+        L.cvae_mc2e_batch.argtypes = [C.POINTER(Mc2eJob), C.c_int, C.c_double, C.c_int, _fp, C.c_size_t, _fp]
+        L.cvae_decode_jobs.restype = C.c_int
+        L.cvae_decode_jobs.argtypes = [C.POINTER(DecodeJob), C.c_int, _fp, C.c_size_t, _fp]
         L.cvae_step_timing.restype = C.c_int
         L.cvae_step_timing.argtypes = [C.POINTER(NetDesc), C.c_int, C.c_int, _fp, C.POINTER(C.c_double * 8), _fp]
         L.cvae_profile_collect.restype = C.c_int
@@ -596,6 +618,19 @@ class CvaeLib(object):
         arr = (LatMeanJob * max(1, len(jobs)))(*jobs)
         self._check(self.lib.cvae_latent_mean(arr, len(jobs), lat_dim, n_draws, seed, stream or None), "cvae_latent_mean")
 
+    def mc2e_batch_work_bytes(self, n_jobs, Dmax, irlen):
+        return self.lib.cvae_mc2e_batch_work_bytes(n_jobs, Dmax, irlen)
+
+    def mc2e_batch(self, jobs, alpha, irlen, work, work_bytes, stream=0):
+        """jobs: list of Mc2eJob (a host list; the library copies it)."""
+        arr = (Mc2eJob * max(1, len(jobs)))(*jobs)
+        self._check(self.lib.cvae_mc2e_batch(arr, len(jobs), alpha, irlen, work, work_bytes, stream or None), "cvae_mc2e_batch")
+
+    def decode_jobs(self, jobs, work, work_bytes, stream=0):
+        """jobs: list of DecodeJob (a host list; the library copies it into `work`)."""
+        arr = (DecodeJob * max(1, len(jobs)))(*jobs)
+        self._check(self.lib.cvae_decode_jobs(arr, len(jobs), work, work_bytes, stream or None), "cvae_decode_jobs")
+
     def step_timing(self, d, B, T, ws, stream=0):
         out = (C.c_double * 8)()
         self._check(self.lib.cvae_step_timing(C.byref(d), B, T, ws, C.byref(out), stream or None), "cvae_step_timing")
@@ -674,5 +709,6 @@ EXPORTS = ("cvae_last_error_string", "cvae_abi_version", "cvae_ctx_create", "cva
            "cvae_kl_gauss_backward",
            "cvae_gv_postfilter", "cvae_mcd_aligned", "cvae_mc2e", "cvae_dtw_work_bytes", "cvae_dtw_org_to_trg",
            "cvae_dtw_batch_work_bytes", "cvae_dtw_batch", "cvae_eval_stats", "cvae_latent_mean",
+           "cvae_mc2e_batch_work_bytes", "cvae_mc2e_batch", "cvae_decode_jobs",
            "cvae_net_prepared_bytes_deep", "cvae_net_prepare_scratch_bytes_deep", "cvae_net_prepare_deep", "cvae_pass_workspace_bytes_deep",
            "cvae_plan_pass", "cvae_plan_pass_deep", "cvae_gru_rnn_forward_deep", "cvae_net_prepared_in_range")

@@ -713,6 +713,61 @@ typedef struct cvae_latmean_job {
 } cvae_latmean_job;
 int cvae_latent_mean(cvae_ctx* ctx, const cvae_latmean_job* jobs, int n_jobs, int lat_dim, int n_draws, uint64_t seed, void* stream);
 
+/*
+ * Stage 6 in batched form (decode_gru-cyclevae_gauss.py:328-475: per utterance pair six mod_pow, three GV post-filters, two
+ * differential cepstra).  Both entry points take a HOST job list (read before the call returns) and issue a number of launches that
+ * does not depend on the list's length.
+ *
+ * cvae_mc2e_batch: cvae_mc2e's energies (same semantics, oracle.mc2e) for every frame of every job at one (alpha, irlen):
+ * mc [T][ld] float32 (is_f64 = 0) or float64, D >= 2 coefficients, e_out [T].  One copy of the list, one kernel that builds the
+ * freqt map of the call (it depends on alpha, irlen and the largest D only), one kernel with a 64-lane block per frame.  irlen 2 ..
+ * 4000 with (2 irlen + max D + 64) doubles of LDS <= 64 KiB.  work: cvae_mc2e_batch_work_bytes(n_jobs, max D, irlen) bytes of device
+ * memory (0: bad arguments).  A frame's energy does not depend on the other frames or jobs of the call.
+ */
+typedef struct cvae_mc2e_job {
+    const void* mc;
+    int32_t is_f64, T, D, pad_;
+    int64_t ld;                  /* row stride in elements, >= D */
+    double* e_out;
+} cvae_mc2e_job;
+size_t cvae_mc2e_batch_work_bytes(cvae_ctx* ctx, int n_jobs, int Dmax, int irlen);
+int cvae_mc2e_batch(cvae_ctx* ctx, const cvae_mc2e_job* jobs, int n_jobs, double alpha, int irlen, void* work, size_t work_bytes,
+                    void* stream);
+/*
+ * cvae_decode_jobs: one launch, one block per job, f64, fixed-order reductions.
+ *   CVAE_DEC_MODPOW  c [T][ldc] (float32, or float64 with c_f64 = 1) -> x [T][D] f64:
+ *                      x[t][0] = c[t][0] + log(e_ref[t] / e_c[t]) / 2   (mod_pow, feature_extract_vc.py:131-138; e_ref or e_c NULL: + 0)
+ *                      x[t][d] = c[t][d], d >= 1;        dpow NULL or [T]: the correction that was added
+ *                    x may be c itself (c_f64 = 1, ldc = D): the in-place correction of decode...:432.
+ *                    diff NULL or [T][D]: x - ref, ref [T][ldref] float32 / float64 (ref_f64)                        (:470, :474)
+ *                    gv NULL or [D-1], then cvgv [D-1], g [T][D], var [D-1]: the post-filter of :419-422 applied to x,
+ *                      g[t][0] = x[t][0];  g[t][d] = sqrt(gv[d-1] / cvgv[d-1]) (x[t][d] - mean_t x[.][d]) + mean_t x[.][d]
+ *                      var = np.var(g[:, 1:], axis=0) (two-pass)
+ *   CVAE_DEC_GATHER  x[k][c - c0] = c[idx[k]][c], k < T, c0 <= c < c1, c float32 / float64; an index outside 0 .. src_rows-1 gives
+ *                    a NaN row instead of a read there (cvae_eval_stats' GATHER64 for f64 sources)
+ * work: n_jobs * sizeof(cvae_decode_job) bytes of device memory.  Outputs of different jobs must not overlap.
+ */
+enum { CVAE_DEC_MODPOW = 0, CVAE_DEC_GATHER = 1 };
+typedef struct cvae_decode_job {
+    int32_t kind, T, D, c_f64;
+    int32_t ref_f64, src_rows, c0, c1;
+    const void* c;
+    int64_t ldc;
+    const double* e_ref;
+    const double* e_c;
+    const double* gv;
+    const double* cvgv;
+    double* x;
+    double* g;
+    double* var;
+    double* dpow;
+    const void* ref;
+    int64_t ldref;
+    double* diff;
+    const int64_t* idx;
+} cvae_decode_job;
+int cvae_decode_jobs(cvae_ctx* ctx, const cvae_decode_job* jobs, int n_jobs, void* work, size_t work_bytes, void* stream);
+
 /* Copy status words (int32[4]) of a workspace to the host; synchronises `stream`.  status[0]!=0 = barrier timeout;
  * status[3] == CVAE_STATUS_RANGE: the latest call on this workspace met an operand outside the limb window (no sink set). */
 int cvae_workspace_status(cvae_ctx* ctx, const void* workspace, int32_t status_out[4], void* stream);
