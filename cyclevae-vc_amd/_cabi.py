@@ -105,6 +105,18 @@ class Mc2eJob(C.Structure):
     _fields_ = [("mc", _fp), ("is_f64", C.c_int32), ("T", C.c_int32), ("D", C.c_int32), ("pad_", C.c_int32), ("ld", C.c_int64), ("e_out", _fp)]
 
 
+class GemmCase(C.Structure):
+    """cvae_gemm_case: one training GEMM / column sum for cvae_selftest_gemm (device addresses; include/cyclevae_hip.h)."""
+    _fields_ = [("kind", C.c_int32), ("accumulate", C.c_int32), ("use_split", C.c_int32), ("M", C.c_int32), ("N", C.c_int32),
+                ("K", C.c_int32), ("seglen", C.c_int32), ("mask_B", C.c_int32), ("mask_Bp", C.c_int32), ("mask_T", C.c_int32),
+                ("lda", C.c_int64), ("ldb", C.c_int64), ("ldc", C.c_int64), ("segstride", C.c_int64),
+                ("a_lo", C.c_int64), ("a_hi", C.c_int64), ("b_lo", C.c_int64), ("b_hi", C.c_int64), ("c_hi", C.c_int64),
+                ("A", _fp), ("B", _fp), ("bias", _fp), ("mask", _fp), ("C", _fp)]
+
+
+GEMM_NT, GEMM_TN, GEMM_KS, GEMM_COLSUM = 0, 1, 2, 3      # cvae_gemm_case.kind
+SELFTEST_GEMM_CNT = 4096                                 # arrival counters at the end of cvae_selftest_gemm's work space
+
 DEC_MODPOW, DEC_GATHER = 0, 1       # cvae_decode_job.kind
 
 
@@ -324,6 +336,10 @@ class CvaeLib(object):
         L.cvae_selftest_limbs.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         L.cvae_selftest_occupy.restype = C.c_int
         L.cvae_selftest_occupy.argtypes = [C.c_int, C.c_size_t, C.c_int64, C.c_void_p]
+        L.cvae_selftest_gemm_work_bytes.restype = C.c_size_t
+        L.cvae_selftest_gemm_work_bytes.argtypes = []
+        L.cvae_selftest_gemm.restype = C.c_int
+        L.cvae_selftest_gemm.argtypes = [C.POINTER(GemmCase), _fp, C.c_size_t, C.POINTER(C.c_int32 * 4), _fp]
         L.cvae_set_draw_parts.restype = C.c_int
         L.cvae_set_draw_parts.argtypes = [C.c_int32]
         L.cvae_set_option.restype = C.c_int
@@ -651,6 +667,15 @@ class CvaeLib(object):
     def selftest_occupy(self, blocks, lds_bytes, cycles, stream=None):
         self._check(self.lib.cvae_selftest_occupy(blocks, lds_bytes, cycles, stream), "cvae_selftest_occupy")
 
+    def selftest_gemm_work_bytes(self):
+        return self.lib.cvae_selftest_gemm_work_bytes()
+
+    def selftest_gemm(self, case, work, work_bytes, stream=None):
+        """Runs one GemmCase through the training GEMM wrappers; returns [tiled, TM, TN, slices] of what was launched."""
+        ran = (C.c_int32 * 4)()
+        self._check(self.lib.cvae_selftest_gemm(C.byref(case), work or None, work_bytes, C.byref(ran), stream or None), "cvae_selftest_gemm")
+        return list(ran)
+
     def set_side_stream(self, stream):
         self._check(self.lib.cvae_set_side_stream(stream), "cvae_set_side_stream")
 
@@ -700,7 +725,7 @@ class CvaeLib(object):
 
 
 EXPORTS = ("cvae_last_error_string", "cvae_abi_version", "cvae_ctx_create", "cvae_ctx_destroy", "cvae_set_status_sink", "cvae_status_latch", "cvae_set_draw_origin", "cvae_set_draw_parts",
-           "cvae_set_option", "cvae_get_option", "cvae_reset_options", "cvae_selftest_limbs", "cvae_selftest_occupy", "cvae_set_side_stream", "cvae_join_side_stream", "cvae_net_prepared_bytes", "cvae_net_prepare_scratch_bytes",
+           "cvae_set_option", "cvae_get_option", "cvae_reset_options", "cvae_selftest_limbs", "cvae_selftest_occupy", "cvae_selftest_gemm_work_bytes", "cvae_selftest_gemm", "cvae_set_side_stream", "cvae_join_side_stream", "cvae_net_prepared_bytes", "cvae_net_prepare_scratch_bytes",
            "cvae_net_prepare", "cvae_pass_workspace_bytes", "cvae_gru_rnn_forward", "cvae_gru_rnn_forward_stacked", "cvae_gru_rnn_forward_stacked_carry", "cvae_sample", "cvae_sample_laplace", "cvae_sample_laplace_backward",
            "cvae_cycle_workspace_bytes", "cvae_cycle_forward", "cvae_cycle_forward_carry", "cvae_profile_collect", "cvae_profile_collect_launches", "cvae_train_profile_collect", "cvae_step_timing", "cvae_workspace_status",
            "cvae_train_image_bytes", "cvae_net_prepare_train", "cvae_net_prepare_train_v", "cvae_train_variants_needed", "cvae_train_tape_bytes", "cvae_train_scratch_bytes",

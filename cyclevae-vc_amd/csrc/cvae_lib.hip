@@ -105,6 +105,7 @@ struct cvae_ctx {
     int side_cap = 0;                                                // tile cap of the side-stream GEMMs being launched (launch_wgrad_side)
     hipEvent_t mask_fork = nullptr, mask_join = nullptr;                         // train-mode forward: the feedback mask drawn on the side stream
     unsigned side_evict = 0;
+    int32_t* gemm_ran = nullptr;                                     // cvae_selftest_gemm: where the GEMM wrappers report what they launched
     // which MFMA-order weight images a train image of THIS context holds (cvae_net_prepare_train_v), by address; an address the
     // context has not prepared holds none (the old process-wide registry assumed "all" for unknown addresses and grew
     // without bound); the oldest entries go when the table is full

@@ -419,6 +419,17 @@ struct SplitWs {
     unsigned* cnt = nullptr;
 };
 
+// cvae_selftest_gemm: what a wrapper launched -- {1 LDS-tiled / two-stage kernel or 0 simple kernel, TM, TN, slices of the contraction}
+static inline void gemm_ran(int tiled, int TM, int TN, int nz) {
+    if (int32_t* r = cx().gemm_ran) { r[0] = tiled; r[1] = TM; r[2] = TN; r[3] = nz; }
+}
+
+// C[m*ldc + n] (+)= sum_k A[m*lda + seg(k)] * Bm[n*ldb + k] + bias[n], then the optional mask epilogue (EpiMask: [B][T][N], M = T*Bp).
+// Operand contract: K and seglen multiples of 16; K a multiple of seglen, or K <= seglen (one segment).  A is read at
+// m*lda + s*segstride + [0, min(seglen, K)) for every segment s (segstride may be negative), Bm at n*ldb + [0, K); C is touched at
+// m*ldc + [0, N) only.  The LDS-tiled kernels need lda, ldb, segstride multiples of 4 and 16-byte aligned A, Bm; anything else (or
+// train_old_gemm) runs k_gemm_nt_seg, where a mask is applied in place by k_mul_mask_tm, which rewrites the WHOLE [M][ldc] block
+// (columns N .. ldc-1 become 0: C must be writable to M*ldc there).
 void gemm_nt(hipStream_t st, const float* A, long lda, int seglen, long segstride, const float* Bm, long ldb, const float* bias,
              float* C, long ldc, int M, int N, int K, int accumulate, SplitWs ws = SplitWs(), EpiMask em = EpiMask{nullptr, 0, 0, 0}) {
     float* part = ws.part;
@@ -435,10 +446,12 @@ void gemm_nt(hipStream_t st, const float* A, long lda, int seglen, long segstrid
         const int nz = ks > 1 ? nblk(K, kchunk) : 1;
         float* pp = nz > 1 ? part : nullptr;
         const dim3 g(nblk(N, 32 * TN), nblk(M, 32 * TM), nz);
+        gemm_ran(1, TM, TN, nz);
         // split contraction: the partial tiles are combined inside the launch by the last block of each tile (cvae_split_combine)
         CVAE_TILE_DISPATCH(launch_nt2, TM, TN, g, A, lda, seglen, segstride, Bm, ldb, bias, C, ldc, M, N, K, accumulate, kchunk, pp, ws.cnt, em);
         return;
     }
+    gemm_ran(0, 0, 0, 1);
     if (opt(OPT_GEMM_TRACE)) fprintf(stderr, "gemm_nt fallback M=%d N=%d K=%d lda=%ld ldb=%ld ss=%ld\n", M, N, K, lda, ldb, segstride);
     hipLaunchKernelGGL((k_gemm_nt_seg<4, 4, 2, 2>), dim3(nblk(N, 128), nblk(M, 128)), dim3(256), 0, st, A, lda, seglen,
                        segstride, Bm, ldb, bias, C, ldc, M, N, K, accumulate);
@@ -447,7 +460,11 @@ void gemm_nt(hipStream_t st, const float* A, long lda, int seglen, long segstrid
                            em.T, N, (int)ldc);
 }
 
+// C[n1*ldc + n2] (+)= sum_m A[m*lda + n1] * Bm[m*ldb + seg(n2)]   (contraction over the M rows; weight gradients).
 // `part`: null, or GEMM_PART_FLOATS of scratch that lets a small output split its contraction over several workgroups
+// Operand contract: the LDS-tiled kernels (lda, ldb, seglen, segstride multiples of 4, 16-byte aligned A, Bm) load float4 guarded
+// on their FIRST element: every row of A must be readable to up(N1, 4) columns, every row of Bm to the end of the float4 that
+// holds the last column of each segment (all callers pad these rows: H3, C9p, Cop, tot).  k_gemm_tn reads exactly N1 / N2 columns.
 void gemm_tn(hipStream_t st, const float* A, long lda, const float* Bm, long ldb, int seglen, long segstride, float* C, long ldc,
              int M, int N1, int N2, int accumulate, SplitWs ws = SplitWs()) {
     float* part = ws.part;
@@ -464,16 +481,21 @@ void gemm_tn(hipStream_t st, const float* A, long lda, const float* Bm, long ldb
         const int nz = ks > 1 ? nblk(M, mchunk) : 1;
         float* pp = nz > 1 ? part : nullptr;
         const dim3 g(nblk(N2, 32 * TN), nblk(N1, 32 * TM), nz);
+        gemm_ran(1, TM, TN, nz);
         CVAE_TILE_DISPATCH(launch_tn2, TM, TN, g, A, lda, Bm, ldb, seglen, segstride, C, ldc, M, N1, N2, accumulate, mchunk, pp, ws.cnt);
         return;
     }
+    gemm_ran(0, 0, 0, 1);
     if (opt(OPT_GEMM_TRACE)) fprintf(stderr, "gemm_tn fallback M=%d N1=%d N2=%d lda=%ld ldb=%ld sl=%d ss=%ld\n", M, N1, N2, lda, ldb, seglen, segstride);
     hipLaunchKernelGGL((k_gemm_tn), dim3(nblk(N2, 64), nblk(N1, 64)), dim3(256), 0, st, A, lda, Bm, ldb, seglen, segstride, C,
                        ldc, M, N1, N2, accumulate);
 }
 
+// C[m*ldc + n] (+)= sum_k A[m*lda + k] * Bm[n*ldb + k].  Operand contract: K a multiple of 16 (the waves split 16-k chunks; a
+// remainder would be dropped); A is read at m*lda + [0, K), Bm at n*ldb + [0, K) as float4 (lda, ldb multiples of 4 in every caller).
 void gemm_ks(hipStream_t st, const float* A, long lda, const float* Bm, long ldb, float* C, long ldc, int M, int N, int K,
              int accumulate) {
+    gemm_ran(1, 0, 0, 1);
     // 16 columns per block: these products have M = Bp rows only, so parallelism must come from N and the K split
     const size_t lds = (size_t)4 * 16 * (16 + 4) * sizeof(float);
     hipLaunchKernelGGL((k_gemm_ks<1>), dim3(nblk(N, 16), nblk(M, 16)), dim3(256), lds, st, A, lda, Bm, ldb, C, ldc, M, N, K,
@@ -498,9 +520,14 @@ struct WgradWork {
     int cap = 0;          // tile cap of the GEMMs when they run on the side stream (0: none)
 };
 
+// out[n] (+)= sum_m A[m*lda + n].  Operand contract: the two-stage kernel reads rows as float4 guarded on their first element, so
+// every row must be readable to up(n, 4) columns (H3 / Cop / C9p / C3p in every caller); k_colsum reads exactly n.  The two-stage
+// kernel writes `out` from the block that draws the last ticket, so it needs the work space: without one (no caller passes an
+// empty SplitWs today) k_colsum runs.
 static void colsum_launch(hipStream_t cs, SplitWs ws, const float* A, long lda, float* out, int rows, int n, int acc) {
     float* part = ws.part;
-    if (!al4(lda) || !al16p(A) || opt(OPT_TRAIN_OLD_GEMM) || nblk(n, 64) > GEMM_CNT) {
+    if (!al4(lda) || !al16p(A) || opt(OPT_TRAIN_OLD_GEMM) || nblk(n, 64) > GEMM_CNT || !part || !ws.cnt) {
+        gemm_ran(0, 0, 0, 1);
         hipLaunchKernelGGL((k_colsum), dim3(nblk(n, 16)), dim3(256), 16 * 17 * sizeof(float), cs, A, lda, out, rows, n, acc);
         return;
     }
@@ -508,6 +535,7 @@ static void colsum_launch(hipStream_t cs, SplitWs ws, const float* A, long lda, 
     int rs = 1024 / nblk(n, 64);
     rs = rs > 64 ? 64 : (rs < 1 ? 1 : rs);
     const int mchunk = (int)up(nblk(rows, rs), 16), nz = nblk(rows, mchunk);
+    gemm_ran(1, 0, 0, nz);
     // (the sum of the slices happens in the launch: the last block of each 64-column group adds them in slice order)
     hipLaunchKernelGGL((k_colsum_part), dim3(nblk(n, 64), nz), dim3(256), 16 * 17 * sizeof(f32x4), cs, A, lda, part, rows, n, mchunk,
                        ws.cnt, out, acc);
@@ -1188,6 +1216,107 @@ int cvae_adam_step_counted(cvae_ctx* ctx, float* param, const float* grad, float
     hipLaunchKernelGGL((k_adam_tick), dim3(1), dim3(64), 0, (hipStream_t)stream, (int*)state, beta1, beta2, (const int*)gate);
     hipLaunchKernelGGL((k_adam_counted), dim3(nblk((long)n, 256)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg, exp_avg_sq,
                        (long)n, lr, beta1, beta2, eps, (const int*)state, (const int*)gate);
+    CVAE_HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// ---- cvae_selftest_gemm: one GEMM / column sum through the wrappers above, for the tests (include/cyclevae_hip.h holds the contracts)
+size_t cvae_selftest_gemm_work_bytes(cvae_ctx* ctx) {
+    CVAE_ENTER_SZ(ctx);
+    return (size_t)(GEMM_PART_FLOATS + GEMM_CNT) * sizeof(float);
+}
+
+int cvae_selftest_gemm(cvae_ctx* ctx, const cvae_gemm_case* c, void* work, size_t work_bytes, int32_t ran[4], void* stream) {
+    CVAE_ENTER(ctx);
+    static_assert(GEMM_CNT == CVAE_SELFTEST_GEMM_CNT, "header and library disagree about the counters");
+    if (!c || !ran) return fail(-1, "selftest_gemm: null argument");
+    if (!c->A || !c->C || (c->kind != CVAE_GEMM_COLSUM && !c->B)) return fail(-1, "selftest_gemm: null operand");
+    const long M = c->M, N = c->N, K = c->K, lda = c->lda, ldb = c->ldb, ldc = c->ldc, ss = c->segstride, sl = c->seglen;
+    if (M < 1 || N < 1 || (c->kind != CVAE_GEMM_COLSUM && K < 1)) return fail(-1, "selftest_gemm: extents must be >= 1");
+    if (lda < 0 || ldb < 0 || ldc < 0) return fail(-1, "selftest_gemm: negative leading dimension");
+    if (c->use_split) {
+        if (!work || work_bytes < (size_t)(GEMM_PART_FLOATS + GEMM_CNT) * sizeof(float) || !al16p(work))
+            return fail(-1, "selftest_gemm: work space missing, smaller than cvae_selftest_gemm_work_bytes() or not 16-byte aligned");
+    }
+    const bool old = opt(OPT_TRAIN_OLD_GEMM) != 0;
+    const bool al_ab = al4(lda) && al16p(c->A) && (c->kind == CVAE_GEMM_COLSUM || (al4(ldb) && al16p(c->B)));
+    // the floats the kernels may touch around A, B, C under the contract, against what the caller owns
+    long a_lo = 0, a_hi = 0, b_lo = 0, b_hi = 0, c_hi = 0;
+    switch (c->kind) {
+    case CVAE_GEMM_NT: {
+        if (sl < 1 || K % 16 || sl % 16) return fail(-1, "selftest_gemm nt: K (%ld) and seglen (%ld) must be multiples of 16", K, sl);
+        if (K > sl && K % sl) return fail(-1, "selftest_gemm nt: K (%ld) must be a multiple of seglen (%ld) or fit one segment", K, sl);
+        if (ldc < N) return fail(-1, "selftest_gemm nt: ldc < N");
+        const long nseg = K <= sl ? 1 : K / sl, len = K < sl ? K : sl;
+        const bool tiled = !old && al_ab && al4(ss);
+        a_lo = (nseg - 1) * ss < 0 ? (nseg - 1) * ss : 0;
+        a_hi = (M - 1) * lda + ((nseg - 1) * ss > 0 ? (nseg - 1) * ss : 0) + len;
+        b_hi = (N - 1) * ldb + K;
+        c_hi = (M - 1) * ldc + N;
+        if (c->mask) {
+            if (c->mask_B < 1 || c->mask_Bp < c->mask_B || c->mask_T < 1 || (long)c->mask_T * c->mask_Bp != M)
+                return fail(-1, "selftest_gemm nt: the mask covers [B][T][N] with B <= Bp and M = T*Bp");
+            if (!tiled) c_hi = M * ldc;      // (k_mul_mask_tm rewrites whole rows)
+        }
+        break;
+    }
+    case CVAE_GEMM_TN: {
+        if (sl < 1) return fail(-1, "selftest_gemm tn: seglen must be >= 1");
+        if (c->bias || c->mask) return fail(-1, "selftest_gemm tn: takes neither bias nor mask");
+        if (ldc < K) return fail(-1, "selftest_gemm tn: ldc < N2");
+        const bool tiled = !old && al_ab && al4(sl) && al4(ss);
+        const long nseg = (K + sl - 1) / sl, q = tiled ? 4 : 1;
+        a_hi = (M - 1) * lda + up(N, q);
+        long lo = 0, hi = 0;
+        for (long s : {0L, nseg - 2, nseg - 1}) {       // (s*ss is linear over the full segments: the ends decide)
+            if (s < 0) continue;
+            const long cnt = K - s * sl < sl ? K - s * sl : sl;
+            if (s * ss < lo) lo = s * ss;
+            if (s * ss + up(cnt, q) > hi) hi = s * ss + up(cnt, q);
+        }
+        b_lo = lo;
+        b_hi = (M - 1) * ldb + hi;
+        c_hi = (N - 1) * ldc + K;
+        break;
+    }
+    case CVAE_GEMM_KS:
+        if (K % 16) return fail(-1, "selftest_gemm ks: K (%ld) must be a multiple of 16", K);
+        if (c->bias || c->mask) return fail(-1, "selftest_gemm ks: takes neither bias nor mask");
+        if (ldc < N) return fail(-1, "selftest_gemm ks: ldc < N");
+        a_hi = (M - 1) * lda + K;
+        b_hi = (N - 1) * ldb + K;
+        c_hi = (M - 1) * ldc + N;
+        break;
+    case CVAE_GEMM_COLSUM: {
+        if (c->bias || c->mask) return fail(-1, "selftest_gemm colsum: takes neither bias nor mask");
+        const bool two = !old && al_ab && c->use_split && nblk(N, 64) <= GEMM_CNT;
+        a_hi = (M - 1) * lda + (two ? up(N, 4) : N);
+        c_hi = N;
+        break;
+    }
+    default:
+        return fail(-1, "selftest_gemm: unknown kind %d", (int)c->kind);
+    }
+    if (c->a_lo > a_lo || c->a_hi < a_hi)
+        return fail(-1, "selftest_gemm: the kernels may touch A at [%ld, %ld), the caller owns [%lld, %lld)", a_lo, a_hi, (long long)c->a_lo, (long long)c->a_hi);
+    if (c->kind != CVAE_GEMM_COLSUM && (c->b_lo > b_lo || c->b_hi < b_hi))
+        return fail(-1, "selftest_gemm: the kernels may touch B at [%ld, %ld), the caller owns [%lld, %lld)", b_lo, b_hi, (long long)c->b_lo, (long long)c->b_hi);
+    if (c->c_hi < c_hi) return fail(-1, "selftest_gemm: the kernels may touch C at [0, %ld), the caller owns %lld floats", c_hi, (long long)c->c_hi);
+    SplitWs ws;
+    if (c->use_split) { ws.part = (float*)work; ws.cnt = (unsigned*)((float*)work + GEMM_PART_FLOATS); }
+    hipStream_t st = (hipStream_t)stream;
+    ran[0] = ran[1] = ran[2] = ran[3] = -1;
+    cx().gemm_ran = ran;
+    switch (c->kind) {
+    case CVAE_GEMM_NT:
+        gemm_nt(st, c->A, lda, (int)sl, ss, c->B, ldb, c->bias, c->C, ldc, (int)M, (int)N, (int)K, c->accumulate, ws,
+                EpiMask{c->mask, c->mask_B, c->mask_Bp, c->mask_T});
+        break;
+    case CVAE_GEMM_TN: gemm_tn(st, c->A, lda, c->B, ldb, (int)sl, ss, c->C, ldc, (int)M, (int)N, (int)K, c->accumulate, ws); break;
+    case CVAE_GEMM_KS: gemm_ks(st, c->A, lda, c->B, ldb, c->C, ldc, (int)M, (int)N, (int)K, c->accumulate); break;
+    default: colsum_launch(st, ws, c->A, lda, c->C, (int)M, (int)N, c->accumulate); break;
+    }
+    cx().gemm_ran = nullptr;
     CVAE_HIP_OK(hipGetLastError());
     return 0;
 }

@@ -234,6 +234,60 @@ int cvae_selftest_limbs(cvae_ctx* ctx, const float* x, float* y, int64_t n, void
  * cycles on `stream`: CU-side contention for the all-resident recurrent kernels, which are launched plainly after a one-time
  * occupancy check (tests/test_gpu_parity.py::test_hand_off_under_cu_contention). */
 int cvae_selftest_occupy(cvae_ctx* ctx, int blocks, size_t lds_bytes, int64_t cycles, void* stream);
+/*
+ * Test aid (additive, ABI 10): ONE training GEMM / column sum through the wrapper a training pass calls, unchanged, so that
+ * the options ("gemm_force", "train_old_gemm", "gemm_max_split", ...) act exactly as they do in a pass.  No reference counterpart
+ * (the reference calls torch.nn.functional; these are the products its autograd graph holds).
+ *
+ * kind and the three extents, in the wrapper's own argument order:
+ *   CVAE_GEMM_NT      C[m*ldc + n] (+)= sum_k A[m*lda + seg(k)] * B[n*ldb + k] + bias[n],   m < M, n < N, k < K
+ *                     seg(k) = (k / seglen)*segstride + k % seglen; then, with a mask ([mask_B][mask_T][N], M = mask_T*mask_Bp):
+ *                     row m = f*mask_Bp + b is multiplied by mask[(b*mask_T + f)*N + n], rows b >= mask_B become 0.
+ *   CVAE_GEMM_TN      C[i*ldc + j] (+)= sum_m A[m*lda + i] * B[m*ldb + seg(j)],   m < M (contraction ROWS), i < N, j < K
+ *   CVAE_GEMM_KS      C[m*ldc + n] (+)= sum_k A[m*lda + k] * B[n*ldb + k]         (the small-M product of the reverse recurrence)
+ *   CVAE_GEMM_COLSUM  C[n] (+)= sum_m A[m*lda + n],   m < M, n < N                  (K, B unused)
+ * use_split: hand the wrapper the split work space (partial tiles + arrival counters) inside `work`; 0: none (no split possible).
+ *
+ * Operand contracts (what the kernels may touch; the callers in a training pass pad their buffers accordingly).  [a_lo, a_hi),
+ * [b_lo, b_hi) and [0, c_hi) are the floats the caller owns around A, B and C; a call whose kernels could leave them, or that
+ * breaks another rule below, is refused with -1 and a message instead of being launched:
+ *   nt      K and seglen multiples of 16; K a multiple of seglen, or K <= seglen (one segment).  A is touched at
+ *           m*lda + s*segstride + [0, min(seglen, K)) for every segment s (segstride may be negative: a_lo < 0), B at
+ *           n*ldb + [0, K), C at m*ldc + [0, N) only.  The LDS-tiled kernels run when lda, ldb, segstride are multiples of 4 and A, B
+ *           are 16-byte aligned; otherwise (or with "train_old_gemm") the simple kernel runs, and THERE a mask is applied in place
+ *           by a second kernel that rewrites the whole [M][ldc] block: columns N .. ldc-1 become 0 (c_hi >= M*ldc).
+ *   tn      tiled when lda, ldb, seglen, segstride are multiples of 4 and A, B 16-byte aligned: every row of A is read as float4 up
+ *           to up(N, 4) columns, every row of B to the end of the float4 that holds the last column of each segment.  The simple
+ *           kernel reads exactly the N and K columns.
+ *   ks      K a multiple of 16; A at m*lda + [0, K), B at n*ldb + [0, K).
+ *   colsum  two-stage kernel (lda a multiple of 4, A 16-byte aligned, split work space given, not "train_old_gemm"): rows are
+ *           read as float4 up to up(N, 4) columns; the simple kernel reads exactly N.  Without a split work space the simple
+ *           kernel runs (the two-stage kernel needs the counters to write its result).
+ *   all     extents >= 1, leading dimensions >= 0, ldc >= the output's columns, bias (nt only, may be NULL) holds N floats.
+ *
+ * work: cvae_selftest_gemm_work_bytes() bytes of device memory, 16-byte aligned, ZEROED ONCE by the caller: the partial-tile area
+ * followed by CVAE_SELFTEST_GEMM_CNT uint32 arrival counters (the last bytes of `work`), which every call leaves at zero again.
+ * ran (HOST int32[4], written before the call returns): what the wrapper launched -- {1 LDS-tiled / two-stage kernel or 0 simple
+ * kernel, TM, TN (block tile 32*TM x 32*TN; 0 for ks and colsum), slices of the contraction (grid z, grid y for colsum)}.
+ * The launch is asynchronous on `stream`.
+ */
+enum { CVAE_GEMM_NT = 0, CVAE_GEMM_TN = 1, CVAE_GEMM_KS = 2, CVAE_GEMM_COLSUM = 3 };
+#define CVAE_SELFTEST_GEMM_CNT 4096
+typedef struct cvae_gemm_case {
+    int32_t kind, accumulate, use_split;
+    int32_t M, N, K;
+    int32_t seglen;
+    int32_t mask_B, mask_Bp, mask_T;     /* read when mask != NULL */
+    int64_t lda, ldb, ldc, segstride;
+    int64_t a_lo, a_hi, b_lo, b_hi, c_hi;
+    const float* A;
+    const float* B;
+    const float* bias;
+    const float* mask;
+    float* C;
+} cvae_gemm_case;
+size_t cvae_selftest_gemm_work_bytes(cvae_ctx* ctx);
+int cvae_selftest_gemm(cvae_ctx* ctx, const cvae_gemm_case* c, void* work, size_t work_bytes, int32_t ran[4], void* stream);
 
 /* Bytes of the caller-owned prepared-weights image / prepare-time scratch for a net. */
 size_t cvae_net_prepared_bytes(cvae_ctx* ctx, const cvae_net_desc* d);
