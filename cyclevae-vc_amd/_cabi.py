@@ -128,6 +128,19 @@ class DecodeJob(C.Structure):
                 ("diff", _fp), ("idx", _fp)]
 
 
+TRAINLOG_MAX_CYC, TRAINLOG_MAX_UTT = 8, 128       # CVAE_TRAINLOG_MAX_CYC, CVAE_TRAINLOG_MAX_UTT
+TRAINLOG_SLOTS = ("lat", "rec", "cv", "latcv", "reccyc")      # cvae_trainlog_window_args.traj[i][k] (stage4.PASS_SLOTS)
+TRAINLOG_REC = 9                                    # doubles per (cycle, utterance) record
+
+
+class TrainlogWindowArgs(C.Structure):
+    """cvae_trainlog_window_args (device addresses; flen_acc, s_idx, e_idx, selected: HOST arrays the call reads before it returns)."""
+    _fields_ = [("traj", (_fp * 5) * TRAINLOG_MAX_CYC), ("x_win", _fp), ("x_row_stride", C.c_int64), ("x_utt_stride", C.c_int64),
+                ("spcidx", _fp), ("spc_ld", C.c_int64), ("flen_acc", _fp), ("s_idx", _fp), ("e_idx", _fp), ("selected", _fp),
+                ("n_cyc", C.c_int32), ("B", C.c_int32), ("T", C.c_int32), ("D", C.c_int32), ("L", C.c_int32), ("stdim", C.c_int32),
+                ("src_idx_s", C.c_int32), ("acc_rows", C.c_int32), ("acc", _fp * 4), ("rec_out", _fp)]
+
+
 class CvaeError(RuntimeError):
     pass
 
@@ -314,6 +327,8 @@ class CvaeLib(object):
         L.cvae_mc2e_batch.argtypes = [C.POINTER(Mc2eJob), C.c_int, C.c_double, C.c_int, _fp, C.c_size_t, _fp]
         L.cvae_decode_jobs.restype = C.c_int
         L.cvae_decode_jobs.argtypes = [C.POINTER(DecodeJob), C.c_int, _fp, C.c_size_t, _fp]
+        L.cvae_trainlog_window.restype = C.c_int
+        L.cvae_trainlog_window.argtypes = [C.POINTER(TrainlogWindowArgs), _fp]
         L.cvae_step_timing.restype = C.c_int
         L.cvae_step_timing.argtypes = [C.POINTER(NetDesc), C.c_int, C.c_int, _fp, C.POINTER(C.c_double * 8), _fp]
         L.cvae_profile_collect.restype = C.c_int
@@ -647,6 +662,10 @@ class CvaeLib(object):
         arr = (DecodeJob * max(1, len(jobs)))(*jobs)
         self._check(self.lib.cvae_decode_jobs(arr, len(jobs), work, work_bytes, stream or None), "cvae_decode_jobs")
 
+    def trainlog_window(self, args, stream=0):
+        """args: a TrainlogWindowArgs; its host arrays are read before the call returns, nothing is waited for."""
+        self._check(self.lib.cvae_trainlog_window(C.byref(args), stream or None), "cvae_trainlog_window")
+
     def step_timing(self, d, B, T, ws, stream=0):
         out = (C.c_double * 8)()
         self._check(self.lib.cvae_step_timing(C.byref(d), B, T, ws, C.byref(out), stream or None), "cvae_step_timing")
@@ -734,6 +753,6 @@ EXPORTS = ("cvae_last_error_string", "cvae_abi_version", "cvae_ctx_create", "cva
            "cvae_kl_gauss_backward",
            "cvae_gv_postfilter", "cvae_mcd_aligned", "cvae_mc2e", "cvae_dtw_work_bytes", "cvae_dtw_org_to_trg",
            "cvae_dtw_batch_work_bytes", "cvae_dtw_batch", "cvae_eval_stats", "cvae_latent_mean",
-           "cvae_mc2e_batch_work_bytes", "cvae_mc2e_batch", "cvae_decode_jobs",
+           "cvae_mc2e_batch_work_bytes", "cvae_mc2e_batch", "cvae_decode_jobs", "cvae_trainlog_window",
            "cvae_net_prepared_bytes_deep", "cvae_net_prepare_scratch_bytes_deep", "cvae_net_prepare_deep", "cvae_pass_workspace_bytes_deep",
            "cvae_plan_pass", "cvae_plan_pass_deep", "cvae_gru_rnn_forward_deep", "cvae_net_prepared_in_range")

@@ -1481,4 +1481,5 @@ int cvae_net_prepared_in_range(cvae_ctx* ctx, const cvae_net_desc* d, int n_laye
 #include "cvae_validation.inc"
 #include "cvae_stage5.inc"
 #include "cvae_decode.inc"
+#include "cvae_trainlog.inc"
 #include "cvae_deep.inc"

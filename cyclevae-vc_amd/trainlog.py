@@ -1,0 +1,418 @@
+"""What the stage-4 training loop does AROUND every step, on the device and without a host stall (reference
+train_gru_cyclevae_gauss_batch.py:660-739, :1312-1316, :1339-1353, :1364-1472; utterance-length mini-batches, :1476-1665, are not built).
+
+The script reads five scalars back per utterance and cycle (`.item()`), runs four dtw_c.calc_mcd per utterance and cycle on host
+copies, copies three trajectories per window to the host for its GV buffers, and at the end of an utterance batch runs one more
+encoder pass and six dtw_c.dtw_org_to_trg per utterance on host copies: a device synchronisation each.  Here:
+
+  per window       ONE launch (cvae_trainlog_window: nine f64 figures per cycle and utterance, and the window's rows appended to
+                   four utterance-long device buffers), one asynchronous copy of the record and of the step's loss to a pinned slot
+                   behind an event; the host formats the script's text when the slot has arrived (lines / poll)
+  per batch        validation.ValidationPass's machinery on the accumulated buffers: one eval-form encoder pass, GATHER64 jobs, six
+                   problems of cvae_dtw_batch per utterance, LATDIST jobs, the GV variances (CVAE_STAT_GV) -- again behind an event
+  per epoch        epoch_end(): the figures and the line of :719-739
+
+PARITY UNPINNED for the DTW / calc_mcd halves (dtw_c is not in the reference tree; oracle.dtw_org_to_trg / mcd_aligned are the
+written definitions).  The five loss figures and the GV variances are formed in float64 from the fp32 trajectories, where the
+script's are fp32 reductions.
+
+The GV rule of :1339-1348 appends the variances of the PREVIOUS utterance batch when a new one starts with iter_count > 0.  The
+reference's generator yields one dataloader batch per pass and the loop resets iter_count at the sentinel, so with it the rule never
+fires and the epoch line prints nan for the six GV figures -- exactly as the script does.  The rule is implemented as written: it
+fires when two utterance batches follow each other without a sentinel between them.
+"""
+import os
+
+import numpy as np
+import torch
+
+import _cabi
+import gru_vae
+import stage4
+
+WIN_SRC = ("loss_mcd_src_src", "loss_mcd_src_trg_src", "loss_mcd_src_trg", "loss_lat_src", "loss_lat_src_cv")      # record [0..4]
+WIN_TRG = ("loss_mcd_trg_trg", "loss_mcd_trg_src_trg", "loss_mcd_trg_src", "loss_lat_trg", "loss_lat_trg_cv")
+DB_SRC = ("mcdpow_src_src", "mcd_src_src", "mcdpow_src_trg_src", "mcd_src_trg_src")                                # record [5..8]
+DB_TRG = ("mcdpow_trg_trg", "mcd_trg_trg", "mcdpow_trg_src_trg", "mcd_trg_src_trg")
+CLOSE_SRC = ("mcdpow_src_trg", "mcd_src_trg", "lat_dist_srctrg1", "lat_dist_srctrg2")                              # :679-695
+CLOSE_TRG = ("mcdpow_trg_src", "mcd_trg_src", "lat_dist_trgsrc1", "lat_dist_trgsrc2")
+GV_SRC = ("gv_src_src", "gv_src_trg", "gv_src_trg_src")                                                            # :1342-1344
+GV_TRG = ("gv_trg_trg", "gv_trg_src", "gv_trg_src_trg")
+EPOCH_ORDER = ("loss_mcd_trg_trg", "loss_mcd_trg_src_trg", "loss_mcd_trg_src", "loss_mcd_src_src", "loss_mcd_src_trg_src", "loss_mcd_src_trg",
+               "loss_lat_trg", "loss_lat_trg_cv", "loss_lat_src", "loss_lat_src_cv",
+               "eval_gv_trg_trg", "mcdpow_trg_trg", "mcd_trg_trg", "eval_gv_trg_src_trg", "mcdpow_trg_src_trg", "mcd_trg_src_trg",
+               "eval_gv_trg_src", "mcdpow_trg_src", "mcdpowstd_trg_src", "mcd_trg_src", "mcdstd_trg_src", "lat_dist_trgsrc1", "lat_dist_trgsrc2",
+               "eval_gv_src_src", "mcdpow_src_src", "mcd_src_src", "eval_gv_src_trg_src", "mcdpow_src_trg_src", "mcd_src_trg_src",
+               "eval_gv_src_trg", "mcdpow_src_trg", "mcdpowstd_src_trg", "mcd_src_trg", "mcdstd_src_trg", "lat_dist_srctrg1", "lat_dist_srctrg2")
+EPOCH_FMT = ("[%d] %.3f %.3f %.3f %.3f %.3f %.3f ; %.3f %.3f %.3f %.3f ; %.6f %.3f dB %.6f dB , %.3f %.3f dB %.3f dB , "
+             "%.6f %.3f dB (+- %.3f) %.6f dB (+- %.3f) , %.6f %.6f ; %.6f %.3f dB %.6f dB , %.3f %.3f dB %.3f dB , "
+             "%.6f %.3f dB (+- %.3f) %.6f dB (+- %.3f) , %.6f %.6f ;; ")           # :728
+
+
+class _Done(object):
+    """The event of a build without a device queue (the host-fiber emulation: a call has finished when it returns)."""
+
+    def query(self):
+        return True
+
+    def synchronize(self):
+        pass
+
+
+def _mean(v):
+    return float(np.mean(v)) if len(v) else float("nan")
+
+
+def _std(v):
+    return float(np.std(v)) if len(v) else float("nan")
+
+
+def _ints(v):
+    return [int(x) for x in (v.tolist() if hasattr(v, "tolist") else v)]
+
+
+class TrainLog(object):
+    """TrainLog(model_encoder, model_decoder, lat_dim, stdim, gv_src_mean, gv_trg_mean, n_cyc=2, spk_src=None, half_cyc=False), used
+    around an unchanged stage4.Stage4Step:
+
+        tl.before(items, y_in_pp)      # items: one 22-field yield of loader.train_generator (batch_size > 0), or the sentinel
+        loss, state = step(...)
+        tl.after(items, step.last_trajs, loss)
+        for line in tl.lines(): logging.info(line)
+        ...
+        s = tl.epoch_end()             # after before(sentinel): the figures of :722-738 and s["line"], then the resets of :1202-1269
+
+    Neither before() on a window nor after() waits for the device.  Timing fields: after(..., sec=) takes the caller's seconds for
+    the "(%.3f sec)" of :1472 and the "(%.3f min., %.3f sec / batch)" of :739; without it both parentheses are omitted.
+    epoch_idx (0 on construction) numbers the epoch line; set it when resuming."""
+
+    MAX_IN_FLIGHT = stage4.Stage4Step.MAX_IN_FLIGHT
+
+    def __init__(self, model_encoder, model_decoder, lat_dim, stdim, gv_src_mean, gv_trg_mean, n_cyc=2, spk_src=None, half_cyc=False):
+        if not 1 <= int(n_cyc) <= _cabi.TRAINLOG_MAX_CYC:
+            raise ValueError("n_cyc = %d: TrainLog takes 1 .. %d cycles" % (n_cyc, _cabi.TRAINLOG_MAX_CYC))
+        self.enc, self.dec, self.lat_dim, self.stdim, self.n_cyc = model_encoder, model_decoder, int(lat_dim), int(stdim), int(n_cyc)
+        self.spk_src, self.half_cyc = spk_src, bool(half_cyc)
+        self.gv_src_mean, self.gv_trg_mean = np.asarray(gv_src_mean, np.float64), np.asarray(gv_trg_mean, np.float64)
+        self.epoch_idx = self.iter_idx = 0
+        self._prev = self._prev_featfile = self._acc = None
+        self._pending, self._lines, self._free = [], [], {}
+        self._fresh = True
+        self.last_lat_srctrg = None            # (kept: the encoder pass of the latest closed utterance batch)
+        self.last_record = None                # (kept: the device record [n_cyc, B, 9] of the latest window)
+        self.last_args = None
+        self._reset()
+
+    def _reset(self):
+        """:1202-1269."""
+        names = WIN_SRC + WIN_TRG + DB_SRC + DB_TRG + CLOSE_SRC + CLOSE_TRG + GV_SRC + GV_TRG
+        self.lists = {k: [[] for _ in range(self.n_cyc)] for k in names}
+        self.loss, self.total = [], []
+        self.iter_count = 0
+
+    # ---- plumbing ----------------------------------------------------------------------------------------------------------------
+    def _is_src(self, featfile):
+        return os.path.basename(os.path.dirname(featfile)) == self.spk_src
+
+    def _pinned(self, n):
+        """A pinned float64 slot of n values from the free list (pageable where there is no device)."""
+        free = self._free.setdefault(n, [])
+        if free:
+            return free.pop()
+        return torch.empty(n, dtype=torch.float64, pin_memory=torch.cuda.is_available())
+
+    def _behind(self, dev_tensor, slot):
+        """Queue the copy of dev_tensor to the pinned slot and return the event behind it."""
+        slot.copy_(dev_tensor, non_blocking=True)
+        if not dev_tensor.is_cuda:
+            return _Done()
+        ev = torch.cuda.Event()
+        ev.record()
+        return ev
+
+    # ---- before: :660-704 and the GV rule of :1339-1348 --------------------------------------------------------------------------
+    def before(self, items, y_in_pp):
+        if len(items) == 16:
+            raise NotImplementedError("utterance-length mini-batches (batch_size == 0, train...:1476-1665) are not built: TrainLog takes the "
+                                      "22-field yields of loader.train_generator(batch_size > 0)")
+        if len(items) != 22:
+            raise ValueError("TrainLog.before: a yield of %d fields, expected 22" % len(items))
+        sentinel = items[9] < 0
+        if not sentinel:
+            gru_vae._need_cuda(items[0], "TrainLog.before(batch_src)")
+        closing = self.iter_count > 0 and (sentinel or items[5] == 0)                                 # :672
+        fresh = sentinel or not (items[5] > 0 and self._prev_featfile == list(items[13]) and self.iter_count > 0)      # :1298
+        gv_rows = 0
+        if fresh and not sentinel and self.iter_count > 0:                                            # :1339-1340
+            gv_rows = min(int(items[21]), int(self._prev[21]))
+        if closing or gv_rows:
+            self._close(y_in_pp, closing, gv_rows)
+        self._fresh = fresh
+
+    def _close(self, y_in_pp, closing, gv_rows):
+        """The figures of the utterance batch that has just ended, from its accumulators: one encoder pass, two statistics launches
+        around one cvae_dtw_batch, one copy behind an event."""
+        p, L, sd = self._prev, self.lat_dim, self.stdim
+        lib, st = gru_vae._lib(), gru_vae._stream()
+        acc = self._acc
+        dev = acc["cv"].device
+        B, rows, D = acc["cv"].shape
+        cursor = [0]
+
+        def take(n):
+            at = cursor[0]
+            cursor[0] += int(n)
+            return at
+        where, jobs1, jobs2, probs = {}, [], [], []
+        job = lambda kind, rows_, c0, c1, a, lda, b=None, ldb=0, idx=None, dst=None, out_off=0, src_rows=0: _cabi.StatJob(
+            kind, rows_, c0, c1, src_rows, 0, a, b, lda, ldb, idx, dst, out_off)
+        row = lambda t, j, col=0: (t.data_ptr() + 4 * (j * t.shape[1] * t.shape[2] + col), t.shape[2])
+        n_close = int(p[21]) if closing else 0
+        flens = _ints(p[15])
+        for j in range(gv_rows):
+            if not 1 <= flens[j] <= rows:
+                raise ValueError("flens_src[%d] = %d does not fit the %d accumulated frames" % (j, flens[j], rows))
+            for k in ("rec", "cv", "reccyc"):
+                where[("gv", k, j)] = take(D - 1)
+        for j in range(n_close):
+            for n in ("mcdpow", "mcd", "ld_a", "ld_b", "cd_a", "cd_b", "al_a", "al_b"):
+                where[(n, j)] = take(1)
+        n_out = cursor[0]
+        lay = []
+        if closing:
+            feat_trg = p[3].to(torch.float32).contiguous()
+            spc = p[11].to(device=dev, dtype=torch.int64).contiguous()
+            spc_trg = p[12].to(device=dev, dtype=torch.int64).contiguous()
+            ns, nsp = _ints(p[17]), _ints(p[18])
+            if feat_trg.shape[0] != B or spc.shape[0] != B or spc_trg.shape[0] != B or feat_trg.shape[2] != sd + D:
+                raise ValueError("the previous yield does not hold %d utterances of %d features" % (B, sd + D))
+            for j in range(n_close):
+                if not (1 <= ns[j] <= spc.shape[1] and 1 <= nsp[j] <= spc_trg.shape[1]):
+                    raise ValueError("flens_spc of utterance %d (%d, %d) do not fit the speech-frame index rows" % (j, ns[j], nsp[j]))
+            y = y_in_pp.to(torch.float32).reshape(-1, 1, y_in_pp.shape[-1])
+            y = y[:1].expand(B, 1, y.shape[-1]).contiguous() if y.shape[0] != B else y
+            with torch.no_grad():                                                                     # :673-677
+                lat_par = self.enc(feat_trg, y, clamp_vae=True, lat_dim=L)[0].contiguous()
+            self.last_lat_srctrg = lat_par
+            mat = lambda r, c: (take(r * c), r, c)
+            twf_len = 0
+            for j in range(n_close):
+                e = {"g_trj": mat(ns[j], D), "g_feat": mat(nsp[j], D), "g_par": mat(nsp[j], 2 * L), "g_own": mat(ns[j], 2 * L),
+                     "al_1": mat(nsp[j], 2 * L), "al_2": mat(ns[j], 2 * L)}
+                t2s = [nsp[j], nsp[j], nsp[j], ns[j], ns[j], nsp[j]]
+                e["frames"] = [take(t) for t in t2s]
+                e["twf"] = []
+                for t in t2s:
+                    e["twf"].append(twf_len)
+                    twf_len += t
+                lay.append(e)
+            twf = torch.empty(max(1, twf_len), dtype=torch.int64, device=dev)
+        arena = torch.empty(max(1, cursor[0]), dtype=torch.float64, device=dev)
+        a0 = arena.data_ptr()
+        A = lambda off: a0 + 8 * off
+        for j in range(gv_rows):                                                                      # :1342-1348 (float64 here)
+            for k in ("rec", "cv", "reccyc"):
+                a, lda = row(acc[k], j)
+                jobs1.append(job(_cabi.STAT_GV, flens[j], 1, D, a, lda, out_off=where[("gv", k, j)]))
+        for j, e in enumerate(lay):
+            ix = spc.data_ptr() + 8 * j * spc.shape[1]
+            ixp = spc_trg.data_ptr() + 8 * j * spc_trg.shape[1]
+            for key, t, idx, col, c1, nrows in (("g_trj", acc["cv"], ix, 0, D, rows), ("g_feat", feat_trg, ixp, sd, D, feat_trg.shape[1]),
+                                                ("g_par", lat_par, ixp, 0, 2 * L, lat_par.shape[1]), ("g_own", acc["lat"], ix, 0, 2 * L, rows)):
+                a, lda = row(t, j, col)
+                jobs1.append(job(_cabi.STAT_GATHER64, e[key][1], 0, c1, a, lda, idx=idx, dst=A(e[key][0]), src_rows=nrows))
+
+            def prob(org, trg_, k, mcd, aligned, mean, c0=0):
+                (oo, r1, c), (to, r2, _) = e[org], e[trg_]
+                return _cabi.DtwProblem(A(oo + c0), A(to + c0), c, c, r1, r2, c - c0, mcd, None if aligned is None else A(e[aligned][0]),
+                                        twf.data_ptr() + 8 * e["twf"][k], A(e["frames"][k]), A(where[(mean, j)]))
+            probs += [prob("g_trj", "g_feat", 0, -1, None, "mcdpow"),                                 # :679
+                      prob("g_trj", "g_feat", 1, -1, None, "mcd", c0=1),                              # :680
+                      prob("g_own", "g_par", 2, -1, "al_1", "al_a"),                                  # :683
+                      prob("g_par", "g_own", 3, 0, None, "cd_a"),                                     # :685
+                      prob("g_par", "g_own", 4, -1, "al_2", "al_b"),                                  # :686
+                      prob("g_own", "g_par", 5, 0, None, "cd_b")]                                     # :688
+            for n, al, ref in (("ld_a", "al_1", "g_par"), ("ld_b", "al_2", "g_own")):                 # :684, :687
+                (ao, r, c), (ro, _, _) = e[al], e[ref]
+                jobs2.append(job(_cabi.STAT_LATDIST, r, 0, c, A(ao), c, A(ro), c, out_off=where[(n, j)]))
+        n1, n2 = len(jobs1), len(jobs2)
+        raw = np.frombuffer(bytes((_cabi.StatJob * (n1 + n2))(*(jobs1 + jobs2))), np.uint8)
+        stage = torch.empty(raw.size, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+        stage.copy_(torch.from_numpy(raw.copy()))
+        jdev = stage.to(dev, non_blocking=True)
+        size = _cabi.C.sizeof(_cabi.StatJob)
+        if n1:
+            lib.eval_stats(jdev.data_ptr(), n1, a0, st)
+        if probs:
+            nb = lib.dtw_batch_work_bytes(len(probs), max(q.T1 for q in probs), max(q.T2 for q in probs))
+            work = torch.empty(nb, dtype=torch.uint8, device=dev)
+            lib.dtw_batch(probs, work.data_ptr(), nb, st)
+        if n2:
+            lib.eval_stats(jdev.data_ptr() + n1 * size, n2, a0, st)
+        slot = self._pinned(max(1, n_out))
+        ev = self._behind(arena[:max(1, n_out)], slot)
+        meta = dict(where=where, gv_rows=gv_rows, n_close=n_close, files=list(p[13]), files_trg=list(p[14]),
+                    gv_files=list(self._prev_featfile or []), D=D, keep=(stage, jdev))
+        self._pending.append(("close", ev, slot, meta))
+
+    # ---- after: the window's launch ----------------------------------------------------------------------------------------------
+    def after(self, items, trajs, loss, sec=None):
+        """Launch cvae_trainlog_window on the trajectories of the window's chain (Stage4Step.last_trajs), queue the copy of its record
+        and of `loss` (the step's 0-dim loss tensor) behind an event, and return.  sec: the caller's seconds for this window."""
+        if len(items) != 22 or items[9] < 0:
+            raise ValueError("TrainLog.after: not a window's yield")
+        x, s, e = items[0], int(items[5]), int(items[6])
+        gru_vae._need_cuda(x, "TrainLog.after(batch_src)")
+        if len(trajs) != self.n_cyc:
+            raise ValueError("TrainLog.after: %d cycles of trajectories, n_cyc = %d" % (len(trajs), self.n_cyc))
+        while sum(1 for q in self._pending if q[0] == "win") >= self.MAX_IN_FLIGHT:                   # as the step does
+            self._pending[0][1].synchronize()
+            self.poll()
+        B, F, Cin = x.shape
+        T, L, sd = e - s + 1, self.lat_dim, self.stdim
+        D = Cin - sd
+        dev = x.device
+        if x.dtype != torch.float32 or not x.is_contiguous():
+            raise ValueError("TrainLog.after: batch_src must be a contiguous float32 tensor")
+        if not 0 <= s <= e < F:
+            raise ValueError("TrainLog.after: window %d .. %d outside the %d frames of batch_src" % (s, e, F))
+        a = _cabi.TrainlogWindowArgs()
+        keep = []
+        for i, tr in enumerate(trajs):
+            for k, name in enumerate(_cabi.TRAINLOG_SLOTS):
+                t = tr[name].detach()
+                want = (B, T, 2 * L if name in ("lat", "latcv") else D)
+                if tuple(t.shape) != want or t.dtype != torch.float32:
+                    raise ValueError("trajectory %s of cycle %d has shape %s, expected %s" % (name, i, tuple(t.shape), want))
+                t = t.contiguous()
+                keep.append(t)
+                a.traj[i][k] = t.data_ptr()
+        if self._fresh or self._acc is None or self._acc["cv"].shape[:2] != (B, F):                   # :1349-1353
+            self._acc = {"rec": torch.zeros(B, F, D, dtype=torch.float32, device=dev), "cv": torch.zeros(B, F, D, dtype=torch.float32, device=dev),
+                         "reccyc": torch.zeros(B, F, D, dtype=torch.float32, device=dev), "lat": torch.zeros(B, F, 2 * L, dtype=torch.float32, device=dev)}
+        spc = items[11]
+        if spc.dtype != torch.int64 or not spc.is_contiguous() or spc.shape[0] != B:
+            raise ValueError("TrainLog.after: spcidx_src must be a contiguous int64 tensor of %d rows" % B)
+        sel = np.zeros(B, np.uint8)
+        sel_list = [int(j) for j in items[19]]
+        sel[sel_list] = 1
+        host = [np.ascontiguousarray(np.asarray(items[20]), np.int32), np.ascontiguousarray(np.asarray(items[7]), np.int32),
+                np.ascontiguousarray(np.asarray(items[8]), np.int32), sel]
+        if any(h.shape != (B,) for h in host):
+            raise ValueError("TrainLog.after: the generator's bookkeeping does not hold %d utterances" % B)
+        n = self.n_cyc * B * _cabi.TRAINLOG_REC
+        rec = torch.empty(n + 1, dtype=torch.float64, device=dev)
+        a.x_win, a.x_row_stride, a.x_utt_stride = x.data_ptr() + 4 * s * Cin, Cin, F * Cin
+        a.spcidx, a.spc_ld = spc.data_ptr(), spc.shape[1]
+        a.flen_acc, a.s_idx, a.e_idx, a.selected = (h.ctypes.data for h in host)
+        a.n_cyc, a.B, a.T, a.D, a.L, a.stdim, a.src_idx_s, a.acc_rows = self.n_cyc, B, T, D, L, sd, s, F
+        for q, k in enumerate(("rec", "cv", "reccyc", "lat")):
+            a.acc[q] = self._acc[k].data_ptr()
+        a.rec_out = rec.data_ptr()
+        gru_vae._lib().trainlog_window(a, gru_vae._stream())
+        self.last_args = (a, keep, host)       # (kept: the argument block of the latest launch and what it points to, for tools/trainlog_timing.py)
+        self.last_record = rec[:n].view(self.n_cyc, B, _cabi.TRAINLOG_REC)
+        self._prev, self._prev_featfile = items, list(items[13])                                      # :1354
+        if not sel_list:                                                                              # :1356: no loss, no step, no line
+            return
+        rec[n:].copy_(loss.detach().reshape(1))
+        slot = self._pinned(n + 1)
+        ev = self._behind(rec, slot)
+        meta = dict(B=B, sel=sel_list, spoken=[j for j in sel_list if int(host[1][j]) >= 0], files=list(items[13]), c_idx=int(items[9]),
+                    sec=sec, keep=keep)
+        self._pending.append(("win", ev, slot, meta))
+        self.iter_idx += 1
+        self.iter_count += 1
+
+    # ---- the host half: whatever has arrived, oldest first -----------------------------------------------------------------------
+    def poll(self):
+        """Take the finished slots, oldest first, into the lists and the text lines; stops at the first one still in flight.
+        Returns the number of slots taken."""
+        n = 0
+        while self._pending and self._pending[0][1].query():
+            kind, _, slot, meta = self._pending.pop(0)
+            (self._take_window if kind == "win" else self._take_close)(slot.numpy().copy(), meta)
+            self._free.setdefault(slot.numel(), []).append(slot)
+            n += 1
+        return n
+
+    def lines(self):
+        """The text lines that have become available since the last call, in the script's order."""
+        self.poll()
+        out, self._lines = self._lines, []
+        return out
+
+    def _take_close(self, host, meta):
+        W = meta["where"]
+        for j in range(meta["gv_rows"]):                                                              # :1341-1348
+            names = GV_SRC if self._is_src(meta["gv_files"][j]) else GV_TRG
+            for n, k in zip(names, ("rec", "cv", "reccyc")):
+                at = W[("gv", k, j)]
+                self.lists[n][0].append(host[at:at + meta["D"] - 1].copy())
+        for j in range(meta["n_close"]):                                                              # :689-704
+            v = lambda n: float(host[W[(n, j)]])
+            vals = (v("mcdpow"), v("mcd"), (v("ld_a") + v("ld_b")) / 2, (v("cd_a") + v("cd_b")) / 2)
+            src = self._is_src(meta["files"][j])
+            for n, x in zip(CLOSE_SRC if src else CLOSE_TRG, vals):
+                self.lists[n][0].append(x)
+            self._lines.append("batch %s loss %s %s = %.3f dB %.3f dB , %.3f %.3f" % (
+                ("srctrg" if src else "trgsrc", meta["files"][j], meta["files_trg"][j]) + vals))
+
+    def _take_window(self, host, meta):
+        B, sel, spoken = meta["B"], meta["sel"], meta["spoken"]
+        R = host[:-1].reshape(self.n_cyc, B, _cabi.TRAINLOG_REC)
+        loss = float(host[-1])
+        means = []
+        for i in range(self.n_cyc):
+            for j in sel:                                                                             # :1373-1386
+                for n, q in zip(WIN_SRC if self._is_src(meta["files"][j]) else WIN_TRG, range(5)):
+                    self.lists[n][i].append(float(R[i, j, q]))
+            kl, klcv = [R[i, j, 3] for j in sel], [R[i, j, 4] for j in sel]
+            # :1393: with more than one selected utterance the script rebuilds the lat_src_cv list from the lat_src list
+            # (stage4.script_loss_loop): KL(lat) of every utterance and KL(latcv) of the LAST one
+            cvlist = klcv if len(sel) == 1 else kl + [klcv[-1]]
+            means.append((_mean([R[i, j, 0] for j in sel]), _mean([R[i, j, 1] for j in sel]), _mean([R[i, j, 2] for j in sel]),
+                          _mean(kl), _mean(cvlist)))                                                  # :1412-1416
+        self.loss.append(loss)                                                                        # :1422
+        for j in spoken:                                                                              # :1431-1458
+            for i in range(self.n_cyc):
+                for n, q in zip(DB_SRC if self._is_src(meta["files"][j]) else DB_TRG, (5, 6, 7, 8)):
+                    self.lists[n][i].append(float(R[i, j, q]))
+        text = "%.3f ;; " % loss                                                                      # :1460-1471 (print_mcd_flag = bool(spoken))
+        for i in range(self.n_cyc):
+            text += "[%d] %.3f %.3f %.3f ; %.3f %.3f " % ((i + 1,) + means[i])
+            if spoken:
+                text += "; %.3f dB %.3f dB , %.3f dB %.3f dB " % tuple(_mean([R[i, j, q] for j in spoken]) for q in (5, 6, 7, 8))
+            text += ";; "
+        line = "batch loss [%d] = %s" % (meta["c_idx"] + 1, text)                                     # :1472
+        if meta["sec"] is not None:
+            line += "  (%.3f sec)" % meta["sec"]
+            self.total.append(float(meta["sec"]))
+        self._lines.append(line)
+
+    # ---- :719-739 ----------------------------------------------------------------------------------------------------------------
+    def epoch_end(self):
+        """Wait for everything in flight; the epoch's figures under the reference's names (n_ev_cyc = 1: the lists of cycle 1) --
+        "loss", the means of the ten loss lists, of the twelve dB lists and of the four latent distances, mcdpowstd_* / mcdstd_* of
+        the two conversions, eval_gv_* -- and "line", the "(EPOCH:%d) average optimization loss" text.  Then the resets of :1202-1269.
+        Lines not yet fetched stay available through lines()."""
+        while self._pending:
+            self._pending[0][1].synchronize()
+            self.poll()
+        l0 = lambda n: self.lists[n][0]
+        s = {"loss": _mean(self.loss)}
+        for n in WIN_SRC + WIN_TRG + DB_SRC + DB_TRG + CLOSE_SRC + CLOSE_TRG:
+            s[n] = _mean(l0(n))
+        for n in ("mcdpow_trg_src", "mcd_trg_src", "mcdpow_src_trg", "mcd_src_trg"):
+            s[n.replace("_", "std_", 1)] = _std(l0(n))
+        for g in GV_SRC + GV_TRG:                                   # a conversion INTO a speaker is held against that speaker's statistics
+            ref = self.gv_trg_mean if g in ("gv_trg_trg", "gv_src_trg", "gv_trg_src_trg") else self.gv_src_mean
+            s["eval_" + g] = float(np.mean(np.sqrt(np.square(np.log(np.mean(l0(g), axis=0)) - np.log(ref))))) if l0(g) else float("nan")
+        text = "%.3f ;; " % s["loss"] + EPOCH_FMT % ((1,) + tuple(s[n] for n in EPOCH_ORDER))
+        line = "(EPOCH:%d) average optimization loss = %s" % (self.epoch_idx + 1, text)
+        if self.total:
+            line += "  (%.3f min., %.3f sec / batch)" % (np.sum(self.total) / 60.0, np.mean(self.total))
+        s["line"] = line
+        self._reset()
+        self.epoch_idx += 1
+        return s

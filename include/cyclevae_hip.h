@@ -822,6 +822,48 @@ typedef struct cvae_decode_job {
 } cvae_decode_job;
 int cvae_decode_jobs(cvae_ctx* ctx, const cvae_decode_job* jobs, int n_jobs, void* work, size_t work_bytes, void* stream);
 
+/*
+ * The per-window half of the stage-4 training log (train_gru_cyclevae_gauss_batch.py:1364-1371, :1431-1439, and the buffers of
+ * :1312-1316 / :1349-1353): ONE launch per frame window (one per CVAE_TRAINLOG_MAX_UTT utterances), one block per (cycle i,
+ * utterance j), f64 arithmetic on the fp32 trajectories, every reduction a fixed-order tree: a record does not depend on the grid
+ * nor on the other utterances of the call.  The call reads the four HOST arrays before it returns, copies nothing and waits for
+ * nothing: the generator's bookkeeping travels as kernel arguments.
+ *   traj[i]      the five trajectories of cycle i as stage4.chain_forward returns them, contiguous fp32 device arrays:
+ *                [0] lat [B][T][2L], [1] rec [B][T][D], [2] cv [B][T][D], [3] latcv [B][T][2L], [4] reccyc [B][T][D]
+ *   x_win        batch_src[0][src_idx_s]: the window's T rows of every utterance, row stride x_row_stride >= stdim + D floats,
+ *                utterance stride x_utt_stride; the target of a frame is its columns stdim .. stdim + D - 1
+ *   spcidx       [B][spc_ld] int64 device: the utterances' speech-frame indices
+ *   selected, flen_acc, s_idx, e_idx    HOST [B]: select_utt_idx as a 0/1 array, and the generator's flen_acc, spcidx_src_s_idx,
+ *                spcidx_src_e_idx
+ * rec_out [n_cyc][B][9] f64 device:
+ *   [0..4]  utterance selected and n = min(flen_acc[j], T) > 0: the means over the window's frames 0 .. n-1 of
+ *           (10/ln10) sqrt2 sum_d |y[t][d] - x[t][stdim + d]| for y = rec, reccyc, cv   (criterion_mcd(L2=False, GV=False), :1366-1368)
+ *           and of 0.5 sum_l (exp(s) + mu^2 - s - 1) for lat, latcv                        (loss_vae, :1370-1371); else NaN
+ *   [5..8]  utterance selected, s_idx[j] >= 0: with f_k = spcidx[j][s_idx[j] + k], k <= e_idx[j] - s_idx[j], r_k = f_k - src_idx_s,
+ *           the means over k of (10/ln10) sqrt(2 sum_{d >= d0} (x[r_k][stdim + d] - y[r_k][d])^2) for (y, d0) = (rec, 0), (rec, 1),
+ *           (reccyc, 0), (reccyc, 1): dtw_c.calc_mcd as oracle.mcd_aligned defines it (PARITY UNPINNED), :1435-1439.  An r_k outside
+ *           0 .. T-1 or an e_idx outside the index rows gives the utterance's four figures NaN instead of a read there; else NaN
+ * acc: all NULL, or the four utterance-long buffers [B][acc_rows][D] (rec, cv, reccyc) and [B][acc_rows][2L] (lat): the blocks of
+ *   cycle 0 copy the window's T rows of EVERY utterance to rows src_idx_s .. src_idx_s + T - 1 (refused when they do not fit).
+ */
+#define CVAE_TRAINLOG_MAX_CYC 8
+#define CVAE_TRAINLOG_MAX_UTT 128
+typedef struct cvae_trainlog_window_args {
+    const float* traj[CVAE_TRAINLOG_MAX_CYC][5];
+    const float* x_win;
+    int64_t x_row_stride, x_utt_stride;
+    const int64_t* spcidx;
+    int64_t spc_ld;
+    const int32_t* flen_acc;
+    const int32_t* s_idx;
+    const int32_t* e_idx;
+    const uint8_t* selected;
+    int32_t n_cyc, B, T, D, L, stdim, src_idx_s, acc_rows;
+    float* acc[4];
+    double* rec_out;
+} cvae_trainlog_window_args;
+int cvae_trainlog_window(cvae_ctx* ctx, const cvae_trainlog_window_args* a, void* stream);
+
 /* Copy status words (int32[4]) of a workspace to the host; synchronises `stream`.  status[0]!=0 = barrier timeout;
  * status[3] == CVAE_STATUS_RANGE: the latest call on this workspace met an operand outside the limb window (no sink set). */
 int cvae_workspace_status(cvae_ctx* ctx, const void* workspace, int32_t status_out[4], void* stream);
