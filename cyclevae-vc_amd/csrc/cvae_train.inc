@@ -227,6 +227,7 @@ static const long GEMM_PART_FLOATS = 16L << 20;   // partial tiles of row-split 
 static const long GEMM_CNT = 4096;                // arrival counters (one per output tile) of a split GEMM, combined in the launch
 static const int BWD_KS = 8;       // K slices of the per-step backward products (k_bwd_step_gemm)
 static const int BWD_KS_MAX = 32;  // (the partial-sum area is sized for this many; option bwd_ks)
+static const int BWD_NTN = 1;      // 16-column tiles per block of k_bwd_step_gemm (the launch refuses an H / 16 that is no multiple of it)
 
 struct TScratch {   // shared by all passes, contents need not survive a call
     long gi, hbuf, obuf, dy, tflags, tprof, dyl, dytot, dyfb, dh, bpart, gpart, dgi, dgh, dc1p, dc0p, dxn, tmpw, gx, dovl, bflags, gpart2,
@@ -1099,11 +1100,15 @@ int cvae_gru_rnn_backward(cvae_ctx* ctx, const cvae_net_desc* d, const void* ima
                 gq.dgh = S + sl.dghc;      // (the chunk-major copy k_gru_step_bwd just wrote)
                 gq.dgi = S + sl.dgic;
                 const int KSr = opt(OPT_BWD_KS) >= 1 && opt(OPT_BWD_KS) <= BWD_KS_MAX ? (int)opt(OPT_BWD_KS) : BWD_KS;
-                const dim3 g((m.H + m.Cop) / 16, KSr, nblk(nt16, NRTB));
-                const size_t lds = (size_t)4 * NRTB * 16 * 20 * sizeof(float);
-                if (NRTB == 4) hipLaunchKernelGGL((k_bwd_step_gemm<4, 1>), g, dim3(256), lds, st, gq);
-                else if (NRTB == 2) hipLaunchKernelGGL((k_bwd_step_gemm<2, 1>), g, dim3(256), lds, st, gq);
-                else hipLaunchKernelGGL((k_bwd_step_gemm<1, 1>), g, dim3(256), lds, st, gq);
+                // a block's BWD_NTN column tiles must lie on one side of the H boundary (it reads dgh OR dgi): any H / 16 with one tile
+                if (m.nch % BWD_NTN)
+                    return fail(-1, "k_bwd_step_gemm with %d column tiles per block needs hidden / 16 to be a multiple of it, got hidden %d",
+                                BWD_NTN, m.H);
+                const dim3 g(nblk((m.H + m.Cop) / 16, BWD_NTN), KSr, nblk(nt16, NRTB));
+                const size_t lds = (size_t)4 * BWD_NTN * NRTB * 16 * 20 * sizeof(float);
+                if (NRTB == 4) hipLaunchKernelGGL((k_bwd_step_gemm<4, BWD_NTN>), g, dim3(256), lds, st, gq);
+                else if (NRTB == 2) hipLaunchKernelGGL((k_bwd_step_gemm<2, BWD_NTN>), g, dim3(256), lds, st, gq);
+                else hipLaunchKernelGGL((k_bwd_step_gemm<1, BWD_NTN>), g, dim3(256), lds, st, gq);
                 bp.part = S + sl.bpart; bp.nparts = KSr;
             }
         }

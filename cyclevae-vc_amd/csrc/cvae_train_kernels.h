@@ -1086,7 +1086,7 @@ __global__ __launch_bounds__(256) void k_bwd_step_gemm(BwdGemmParams p) {
     const int sl_lo = (nchk * ks) / KS, sl_hi = (nchk * (ks + 1)) / KS, nsl = sl_hi - sl_lo;
     const int c_lo = sl_lo + (nsl * wave) / 4, c_hi = sl_lo + (nsl * (wave + 1)) / 4;
     const int ntile = (H + p.Cop) >> 4, nrt = p.Bp >> 4, rt0 = blockIdx.z * NRT;
-    // a block's tiles are all on the same side of the H boundary (H / 16 is a multiple of NTN for the sizes it is built for)
+    // a block's tiles are all on the same side of the H boundary: the launch site refuses an H / 16 that is no multiple of NTN
     const int tile0 = blockIdx.x * NTN;
     const bool hid = tile0 * 16 < H;
     const float* A = hid ? p.dgh : p.dgi;

@@ -47,6 +47,17 @@ TABLE = [
     (6, 128, 2, P | E | S, 8, {}, LL),
     (6, 48, 2, P | E | S, 8, {}, GENERIC),           # LL wants H % 64 == 0
     (6, 1040, 2, P | E | S, 8, {}, PER_STEP),        # 260 blocks on 256 CUs
+    # the width classes of tests/width_util.py
+    (6, 320, 1, P | E | S, 8, {}, LL),               # wave 1 of k_gru_steps_ll with one word
+    (6, 320, 3, P | E | S, 8, {}, LL),
+    (6, 320, 4, P | E | S, 8, {}, GENERIC),          # a fourth row: off the word exchange, no tuned kernel at H = 320
+    (10, 960, 3, P | E | S, 8, {}, LL),              # wave 3 with three words
+    (10, 960, 17, P | E | S, 8, {}, GENERIC),
+    (10, 1008, 2, P | E | S, 8, {}, GENERIC),        # LL wants H % 64 == 0; 252 blocks: the largest resident grid
+    (10, 1008, 65, P | E | S, 8, {}, GENERIC),
+    (10, 1008, 65, 0, 8, {}, PER_STEP),
+    (6, 1040, 17, P | E | S, 8, {}, PER_STEP),
+    (6, 1040, 17, P | G, 8, {}, PER_STEP),           # GENERIC_STEP asks for the any-H kernel: still T launches when it is not resident
 ]
 
 
