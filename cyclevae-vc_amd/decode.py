@@ -5,7 +5,7 @@ variances, 6 mod_pow (8 distinct mc2e matrices), 3 GV post-filters and 2 differe
 logs the lists' means (:606-644).
 
 Here a call takes up to ten pairs.  Network half (:302-323): stage5.CvgvPass.network_passes, unchanged -- the statements are those
-of calc_cvgv...:179-199.  Metric half (:328-475), as in stage5.CvgvPass.metrics: one f64 arena and, whatever the number of pairs,
+of calc_cvgv...:179-199.  Metric half (:328-475), a metricplan.MetricPlan: one f64 arena and, whatever the number of pairs,
     cvae_eval_stats     GV variances of the raw trajectories, the packed f64 speech frames of the fp32 pass outputs
     cvae_mc2e_batch     round 1: mcep, mcep_trg and the three raw trajectories (5 matrices per pair)
     cvae_decode_jobs    mod_pow + GV post-filter + its variance (3 per pair), with cvmcep - mcep
@@ -31,6 +31,7 @@ import torch
 import _cabi
 import gru_vae
 import stage5
+from metricplan import MetricPlan
 
 # the script's per-utterance figures: "<name>_mean" / "<name>_std" are what it appends to its two lists per name
 MCD_NAMES = ("mcdpow_cv", "mcd_cv", "mcdpow_src_cv", "mcd_src_cv", "mcdpow_trg_cv", "mcd_trg_cv", "mcd_cvgv", "mcd_src_cvgv", "mcd_trg_cvgv")
@@ -128,135 +129,63 @@ class DecodePass(object):
         mceps = self._check_items(items)
         gru_vae._need_cuda(passes[0]["cvmcep"], "DecodePass.metrics(cvmcep)")
         dev = passes[0]["cvmcep"].device
-        f32 = lambda t: t.to(torch.float32).contiguous()
-        i64 = lambda t: t.to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
-        P = [{k: f32(p[k]) for k in PASS_NAMES} for p in passes]
+        plan = MetricPlan(dev, profile is not None)
         S = self._stat_on(dev)
-        cursor = [0]
+        is64 = lambda t: int(t.dtype == torch.float64)
 
-        def take(k):
-            at = cursor[0]
-            cursor[0] += int(k)
-            return at
-        lay = []
-        for q, (it, p, (mc_s, mc_t)) in enumerate(zip(items, P, mceps)):
-            ix_s, ix_t = i64(it[2]), i64(it[3])
-            ta, tb, ns, nt = p["cvmcep"].shape[0], p["cvmcep_trg"].shape[0], ix_s.numel(), ix_t.numel()
-            want = {"cvmcep": (ta, D), "cvmcep_src": (ta, D), "cvmcep_trg": (tb, D), "lat_src": (ta, 2 * L), "lat_trg": (tb, 2 * L),
-                    "lat_feat": (ta, L), "lat_feat_trg": (tb, L)}
-            for k, shape in want.items():      # the kernels address these by the shapes: another shape must not reach them
-                if tuple(p[k].shape) != shape:
-                    raise ValueError("pair %d: pass output %s has shape %s, expected %s" % (q, k, tuple(p[k].shape), shape))
-            if mc_s.shape[0] != ta or mc_t.shape[0] != tb:
-                raise ValueError("pair %d: mcep of %d / %d frames beside trajectories of %d / %d" % (q, mc_s.shape[0], mc_t.shape[0], ta, tb))
-            e = {"ix_s": ix_s, "ix_t": ix_t, "mc_s": mc_s, "mc_t": mc_t, "ta": ta, "tb": tb, "ns": ns, "nt": nt}
-            e["gv"] = {n: take(D - 1) for n in GV_TERMS}
-            e["ms"] = {n: take(2) for n in MCD_NAMES}
-            e["ld"] = {n: take(1) for n in ("enc_rmse_a", "enc_cos_a", "enc_rmse_b", "enc_cos_b", "pri_rmse_a", "pri_cos_a", "pri_rmse_b",
-                                            "pri_cos_b")}
-            e["junk"] = [take(1) for _ in range(7)]      # (mean costs of the mel-cd alignments: MEANSTD64 gives the means that are read)
-            lay.append(e)
-        n_out = cursor[0]
-        twf_len = 0
-        for e in lay:
-            ta, tb, ns, nt = e["ta"], e["tb"], e["ns"], e["nt"]
-            mat = lambda rows, cols: (take(rows * cols), rows, cols)
-            e["g_cv"], e["g_cvsrc"], e["g_cvtrg"] = mat(ns, D), mat(ns, D), mat(nt, D)
-            e["g_enc_s"], e["g_enc_t"], e["g_pri_s"], e["g_pri_t"] = mat(ns, 2 * L), mat(nt, 2 * L), mat(ns, L), mat(nt, L)
-            e["al_enc_st"], e["al_enc_ts"], e["al_pri_st"], e["al_pri_ts"] = mat(nt, 2 * L), mat(ns, 2 * L), mat(nt, L), mat(ns, L)
-            e["mcspc_s"], e["mcspc_t"] = mat(ns, D), mat(nt, D)                      # mcep[spcidx_src], mcepspc_trg (:278)
-            e["gg_cv"], e["gg_cvsrc"], e["gg_cvtrg"] = mat(ns, D), mat(ns, D), mat(nt, D)      # the post-filtered arrays' speech frames
-            t2s = [nt, nt, nt, ns, ns, nt, nt, ns, ns, nt, nt]      # T2 of the eleven alignments
-            e["frames"] = [take(t) for t in t2s]
-            e["twf"] = []
-            for t in t2s:
-                e["twf"].append(twf_len)
-                twf_len += t
-            e["e"] = {"mcep": take(ta), "mcep_trg": take(tb), "cvmcep": take(ta), "cvmcep_src": take(ta), "cvmcep_trg": take(tb),
-                      "cvmcep_gv": take(ta), "cvmcep_src_gv": take(ta), "cvmcep_trg_gv": take(tb)}
-            e["trj"] = {n: take((tb if "trg" in n else ta) * D) for n in TRAJ_NAMES}
-        arena = torch.empty(cursor[0], dtype=torch.float64, device=dev)
-        twf = torch.empty(twf_len, dtype=torch.int64, device=dev)
-        a0, w0 = arena.data_ptr(), twf.data_ptr()
-        A = lambda off: a0 + 8 * off
-
-        def job(kind, rows, c0, c1, a, lda, b=None, ldb=0, idx=None, dst=None, out_off=0, src_rows=0):
-            return _cabi.StatJob(kind, rows, c0, c1, src_rows, 0, a, b, lda, ldb, idx, dst, out_off)
-
-        def modpow(c, c_f64, ldc, T, e_ref, e_c, x, ref=None, diff=None, gv=None, cvgv=None, g=None, var=None):
-            rp, rf, rl = (ref.data_ptr(), int(ref.dtype == torch.float64), ref.stride(0)) if ref is not None else (None, 0, 0)
-            return _cabi.DecodeJob(_cabi.DEC_MODPOW, T, D, c_f64, rf, 0, 0, 0, c, ldc, A(e_ref), A(e_c), gv, cvgv, A(x),
-                                   None if g is None else A(g), None if var is None else A(var), None, rp, rl,
-                                   None if diff is None else A(diff), None)
+        # DecodeJob / Mc2eJob fields; the arena regions among them (Refs) become addresses behind plan.finalise()
+        def modpow(c, c_f64, T, e_ref, e_c, x, ref=None, diff=None, gv=None, cvgv=None, g=None, var=None):
+            rp, rf, rl = (ref.data_ptr(), is64(ref), ref.stride(0)) if ref is not None else (None, 0, 0)
+            return (_cabi.DEC_MODPOW, T, D, c_f64, rf, 0, 0, 0, c, D, e_ref, e_c, gv, cvgv, x, g, var, None, rp, rl, diff, None)
 
         def gather(src, src_f64, ld, src_rows, ix, dst):
-            return _cabi.DecodeJob(_cabi.DEC_GATHER, dst[1], D, src_f64, 0, src_rows, 0, D, src, ld, None, None, None, None, A(dst[0]), None,
-                                   None, None, None, 0, None, ix.data_ptr())
-        mcjob = lambda t, e_off: _cabi.Mc2eJob(t.data_ptr(), int(t.dtype == torch.float64), t.shape[0], D, 0, t.stride(0), A(e_off))
-        mcjob64 = lambda off, T, e_off: _cabi.Mc2eJob(A(off), 1, T, D, 0, D, A(e_off))
-        jobs1, jobs2, probs, mc1, mc2, dA, dG, dB = [], [], [], [], [], [], [], []
-        for e, p in zip(lay, P):
-            ns, nt, ta, tb, E, X = e["ns"], e["nt"], e["ta"], e["tb"], e["e"], e["trj"]
-            # :375, :389, :404
-            for n, k in (("cvlist", "cvmcep"), ("cvlist_src", "cvmcep_src"), ("cvlist_trg", "cvmcep_trg")):
-                jobs1.append(job(_cabi.STAT_GV, p[k].shape[0], 1, D, p[k].data_ptr(), D, out_off=e["gv"][n]))
-            # :332-333, :347-348, :363, :377, :392 -- the speech frames of the pass outputs as packed f64 matrices
-            for key, k, ix in (("g_cv", "cvmcep", "ix_s"), ("g_cvsrc", "cvmcep_src", "ix_s"), ("g_cvtrg", "cvmcep_trg", "ix_t"),
-                               ("g_enc_s", "lat_src", "ix_s"), ("g_enc_t", "lat_trg", "ix_t"), ("g_pri_s", "lat_feat", "ix_s"),
-                               ("g_pri_t", "lat_feat_trg", "ix_t")):
-                off, r, c = e[key]
-                jobs1.append(job(_cabi.STAT_GATHER64, r, 0, c, p[k].data_ptr(), c, idx=e[ix].data_ptr(), dst=A(off), src_rows=p[k].shape[0]))
+            return (_cabi.DEC_GATHER, dst.rows, D, src_f64, 0, src_rows, 0, D, src, ld, None, None, None, None, dst, None, None, None, None, 0,
+                    None, ix.data_ptr())
+        mcjob = lambda t, e: (t.data_ptr(), is64(t), t.shape[0], D, 0, t.stride(0), e)
+        mc1, mc2, dA, dG, dB, out = [], [], [], [], [], []
+        for q, (it, p, (mc_s, mc_t)) in enumerate(zip(items, passes, mceps)):
+            p, ix_s, ix_t, ta, tb = stage5.pair_inputs(plan, q, it, p, L, D)
+            if mc_s.shape[0] != ta or mc_t.shape[0] != tb:
+                raise ValueError("pair %d: mcep of %d / %d frames beside trajectories of %d / %d" % (q, mc_s.shape[0], mc_t.shape[0], ta, tb))
+            plan.hold((mc_s, mc_t))
+            # :375, :389, :404; :332-354, :363, :377, :392 -- the speech frames of the pass outputs as packed f64 matrices
+            o = stage5.pair_operands(plan, p, ix_s, ix_t, ("cvlist", "cvlist_src", "cvlist_trg"), MCD_NAMES)
+            g, ns, nt = o["g"], ix_s.numel(), ix_t.numel()
+            gv, ms = o["gv"], o["ms"]
+            gv.update((n, plan.vec(D - 1)) for n in ("cvgvlist", "cvgvlist_src", "cvgvlist_trg"))
+            E = {n: plan.mat(1, tb if "trg" in n else ta) for n in ("mcep", "mcep_trg") + TRAJ_NAMES[:6]}      # mc2e's energies
+            X = o["trj"] = {n: plan.mat(tb if "trg" in n else ta, D) for n in TRAJ_NAMES}
             # :407-415 -- mod_pow of the three trajectories; :419-422, :436-439, :453-456 -- the post-filter of its result
-            mc1 += [mcjob(e["mc_s"], E["mcep"]), mcjob(e["mc_t"], E["mcep_trg"])]
-            for k, ref, er, T, gv, cg in (("cvmcep", e["mc_s"], "mcep", ta, "gv_mean_trg", "cvgv_mean"),
-                                          ("cvmcep_src", e["mc_s"], "mcep", ta, "gv_mean_src", "cvgvsrc_mean"),
-                                          ("cvmcep_trg", e["mc_t"], "mcep_trg", tb, "gv_mean_trg", "cvgvtrg_mean")):
+            mc1 += [mcjob(mc_s, E["mcep"]), mcjob(mc_t, E["mcep_trg"])]
+            for k, ref, er, T, gm, cg in (("cvmcep", mc_s, "mcep", ta, "gv_mean_trg", "cvgv_mean"),
+                                          ("cvmcep_src", mc_s, "mcep", ta, "gv_mean_src", "cvgvsrc_mean"),
+                                          ("cvmcep_trg", mc_t, "mcep_trg", tb, "gv_mean_trg", "cvgvtrg_mean")):
                 kg, first = k + "_gv", k == "cvmcep"
                 mc1.append(mcjob(p[k], E[k]))
-                dA.append(modpow(p[k].data_ptr(), 0, D, T, E[er], E[k], X[k], ref=ref if first else None,
+                dA.append(modpow(p[k].data_ptr(), 0, T, E[er], E[k], X[k], ref=ref if first else None,
                                  diff=X["mc_cv_diff_nogv"] if first else None,                                   # :470
-                                 gv=S[gv].data_ptr(), cvgv=S[cg].data_ptr(), g=X[kg], var=e["gv"][k.replace("cvmcep", "cvgvlist")]))
+                                 gv=S[gm].data_ptr(), cvgv=S[cg].data_ptr(), g=X[kg], var=gv[k.replace("cvmcep", "cvgvlist")]))
                 # :432, :449, :466 -- mod_pow of the post-filtered array, in place
-                mc2.append(mcjob64(X[kg], T, E[kg]))
-                dB.append(modpow(A(X[kg]), 1, D, T, E[er], E[kg], X[kg], ref=ref if first else None,
+                mc2.append((X[kg], 1, T, D, 0, D, E[kg]))
+                dB.append(modpow(X[kg], 1, T, E[er], E[kg], X[kg], ref=ref if first else None,
                                  diff=X["mc_cv_diff"] if first else None))                                       # :474
             # :377 mcep[spcidx_src], :278 mcepspc_trg, :424 / :441 / :458 the post-filtered arrays at the speech frames
-            f64 = lambda t: int(t.dtype == torch.float64)
-            dG += [gather(e["mc_s"].data_ptr(), f64(e["mc_s"]), e["mc_s"].stride(0), ta, e["ix_s"], e["mcspc_s"]),
-                   gather(e["mc_t"].data_ptr(), f64(e["mc_t"]), e["mc_t"].stride(0), tb, e["ix_t"], e["mcspc_t"]),
-                   gather(A(X["cvmcep_gv"]), 1, D, ta, e["ix_s"], e["gg_cv"]),
-                   gather(A(X["cvmcep_src_gv"]), 1, D, ta, e["ix_s"], e["gg_cvsrc"]),
-                   gather(A(X["cvmcep_trg_gv"]), 1, D, tb, e["ix_t"], e["gg_cvtrg"])]
-
-            def prob(org, trg_, k, mcd, aligned=None, mean=None, c0=0):
-                """org / trg_: (address, rows, columns) of packed f64 matrices; c0: the first compared column"""
-                (oa, r1, c), (ta_, r2, _) = org, trg_
-                return _cabi.DtwProblem(oa + 8 * c0, ta_ + 8 * c0, c, c, r1, r2, c - c0, mcd, None if aligned is None else A(aligned[0]),
-                                        w0 + 8 * e["twf"][k], A(e["frames"][k]), A(mean))
-            at = lambda m: (A(m[0]), m[1], m[2])
-            mct, g_cv = at(e["mcspc_t"]), at(e["g_cv"])
-            J, ld = e["junk"], e["ld"]
-            probs += [prob(g_cv, mct, 0, -1, None, J[0]), prob(g_cv, mct, 1, -1, None, J[1], c0=1)]          # :363-364
-            for tag, gs, gt, al_st, al_ts, j0, k0 in (("enc", e["g_enc_s"], e["g_enc_t"], e["al_enc_st"], e["al_enc_ts"], 2, 2),      # :334-339
-                                                      ("pri", e["g_pri_s"], e["g_pri_t"], e["al_pri_st"], e["al_pri_ts"], 4, 6)):    # :349-354
-                probs += [prob(at(gs), at(gt), k0, -1, al_st, J[j0]), prob(at(gt), at(gs), k0 + 1, 0, None, ld[tag + "_cos_a"]),
-                          prob(at(gt), at(gs), k0 + 2, -1, al_ts, J[j0 + 1]), prob(at(gs), at(gt), k0 + 3, 0, None, ld[tag + "_cos_b"])]
-                # :335, :338, :350, :353
-                jobs2.append(job(_cabi.STAT_LATDIST, gt[1], 0, gt[2], A(al_st[0]), gt[2], A(gt[0]), gt[2], out_off=ld[tag + "_rmse_a"]))
-                jobs2.append(job(_cabi.STAT_LATDIST, gs[1], 0, gs[2], A(al_ts[0]), gs[2], A(gs[0]), gs[2], out_off=ld[tag + "_rmse_b"]))
-            probs.append(prob(at(e["gg_cv"]), mct, 10, -1, None, J[6], c0=1))                                   # :424
-            # :365-368, :425-426 -- mean and np.std of the three mel-cepstrum alignments' frame costs
-            for n, k in (("mcdpow_cv", 0), ("mcd_cv", 1), ("mcd_cvgv", 10)):
-                jobs2.append(job(_cabi.STAT_MEANSTD64, nt, 0, 1, A(e["frames"][k]), 1, out_off=e["ms"][n], src_rows=nt))
+            mcspc_s, mcspc_t = plan.mat(ns, D), plan.mat(nt, D)
+            gg = {k: plan.mat(nt if "trg" in k else ns, D) for k in ("cvmcep", "cvmcep_src", "cvmcep_trg")}
+            dG += [gather(mc_s.data_ptr(), is64(mc_s), mc_s.stride(0), ta, ix_s, mcspc_s),
+                   gather(mc_t.data_ptr(), is64(mc_t), mc_t.stride(0), tb, ix_t, mcspc_t)]
+            dG += [gather(X[k + "_gv"], 1, D, tb if "trg" in k else ta, ix_t if "trg" in k else ix_s, gg[k]) for k in gg]
+            # :363-368, :424-426 -- the three mel-cepstrum alignments; mean and np.std of their frame costs
+            for n, org, c0 in (("mcdpow_cv", g["cvmcep"], 0), ("mcd_cv", g["cvmcep"], 1), ("mcd_cvgv", gg["cvmcep"], 1)):
+                frames = plan.align(org, mcspc_t, -1, c0=c0)
+                plan.stat(2, _cabi.STAT_MEANSTD64, nt, 0, 1, frames, 1, out=ms[n], src_rows=nt)
             # :377-378, :392-393, :441, :458 -- calc_mcd(mcep at the speech frames, reconstruction at the speech frames)
-            for n, mc, g, c0 in (("mcdpow_src_cv", e["mcspc_s"], e["g_cvsrc"], 0), ("mcd_src_cv", e["mcspc_s"], e["g_cvsrc"], 1),
-                                 ("mcdpow_trg_cv", e["mcspc_t"], e["g_cvtrg"], 0), ("mcd_trg_cv", e["mcspc_t"], e["g_cvtrg"], 1),
-                                 ("mcd_src_cvgv", e["mcspc_s"], e["gg_cvsrc"], 1), ("mcd_trg_cvgv", e["mcspc_t"], e["gg_cvtrg"], 1)):
-                jobs2.append(job(_cabi.STAT_MCD64, g[1], c0, D, A(mc[0]), D, A(g[0]), D, out_off=e["ms"][n], src_rows=g[1]))
-        n1, n2 = len(jobs1), len(jobs2)
-        raw = bytes((_cabi.StatJob * (n1 + n2))(*(jobs1 + jobs2)))
-        jdev = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(dev)
-        dtw_bytes = lib.dtw_batch_work_bytes(len(probs), max(p.T1 for p in probs), max(p.T2 for p in probs))
+            for n, mc, r, c0 in (("mcdpow_src_cv", mcspc_s, g["cvmcep_src"], 0), ("mcd_src_cv", mcspc_s, g["cvmcep_src"], 1),
+                                 ("mcdpow_trg_cv", mcspc_t, g["cvmcep_trg"], 0), ("mcd_trg_cv", mcspc_t, g["cvmcep_trg"], 1),
+                                 ("mcd_src_cvgv", mcspc_s, gg["cvmcep_src"], 1), ("mcd_trg_cvgv", mcspc_t, gg["cvmcep_trg"], 1)):
+                plan.stat(2, _cabi.STAT_MCD64, r.rows, c0, D, mc, D, r, D, out=ms[n], src_rows=r.rows)
+            out.append(o)
+        dtw_bytes = plan.dtw_work_bytes()
         mc_bytes = lib.mc2e_batch_work_bytes(len(mc1), D, self.irlen)
         if mc_bytes == 0:
             raise _cabi.CvaeError("cvae_mc2e_batch_work_bytes: bad arguments (D=%d, irlen=%d)" % (D, self.irlen))
@@ -264,49 +193,35 @@ class DecodePass(object):
         up = lambda v: (v + 255) // 256 * 256
         parts = [dtw_bytes, mc_bytes, len(dA) * dj, len(dG) * dj, len(dB) * dj]
         offs = np.concatenate([[0], np.cumsum([up(v) for v in parts])])
-        work = torch.empty(int(offs[-1]), dtype=torch.uint8, device=dev)
+        work = plan.hold(torch.empty(int(offs[-1]), dtype=torch.uint8, device=dev))
         W = lambda k: work.data_ptr() + int(offs[k])
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(9)] if profile is not None else None
-        mark = (lambda k: ev[k].record()) if ev else (lambda k: None)
-        mark(0)
-        lib.eval_stats(jdev.data_ptr(), n1, a0, st)
-        mark(1)
+        plan.finalise(work=W(0))
+        mc1, mc2 = ([_cabi.Mc2eJob(*plan.resolve(f)) for f in jobs] for jobs in (mc1, mc2))
+        dA, dG, dB = ([_cabi.DecodeJob(*plan.resolve(f)) for f in jobs] for jobs in (dA, dG, dB))
+        plan.begin()
+        plan.stats(1)
         lib.mc2e_batch(mc1, self.mcep_alpha, self.irlen, W(1), mc_bytes, st)
-        mark(2)
+        plan.mark("mc2e_1")
         lib.decode_jobs(dA, W(2), parts[2], st)
         lib.decode_jobs(dG, W(3), parts[3], st)
-        mark(3)
-        lib.dtw_batch(probs, W(0), dtw_bytes, st)
-        mark(4)
+        plan.mark("modpow")
+        plan.dtw()
         lib.mc2e_batch(mc2, self.mcep_alpha, self.irlen, W(1), mc_bytes, st)
-        mark(5)
+        plan.mark("mc2e_2")
         lib.decode_jobs(dB, W(4), parts[4], st)
-        mark(6)
-        lib.eval_stats(jdev.data_ptr() + n1 * C.sizeof(_cabi.StatJob), n2, a0, st)
-        mark(7)
-        host = arena[:n_out].cpu().numpy()          # the ONE D2H copy (waits for the stream)
-        if ev:
-            ms = lambda a, b: ev[a].elapsed_time(ev[b])
-            profile.update(stats=ms(0, 1) + ms(6, 7), mc2e_1=ms(1, 2), modpow=ms(2, 3) + ms(5, 6), dtw=ms(3, 4), mc2e_2=ms(4, 5),
-                           frames_1=sum(j.T for j in mc1), frames_2=sum(j.T for j in mc2), problems=len(probs),
-                           jobs=n1 + n2 + len(dA) + len(dG) + len(dB))
+        plan.mark("modpow")
+        plan.stats(2)
+        host = plan.results().cpu().numpy()          # the ONE D2H copy (waits for the stream)
+        if profile is not None:
+            t = plan.times()
+            profile.update(stats=t["stats1"] + t["stats2"], mc2e_1=t["mc2e_1"], modpow=t["modpow"], dtw=t["dtw"], mc2e_2=t["mc2e_2"],
+                           frames_1=sum(j.T for j in mc1), frames_2=sum(j.T for j in mc2), problems=len(plan.probs),
+                           jobs=len(plan.table) + len(dA) + len(dG) + len(dB))
         gru_vae.check_status()
         res = []
-        for e in lay:
-            r = {n: arena[off:off + (e["tb"] if "trg" in n else e["ta"]) * D].view(-1, D) for n, off in e["trj"].items()}
-            for n, off in e["gv"].items():
-                r[n] = host[off:off + D - 1].copy()
-            for n, off in e["ms"].items():
-                r[n + "_mean"], r[n + "_std"] = float(host[off]), float(host[off + 1])
-            v = {n: float(host[off]) for n, off in e["ld"].items()}
-            for tag in ("enc", "pri"):                                                           # :341-342, :356-357
-                r["lat_dist_rmse_" + tag] = (v[tag + "_rmse_a"] + v[tag + "_rmse_b"]) / 2
-                r["lat_dist_cosim_" + tag] = (v[tag + "_cos_a"] + v[tag + "_cos_b"]) / 2
-            # calc_mcd's means are NaN exactly when a gathered row is (an index outside the utterance, or a NaN trajectory): an
-            # alignment may step around such a row, so its figures are withdrawn here rather than trusted
-            if not (np.isfinite(r["mcdpow_src_cv_mean"]) and np.isfinite(r["mcdpow_trg_cv_mean"])):
-                for n in MCD_TERMS + DIST_TERMS:
-                    r[n] = float("nan")
+        for o in out:
+            r = {n: plan.view(x) for n, x in o["trj"].items()}
+            r.update(stage5.pair_figures(host, o, MCD_TERMS, ("mcdpow_src_cv", "mcdpow_trg_cv")))
             res.append(r)
         return res
 

@@ -7,7 +7,7 @@ and calls the host library dtw_c ten times.
 Here a call takes up to ten pairs.  Network half (:179-199): the 2N encoder rows as one stacked pass (stage6._encode_pairs), ONE
 cvae_latent_mean launch for all 2N n_smpl_dec-draw means lat_feat, the 3N decoder rows as one stacked pass whose cells read
 lat_feat as a plain input segment -- the mean is formed once and read by both the decoder and the statistics, as in the script.
-Metric half (:203-283), as in validation.ValidationPass.metrics: one f64 arena, cvae_eval_stats (GV variances, packed f64 DTW
+Metric half (:203-283), a metricplan.MetricPlan: one f64 arena, cvae_eval_stats (GV variances, packed f64 DTW
 operands), one cvae_dtw_batch (ten alignments per pair), cvae_eval_stats again (mean / std of the DTW frame costs, calc_mcd's
 mean / std, the latent distances of the aligned sequences) and ONE D2H copy.  The number of library calls does not depend on N,
 and every figure of a pair is one block's fixed-order reduction: it does not depend on which call the pair lands in.
@@ -17,18 +17,18 @@ is the written definition at oracle/cyclevae_oracle.py::dtw_org_to_trg / mcd_ali
 validation.ValidationPass.  The GV variances are exact counterparts: the script casts the trajectory to float64 before np.var
 (:195).  Out of scope: the multi-device fan-out of :120-123 (stage6.split_file_list gives the chunks), mod_pow.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
 import _cabi
 import gru_vae
 import stage6
+from metricplan import MetricPlan
 
 # per-pair scalars, under the script's names (:212-282)
 MCD_TERMS = ("mcdpow_mean", "mcdpow_std", "mcd_mean", "mcd_std", "mcdpow_src_mean", "mcdpow_src_std", "mcd_src_mean", "mcd_src_std",
              "mcdpow_trg_mean", "mcdpow_trg_std", "mcd_trg_mean", "mcd_trg_std")
+MS_NAMES = ("mcdpow", "mcd", "mcdpow_src", "mcd_src", "mcdpow_trg", "mcd_trg")      # MCD_TERMS are these with _mean / _std
 DIST_TERMS = ("lat_dist_rmse_enc", "lat_dist_cosim_enc", "lat_dist_rmse_pri", "lat_dist_cosim_pri")
 GV_TERMS = ("cvgv", "cvgvsrc", "cvgvtrg")                      # np.var(traj[:, 1:], 0) of cvmcep, cvmcep_src, cvmcep_trg (:203-205)
 # what last_passes holds: the five trajectories of stage6.convert_pairs and the two latent means, per pair
@@ -39,6 +39,60 @@ MAX_PAIRS = 10                                                   # 3N decoder ro
 def dataset_suffix(mdl_name, n_cyc, lat_dim, iterations, spk_trg, n_smpl_dec):
     """:349's string: the six datasets are "/cvgv_mean_" + this, and so on."""
     return "%s-%s-%s-%s-%s-%s" % (mdl_name, n_cyc, lat_dim, iterations, spk_trg, n_smpl_dec)
+
+
+def pair_inputs(plan, q, item, p, L, D):
+    """Pair q's pass outputs as contiguous fp32 and its two speech-frame index lists as int64 device vectors, held by the plan;
+    refused unless every pass output has the shape the kernels address it by.  Returns (outputs, ix_src, ix_trg, Ts, Tt)."""
+    dev = p["cvmcep"].device
+    p = {k: plan.hold(p[k].to(torch.float32).contiguous()) for k in PASS_NAMES}
+    ix_s, ix_t = (plan.hold(t.to(device=dev, dtype=torch.int64).reshape(-1).contiguous()) for t in (item[2], item[3]))
+    ta, tb = p["cvmcep"].shape[0], p["cvmcep_trg"].shape[0]
+    want = {"cvmcep": (ta, D), "cvmcep_src": (ta, D), "cvmcep_trg": (tb, D), "lat_src": (ta, 2 * L), "lat_trg": (tb, 2 * L),
+            "lat_feat": (ta, L), "lat_feat_trg": (tb, L)}
+    for k, shape in want.items():      # the kernels address these by the shapes: another shape must not reach them
+        if tuple(p[k].shape) != shape:
+            raise ValueError("pair %d: pass output %s has shape %s, expected %s" % (q, k, tuple(p[k].shape), shape))
+    if ix_s.numel() < 1 or ix_t.numel() < 1:      # (stage 5's refusal: decode.DecodePass._check_items has refused this before, in its words)
+        raise ValueError("pair %d: empty speech-frame index list" % q)
+    return p, ix_s, ix_t, ta, tb
+
+
+def pair_operands(plan, p, ix_s, ix_t, gv_names, ms_names):
+    """What stages 5 and 6 both declare for a pair.  Returns the pair's regions, which pair_figures() reads:
+      "gv"  {name: result vector}: the GV variances of cvmcep, cvmcep_src, cvmcep_trg under the three gv_names (a caller with
+            further GV vectors adds them here)
+      "ms"  {name: result vector of (mean, std)} for ms_names; the caller declares the jobs that write them
+      "g"   {pass name: packed f64 matrix}: the speech frames of all seven pass outputs
+      "ld"  {"enc" / "pri": latent_distance() slots} of the encoder's and of the decoder-input latents"""
+    o = {"gv": {}, "ms": {n: plan.vec(2) for n in ms_names}, "g": {}}
+    for n, k in zip(gv_names, ("cvmcep", "cvmcep_src", "cvmcep_trg")):
+        o["gv"][n] = plan.vec(p[k].shape[1] - 1)
+        plan.stat(1, _cabi.STAT_GV, p[k].shape[0], 1, p[k].shape[1], p[k].data_ptr(), p[k].shape[1], out=o["gv"][n])
+    for k in PASS_NAMES:
+        ix, c = ix_t if k.endswith("trg") else ix_s, p[k].shape[1]
+        o["g"][k] = plan.mat(ix.numel(), c)
+        plan.stat(1, _cabi.STAT_GATHER64, ix.numel(), 0, c, p[k].data_ptr(), c, idx=ix.data_ptr(), dst=o["g"][k], src_rows=p[k].shape[0])
+    o["ld"] = {"enc": plan.latent_distance(o["g"]["lat_src"], o["g"]["lat_trg"]),
+               "pri": plan.latent_distance(o["g"]["lat_feat"], o["g"]["lat_feat_trg"])}
+    return o
+
+
+def pair_figures(host, o, mcd_terms, calc_mcd):
+    """A pair's result dict from the host copy of the results and pair_operands()'s regions: the GV vectors, "<n>_mean" / "<n>_std"
+    of o["ms"], DIST_TERMS.  calc_mcd: the o["ms"] names of one calc_mcd figure per side; mcd_terms: what is withdrawn with them."""
+    r = {n: ref.of(host) for n, ref in o["gv"].items()}
+    for n, ref in o["ms"].items():
+        r[n + "_mean"], r[n + "_std"] = float(host[ref.off]), float(host[ref.off + 1])
+    for tag, refs in o["ld"].items():                                                        # :264-265, :279-280
+        rmse_a, rmse_b, cos_a, cos_b = (float(host[x.off]) for x in refs)
+        r["lat_dist_rmse_" + tag], r["lat_dist_cosim_" + tag] = (rmse_a + rmse_b) / 2, (cos_a + cos_b) / 2
+    # calc_mcd's means are NaN exactly when a gathered row is (an index outside the utterance, or a NaN trajectory): an
+    # alignment may step around such a row, so its figures are withdrawn here rather than trusted
+    if not all(np.isfinite(r[n + "_mean"]) for n in calc_mcd):
+        for n in mcd_terms + DIST_TERMS:
+            r[n] = float("nan")
+    return r
 
 
 class CvgvPass(object):
@@ -135,139 +189,46 @@ class CvgvPass(object):
         DIST_TERMS) NaN -- the library gathers NaN rows instead of reading there; the GV vectors do not read them and stay.
         profile: a dict that receives the device milliseconds of "stats" (both statistics launches) and "dtw", and the counts "jobs",
         "problems", "work_bytes"."""
-        lib, st = gru_vae._lib(), gru_vae._stream()
         L = self.lat_dim
         if len(items) != len(passes) or not 1 <= len(items) <= MAX_PAIRS:
             raise ValueError("1..%d utterance pairs per call, got %d items and %d pass outputs" % (MAX_PAIRS, len(items), len(passes)))
         gru_vae._need_cuda(passes[0]["cvmcep"], "CvgvPass.metrics(cvmcep)")
         dev = passes[0]["cvmcep"].device
-        f32 = lambda t: t.to(torch.float32).contiguous()
-        i64 = lambda t: t.to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+        plan = MetricPlan(dev, profile is not None)
         f64 = lambda t: t.to(device=dev, dtype=torch.float64).contiguous()
-        P = [{k: f32(p[k]) for k in PASS_NAMES} for p in passes]
-        D = P[0]["cvmcep"].shape[1]
-        cursor = [0]
-
-        def take(k):
-            at = cursor[0]
-            cursor[0] += int(k)
-            return at
-        lay = []
-        for q, (it, p) in enumerate(zip(items, P)):
-            ix_s, ix_t, mc_s, mc_t = i64(it[2]), i64(it[3]), f64(it[4]), f64(it[5])
-            ta, tb, ns, nt = p["cvmcep"].shape[0], p["cvmcep_trg"].shape[0], ix_s.numel(), ix_t.numel()
-            want = {"cvmcep": (ta, D), "cvmcep_src": (ta, D), "cvmcep_trg": (tb, D), "lat_src": (ta, 2 * L), "lat_trg": (tb, 2 * L),
-                    "lat_feat": (ta, L), "lat_feat_trg": (tb, L)}
-            for k, shape in want.items():      # the kernels address these by the shapes: another shape must not reach them
-                if tuple(p[k].shape) != shape:
-                    raise ValueError("pair %d: pass output %s has shape %s, expected %s" % (q, k, tuple(p[k].shape), shape))
-            if ns < 1 or nt < 1:
-                raise ValueError("pair %d: empty speech-frame index list" % q)
-            if tuple(mc_s.shape) != (ns, D) or mc_t.dim() != 2 or mc_t.shape[1] != D or mc_t.shape[0] < 1:
+        D = passes[0]["cvmcep"].shape[1]
+        out = []
+        for q, (it, p) in enumerate(zip(items, passes)):
+            p, ix_s, ix_t, ta, tb = pair_inputs(plan, q, it, p, L, D)
+            mc_s, mc_t = plan.hold(f64(it[4])), f64(it[5])
+            if tuple(mc_s.shape) != (ix_s.numel(), D) or mc_t.dim() != 2 or mc_t.shape[1] != D or mc_t.shape[0] < 1:
                 # (:224: calc_mcd compares mcepspc_src with the ns gathered frames row by row)
                 raise ValueError("pair %d: mcepspc_src %s / mcepspc_trg %s do not fit %d speech frames of %d coefficients"
-                                 % (q, tuple(mc_s.shape), tuple(mc_t.shape), ns, D))
-            e = {"ix_s": ix_s, "ix_t": ix_t, "mc_s": mc_s, "mc_t": mc_t, "ta": ta, "tb": tb, "ns": ns, "nt": nt, "St": mc_t.shape[0]}
-            e["gv"] = [take(D - 1) for _ in GV_TERMS]
-            e["ms"] = {n: take(2) for n in ("mcdpow", "mcd", "mcdpow_src", "mcd_src", "mcdpow_trg", "mcd_trg")}
-            e["ld"] = {n: take(1) for n in ("enc_rmse_a", "enc_cos_a", "enc_rmse_b", "enc_cos_b", "pri_rmse_a", "pri_cos_a", "pri_rmse_b",
-                                            "pri_cos_b")}
-            e["junk"] = [take(1) for _ in range(6)]      # (mean costs of the mel-cd alignments: MEANSTD64 gives the means that are read)
-            lay.append(e)
-        n_out = cursor[0]
-        twf_len = 0
-        for e in lay:
-            ns, nt, St = e["ns"], e["nt"], e["St"]
-            mat = lambda rows, cols: (take(rows * cols), rows, cols)
-            e["g_cv"], e["g_cvsrc"], e["g_cvtrg"] = mat(ns, D), mat(ns, D), mat(nt, D)
-            e["g_enc_s"], e["g_enc_t"], e["g_pri_s"], e["g_pri_t"] = mat(ns, 2 * L), mat(nt, 2 * L), mat(ns, L), mat(nt, L)
-            e["al_enc_st"], e["al_enc_ts"], e["al_pri_st"], e["al_pri_ts"] = mat(nt, 2 * L), mat(ns, 2 * L), mat(nt, L), mat(ns, L)
-            t2s = [St, St, nt, ns, ns, nt, nt, ns, ns, nt]      # T2 of the ten alignments
-            e["frames"] = [take(t) for t in t2s]
-            e["twf"] = []
-            for t in t2s:
-                e["twf"].append(twf_len)
-                twf_len += t
-        arena = torch.empty(cursor[0], dtype=torch.float64, device=dev)
-        twf = torch.empty(twf_len, dtype=torch.int64, device=dev)
-        a0, w0 = arena.data_ptr(), twf.data_ptr()
-        A = lambda off: a0 + 8 * off
-
-        def job(kind, rows, c0, c1, a, lda, b=None, ldb=0, idx=None, dst=None, out_off=0, src_rows=0):
-            return _cabi.StatJob(kind, rows, c0, c1, src_rows, 0, a, b, lda, ldb, idx, dst, out_off)
-        jobs1, jobs2, probs = [], [], []
-        for e, p in zip(lay, P):
-            ns, nt = e["ns"], e["nt"]
-            # :203-205
-            for off, k in zip(e["gv"], ("cvmcep", "cvmcep_src", "cvmcep_trg")):
-                jobs1.append(job(_cabi.STAT_GV, p[k].shape[0], 1, D, p[k].data_ptr(), D, out_off=off))
-            # :210-211, :224-225, :238-239, :255-256, :270-271 -- the speech frames as packed f64 matrices
-            for key, k, ix in (("g_cv", "cvmcep", "ix_s"), ("g_cvsrc", "cvmcep_src", "ix_s"), ("g_cvtrg", "cvmcep_trg", "ix_t"),
-                               ("g_enc_s", "lat_src", "ix_s"), ("g_enc_t", "lat_trg", "ix_t"), ("g_pri_s", "lat_feat", "ix_s"),
-                               ("g_pri_t", "lat_feat_trg", "ix_t")):
-                off, r, c = e[key]
-                jobs1.append(job(_cabi.STAT_GATHER64, r, 0, c, p[k].data_ptr(), c, idx=e[ix].data_ptr(), dst=A(off), src_rows=p[k].shape[0]))
-
-            def prob(org, trg_, k, mcd, aligned=None, mean=None, c0=0):
-                """org / trg_: (address, rows, columns) of packed f64 matrices; c0: the first compared column"""
-                (oa, r1, c), (ta_, r2, _) = org, trg_
-                return _cabi.DtwProblem(oa + 8 * c0, ta_ + 8 * c0, c, c, r1, r2, c - c0, mcd, None if aligned is None else A(aligned[0]),
-                                        w0 + 8 * e["twf"][k], A(e["frames"][k]), A(mean))
-            at = lambda m: (A(m[0]), m[1], m[2])
-            mct = (e["mc_t"].data_ptr(), e["St"], D)
-            g_cv = at(e["g_cv"])
-            J, ld = e["junk"], e["ld"]
-            probs += [prob(g_cv, mct, 0, -1, None, J[0]), prob(g_cv, mct, 1, -1, None, J[1], c0=1)]          # :210-211
-            for tag, gs, gt, al_st, al_ts, j0, k0 in (("enc", e["g_enc_s"], e["g_enc_t"], e["al_enc_st"], e["al_enc_ts"], 2, 2),      # :257-262
-                                                      ("pri", e["g_pri_s"], e["g_pri_t"], e["al_pri_st"], e["al_pri_ts"], 4, 6)):    # :272-277
-                probs += [prob(at(gs), at(gt), k0, -1, al_st, J[j0]), prob(at(gt), at(gs), k0 + 1, 0, None, ld[tag + "_cos_a"]),
-                          prob(at(gt), at(gs), k0 + 2, -1, al_ts, J[j0 + 1]), prob(at(gs), at(gt), k0 + 3, 0, None, ld[tag + "_cos_b"])]
-                # :258, :261, :273, :276
-                jobs2.append(job(_cabi.STAT_LATDIST, gt[1], 0, gt[2], A(al_st[0]), gt[2], A(gt[0]), gt[2], out_off=ld[tag + "_rmse_a"]))
-                jobs2.append(job(_cabi.STAT_LATDIST, gs[1], 0, gs[2], A(al_ts[0]), gs[2], A(gs[0]), gs[2], out_off=ld[tag + "_rmse_b"]))
-            # :212-215 -- mean and np.std of the two alignments' frame costs
-            for n, k in (("mcdpow", 0), ("mcd", 1)):
-                jobs2.append(job(_cabi.STAT_MEANSTD64, e["St"], 0, 1, A(e["frames"][k]), 1, out_off=e["ms"][n], src_rows=e["St"]))
+                                 % (q, tuple(mc_s.shape), tuple(mc_t.shape), ix_s.numel(), D))
+            o = pair_operands(plan, p, ix_s, ix_t, GV_TERMS, MS_NAMES)                                       # :203-205, :257-262, :272-277
+            g, ms, St = o["g"], o["ms"], mc_t.shape[0]
+            mct = plan.f64(mc_t)
+            # :210-215 -- the two alignments with mcepspc_trg; mean and np.std of their frame costs
+            for n, c0 in (("mcdpow", 0), ("mcd", 1)):
+                frames = plan.align(g["cvmcep"], mct, -1, c0=c0)
+                plan.stat(2, _cabi.STAT_MEANSTD64, St, 0, 1, frames, 1, out=ms[n], src_rows=St)
             # :224-229, :238-243 -- calc_mcd(mcepspc, reconstruction at the speech frames), with and without coefficient 0
-            for n, mc, g in (("_src", e["mc_s"], e["g_cvsrc"]), ("_trg", e["mc_t"], e["g_cvtrg"])):
+            for n, mc, r in (("_src", mc_s, g["cvmcep_src"]), ("_trg", mc_t, g["cvmcep_trg"])):
                 for pre, c0 in (("mcdpow", 0), ("mcd", 1)):
-                    jobs2.append(job(_cabi.STAT_MCD64, g[1], c0, D, mc.data_ptr(), D, A(g[0]), D, out_off=e["ms"][pre + n],
-                                     src_rows=min(g[1], mc.shape[0])))
-        n1, n2 = len(jobs1), len(jobs2)
-        raw = bytes((_cabi.StatJob * (n1 + n2))(*(jobs1 + jobs2)))
-        jdev = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(dev)
-        work_bytes = lib.dtw_batch_work_bytes(len(probs), max(p.T1 for p in probs), max(p.T2 for p in probs))
-        work = torch.empty(work_bytes, dtype=torch.uint8, device=dev)
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if profile is not None else None
-        mark = (lambda k: ev[k].record()) if ev else (lambda k: None)
-        mark(0)
-        lib.eval_stats(jdev.data_ptr(), n1, a0, st)
-        mark(1)
-        lib.dtw_batch(probs, work.data_ptr(), work_bytes, st)
-        mark(2)
-        lib.eval_stats(jdev.data_ptr() + n1 * C.sizeof(_cabi.StatJob), n2, a0, st)
-        mark(3)
-        host = arena[:n_out].cpu().numpy()          # the ONE D2H copy (waits for the stream)
-        if ev:
-            profile.update(stats=ev[0].elapsed_time(ev[1]) + ev[2].elapsed_time(ev[3]), dtw=ev[1].elapsed_time(ev[2]), jobs=n1 + n2,
-                           problems=len(probs), work_bytes=int(work_bytes))
+                    plan.stat(2, _cabi.STAT_MCD64, r.rows, c0, D, mc.data_ptr(), D, r, D, out=ms[pre + n], src_rows=min(r.rows, mc.shape[0]))
+            out.append(o)
+        plan.finalise()
+        plan.begin()
+        plan.stats(1)
+        plan.dtw()
+        plan.stats(2)
+        host = plan.results().cpu().numpy()          # the ONE D2H copy (waits for the stream)
+        if profile is not None:
+            t = plan.times()
+            profile.update(stats=t["stats1"] + t["stats2"], dtw=t["dtw"], jobs=len(plan.table), problems=len(plan.probs),
+                           work_bytes=int(plan.work_bytes))
         gru_vae.check_status()
-        res = []
-        for e in lay:
-            r = {g: host[off:off + D - 1].copy() for g, off in zip(GV_TERMS, e["gv"])}
-            for n, off in e["ms"].items():
-                r[n + "_mean"], r[n + "_std"] = float(host[off]), float(host[off + 1])
-            v = {n: float(host[off]) for n, off in e["ld"].items()}
-            for tag in ("enc", "pri"):                                                           # :264-265, :279-280
-                r["lat_dist_rmse_" + tag] = (v[tag + "_rmse_a"] + v[tag + "_rmse_b"]) / 2
-                r["lat_dist_cosim_" + tag] = (v[tag + "_cos_a"] + v[tag + "_cos_b"]) / 2
-            # calc_mcd's means are NaN exactly when a gathered row is (an index outside the utterance, or a NaN trajectory): an
-            # alignment may step around such a row, so its figures are withdrawn here rather than trusted
-            if not (np.isfinite(r["mcdpow_src_mean"]) and np.isfinite(r["mcdpow_trg_mean"])):
-                for n in MCD_TERMS + DIST_TERMS:
-                    r[n] = float("nan")
-            res.append(r)
-        return res
+        return [pair_figures(host, o, MCD_TERMS, ("mcdpow_src", "mcdpow_trg")) for o in out]
 
     def pairs(self, items, y_in_pp, y_in_src, y_in_trg, eps=None, seed=None, first_pair_id=0):
         """One call of at most ten pairs.  items: tuples (feat_src [Ts,Cin], feat_trg [Tt,Cin], spcidx_src, spcidx_trg, mcepspc_src

@@ -8,7 +8,7 @@ encoder pass and six dtw_c.dtw_org_to_trg per utterance on host copies: a device
   per window       ONE launch (cvae_trainlog_window: nine f64 figures per cycle and utterance, and the window's rows appended to
                    four utterance-long device buffers), one asynchronous copy of the record and of the step's loss to a pinned slot
                    behind an event; the host formats the script's text when the slot has arrived (lines / poll)
-  per batch        validation.ValidationPass's machinery on the accumulated buffers: one eval-form encoder pass, GATHER64 jobs, six
+  per batch        a metricplan.MetricPlan on the accumulated buffers: one eval-form encoder pass, GATHER64 jobs, six
                    problems of cvae_dtw_batch per utterance, LATDIST jobs, the GV variances (CVAE_STAT_GV) -- again behind an event
   per epoch        epoch_end(): the figures and the line of :719-739
 
@@ -29,6 +29,7 @@ import torch
 import _cabi
 import gru_vae
 import stage4
+from metricplan import MetricPlan, batch_rows, ints, row
 
 WIN_SRC = ("loss_mcd_src_src", "loss_mcd_src_trg_src", "loss_mcd_src_trg", "loss_lat_src", "loss_lat_src_cv")      # record [0..4]
 WIN_TRG = ("loss_mcd_trg_trg", "loss_mcd_trg_src_trg", "loss_mcd_trg_src", "loss_lat_trg", "loss_lat_trg_cv")
@@ -65,10 +66,6 @@ def _mean(v):
 
 def _std(v):
     return float(np.std(v)) if len(v) else float("nan")
-
-
-def _ints(v):
-    return [int(x) for x in (v.tolist() if hasattr(v, "tolist") else v)]
 
 
 class TrainLog(object):
@@ -153,106 +150,56 @@ class TrainLog(object):
         """The figures of the utterance batch that has just ended, from its accumulators: one encoder pass, two statistics launches
         around one cvae_dtw_batch, one copy behind an event."""
         p, L, sd = self._prev, self.lat_dim, self.stdim
-        lib, st = gru_vae._lib(), gru_vae._stream()
         acc = self._acc
         dev = acc["cv"].device
         B, rows, D = acc["cv"].shape
-        cursor = [0]
-
-        def take(n):
-            at = cursor[0]
-            cursor[0] += int(n)
-            return at
-        where, jobs1, jobs2, probs = {}, [], [], []
-        job = lambda kind, rows_, c0, c1, a, lda, b=None, ldb=0, idx=None, dst=None, out_off=0, src_rows=0: _cabi.StatJob(
-            kind, rows_, c0, c1, src_rows, 0, a, b, lda, ldb, idx, dst, out_off)
-        row = lambda t, j, col=0: (t.data_ptr() + 4 * (j * t.shape[1] * t.shape[2] + col), t.shape[2])
+        plan = MetricPlan(dev)
+        plan.hold(acc)
+        where = {}
         n_close = int(p[21]) if closing else 0
-        flens = _ints(p[15])
-        for j in range(gv_rows):
+        flens = ints(p[15])
+        for j in range(gv_rows):                                                                      # :1342-1348 (float64 here)
             if not 1 <= flens[j] <= rows:
                 raise ValueError("flens_src[%d] = %d does not fit the %d accumulated frames" % (j, flens[j], rows))
             for k in ("rec", "cv", "reccyc"):
-                where[("gv", k, j)] = take(D - 1)
-        for j in range(n_close):
-            for n in ("mcdpow", "mcd", "ld_a", "ld_b", "cd_a", "cd_b", "al_a", "al_b"):
-                where[(n, j)] = take(1)
-        n_out = cursor[0]
-        lay = []
+                a, lda = row(acc[k], j)
+                where[("gv", k, j)] = plan.vec(D - 1)
+                plan.stat(1, _cabi.STAT_GV, flens[j], 1, D, a, lda, out=where[("gv", k, j)])
         if closing:
-            feat_trg = p[3].to(torch.float32).contiguous()
-            spc = p[11].to(device=dev, dtype=torch.int64).contiguous()
-            spc_trg = p[12].to(device=dev, dtype=torch.int64).contiguous()
-            ns, nsp = _ints(p[17]), _ints(p[18])
+            feat_trg = plan.hold(p[3].to(torch.float32).contiguous())
+            spc = plan.hold(p[11].to(device=dev, dtype=torch.int64).contiguous())
+            spc_trg = plan.hold(p[12].to(device=dev, dtype=torch.int64).contiguous())
+            ns, nsp = ints(p[17]), ints(p[18])
             if feat_trg.shape[0] != B or spc.shape[0] != B or spc_trg.shape[0] != B or feat_trg.shape[2] != sd + D:
                 raise ValueError("the previous yield does not hold %d utterances of %d features" % (B, sd + D))
             for j in range(n_close):
                 if not (1 <= ns[j] <= spc.shape[1] and 1 <= nsp[j] <= spc_trg.shape[1]):
                     raise ValueError("flens_spc of utterance %d (%d, %d) do not fit the speech-frame index rows" % (j, ns[j], nsp[j]))
-            y = y_in_pp.to(torch.float32).reshape(-1, 1, y_in_pp.shape[-1])
-            y = y[:1].expand(B, 1, y.shape[-1]).contiguous() if y.shape[0] != B else y
             with torch.no_grad():                                                                     # :673-677
-                lat_par = self.enc(feat_trg, y, clamp_vae=True, lat_dim=L)[0].contiguous()
+                lat_par = self.enc(feat_trg, batch_rows(y_in_pp, B), clamp_vae=True, lat_dim=L)[0].contiguous()
             self.last_lat_srctrg = lat_par
-            mat = lambda r, c: (take(r * c), r, c)
-            twf_len = 0
-            for j in range(n_close):
-                e = {"g_trj": mat(ns[j], D), "g_feat": mat(nsp[j], D), "g_par": mat(nsp[j], 2 * L), "g_own": mat(ns[j], 2 * L),
-                     "al_1": mat(nsp[j], 2 * L), "al_2": mat(ns[j], 2 * L)}
-                t2s = [nsp[j], nsp[j], nsp[j], ns[j], ns[j], nsp[j]]
-                e["frames"] = [take(t) for t in t2s]
-                e["twf"] = []
-                for t in t2s:
-                    e["twf"].append(twf_len)
-                    twf_len += t
-                lay.append(e)
-            twf = torch.empty(max(1, twf_len), dtype=torch.int64, device=dev)
-        arena = torch.empty(max(1, cursor[0]), dtype=torch.float64, device=dev)
-        a0 = arena.data_ptr()
-        A = lambda off: a0 + 8 * off
-        for j in range(gv_rows):                                                                      # :1342-1348 (float64 here)
-            for k in ("rec", "cv", "reccyc"):
-                a, lda = row(acc[k], j)
-                jobs1.append(job(_cabi.STAT_GV, flens[j], 1, D, a, lda, out_off=where[("gv", k, j)]))
-        for j, e in enumerate(lay):
+        for j in range(n_close):
             ix = spc.data_ptr() + 8 * j * spc.shape[1]
             ixp = spc_trg.data_ptr() + 8 * j * spc_trg.shape[1]
-            for key, t, idx, col, c1, nrows in (("g_trj", acc["cv"], ix, 0, D, rows), ("g_feat", feat_trg, ixp, sd, D, feat_trg.shape[1]),
-                                                ("g_par", lat_par, ixp, 0, 2 * L, lat_par.shape[1]), ("g_own", acc["lat"], ix, 0, 2 * L, rows)):
+            g = {}
+            for key, t, idx, col, c1, n in (("trj", acc["cv"], ix, 0, D, ns[j]), ("feat", feat_trg, ixp, sd, D, nsp[j]),
+                                            ("par", lat_par, ixp, 0, 2 * L, nsp[j]), ("own", acc["lat"], ix, 0, 2 * L, ns[j])):
                 a, lda = row(t, j, col)
-                jobs1.append(job(_cabi.STAT_GATHER64, e[key][1], 0, c1, a, lda, idx=idx, dst=A(e[key][0]), src_rows=nrows))
-
-            def prob(org, trg_, k, mcd, aligned, mean, c0=0):
-                (oo, r1, c), (to, r2, _) = e[org], e[trg_]
-                return _cabi.DtwProblem(A(oo + c0), A(to + c0), c, c, r1, r2, c - c0, mcd, None if aligned is None else A(e[aligned][0]),
-                                        twf.data_ptr() + 8 * e["twf"][k], A(e["frames"][k]), A(where[(mean, j)]))
-            probs += [prob("g_trj", "g_feat", 0, -1, None, "mcdpow"),                                 # :679
-                      prob("g_trj", "g_feat", 1, -1, None, "mcd", c0=1),                              # :680
-                      prob("g_own", "g_par", 2, -1, "al_1", "al_a"),                                  # :683
-                      prob("g_par", "g_own", 3, 0, None, "cd_a"),                                     # :685
-                      prob("g_par", "g_own", 4, -1, "al_2", "al_b"),                                  # :686
-                      prob("g_own", "g_par", 5, 0, None, "cd_b")]                                     # :688
-            for n, al, ref in (("ld_a", "al_1", "g_par"), ("ld_b", "al_2", "g_own")):                 # :684, :687
-                (ao, r, c), (ro, _, _) = e[al], e[ref]
-                jobs2.append(job(_cabi.STAT_LATDIST, r, 0, c, A(ao), c, A(ro), c, out_off=where[(n, j)]))
-        n1, n2 = len(jobs1), len(jobs2)
-        raw = np.frombuffer(bytes((_cabi.StatJob * (n1 + n2))(*(jobs1 + jobs2))), np.uint8)
-        stage = torch.empty(raw.size, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
-        stage.copy_(torch.from_numpy(raw.copy()))
-        jdev = stage.to(dev, non_blocking=True)
-        size = _cabi.C.sizeof(_cabi.StatJob)
-        if n1:
-            lib.eval_stats(jdev.data_ptr(), n1, a0, st)
-        if probs:
-            nb = lib.dtw_batch_work_bytes(len(probs), max(q.T1 for q in probs), max(q.T2 for q in probs))
-            work = torch.empty(nb, dtype=torch.uint8, device=dev)
-            lib.dtw_batch(probs, work.data_ptr(), nb, st)
-        if n2:
-            lib.eval_stats(jdev.data_ptr() + n1 * size, n2, a0, st)
-        slot = self._pinned(max(1, n_out))
-        ev = self._behind(arena[:max(1, n_out)], slot)
+                g[key] = plan.mat(n, c1)
+                plan.stat(1, _cabi.STAT_GATHER64, n, 0, c1, a, lda, idx=idx, dst=g[key], src_rows=t.shape[1])
+            for n, c0 in (("mcdpow", 0), ("mcd", 1)):                                                 # :679-680
+                where[(n, j)] = plan.vec()
+                plan.align(g["trj"], g["feat"], -1, None, where[(n, j)], c0=c0)
+            where[("ld", j)] = plan.latent_distance(g["own"], g["par"])                               # :683-688
+        plan.finalise()
+        plan.begin(pinned=True)
+        plan.stats(1)
+        plan.dtw()
+        plan.stats(2)
+        slot = self._pinned(max(1, plan.n_out))
+        ev = self._behind(plan.results(), slot)
         meta = dict(where=where, gv_rows=gv_rows, n_close=n_close, files=list(p[13]), files_trg=list(p[14]),
-                    gv_files=list(self._prev_featfile or []), D=D, keep=(stage, jdev))
+                    gv_files=list(self._prev_featfile or []), keep=plan)
         self._pending.append(("close", ev, slot, meta))
 
     # ---- after: the window's launch ----------------------------------------------------------------------------------------------
@@ -347,11 +294,10 @@ class TrainLog(object):
         for j in range(meta["gv_rows"]):                                                              # :1341-1348
             names = GV_SRC if self._is_src(meta["gv_files"][j]) else GV_TRG
             for n, k in zip(names, ("rec", "cv", "reccyc")):
-                at = W[("gv", k, j)]
-                self.lists[n][0].append(host[at:at + meta["D"] - 1].copy())
+                self.lists[n][0].append(W[("gv", k, j)].of(host))
         for j in range(meta["n_close"]):                                                              # :689-704
-            v = lambda n: float(host[W[(n, j)]])
-            vals = (v("mcdpow"), v("mcd"), (v("ld_a") + v("ld_b")) / 2, (v("cd_a") + v("cd_b")) / 2)
+            ld_a, ld_b, cd_a, cd_b = (float(host[r.off]) for r in W[("ld", j)])
+            vals = (float(host[W[("mcdpow", j)].off]), float(host[W[("mcd", j)].off]), (ld_a + ld_b) / 2, (cd_a + cd_b) / 2)
             src = self._is_src(meta["files"][j])
             for n, x in zip(CLOSE_SRC if src else CLOSE_TRG, vals):
                 self.lists[n][0].append(x)

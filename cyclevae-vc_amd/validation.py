@@ -11,13 +11,12 @@ PARITY UNPINNED for the DTW and calc_mcd halves: dtw_c is a third-party binary t
 is the written definition at oracle/cyclevae_oracle.py::dtw_org_to_trg / mcd_aligned, as for stage6.dtw_org_to_trg.  The GV
 variances are taken in float64 from the fp32 trajectories (the reference's np.var runs in float32 on the same values).
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
 import _cabi
 import gru_vae
+from metricplan import MetricPlan, batch_rows, ints, row
 
 N_EV_CYC = 1      # train...:604
 
@@ -43,10 +42,6 @@ def _side(items):
     return {"feat": feat, "code_own": code_own, "code_other": code_other, "feat_par": feat_par, "cv": cv, "spcidx": spc,
             "spcidx_par": spc_par, "flens": flens, "flens_par": flens_par, "flens_spc": flens_spc, "flens_spc_par": flens_spc_par,
             "n_utt": n_utt}
-
-
-def _ints(v):
-    return [int(x) for x in (v.tolist() if hasattr(v, "tolist") else v)]
 
 
 class ValidationPass(object):
@@ -88,10 +83,6 @@ class ValidationPass(object):
         enc, dec, L, sd = self.enc, self.dec, self.lat_dim, self.stdim
         f = lambda t: t.to(torch.float32)
 
-        def rows(y, B):
-            y = f(y).reshape(-1, 1, y.shape[-1])
-            return y[:1].expand(B, 1, y.shape[-1]).contiguous() if y.shape[0] != B else y
-
         def run(mod, xs, ys, clamp):
             """mod over a list of [B, T, C] inputs: inputs of one length go as rows of one call (rows are independent recurrences)."""
             outs = [None] * len(xs)
@@ -111,7 +102,7 @@ class ValidationPass(object):
             return gru_vae.sampling_with_eps(lat, f(eps[name]), lat_dim=L)
 
         B = src["feat"].shape[0]
-        ypp, ys, yt = rows(y_pp, B), rows(y_src, B), rows(y_trg, B)
+        ypp, ys, yt = batch_rows(y_pp, B), batch_rows(y_src, B), batch_rows(y_trg, B)
         o = {}
         o["lat_srctrg"], o["lat_trgsrc"], o["lat_trg"], o["lat_src"] = run(
             enc, [f(src["feat_par"]), f(trg["feat_par"]), f(trg["feat"]), f(src["feat"])], [ypp] * 4, True)      # :837-838, :872-873
@@ -133,18 +124,17 @@ class ValidationPass(object):
         D2H copy.  Returns {name: [B] float64 numpy} for LOSS_TERMS, DB_TERMS, DIST_TERMS and {gv name: [B, D-1]}.
         profile: a dict that receives the device milliseconds of "stats", "dtw" and "latdist" (events around the three calls;
         tools/validation_timing.py) and the counts "jobs", "problems", "work_bytes"."""
-        lib = gru_vae._lib()
-        st = gru_vae._stream()
         L, sd = self.lat_dim, self.stdim
-        f32 = lambda t: t.to(torch.float32).contiguous()
+        dev = passes["lat_src"].device
+        plan = MetricPlan(dev, profile is not None)
+        f32 = lambda t: plan.hold(t.to(torch.float32).contiguous())
         P = {k: f32(v) for k, v in passes.items()}
-        dev = P["lat_src"].device
         feat = {"src": f32(src["feat"]), "trg": f32(trg["feat"]), "src_par": f32(src["feat_par"]), "trg_par": f32(trg["feat_par"])}
         spc = {"src": src["spcidx"], "trg": trg["spcidx"], "src_par": src["spcidx_par"], "trg_par": trg["spcidx_par"]}
-        spc = {k: v.to(device=dev, dtype=torch.int64).contiguous() for k, v in spc.items()}
-        flen = {"src": _ints(src["flens"]), "trg": _ints(trg["flens"])}
-        nspc = {"src": _ints(src["flens_spc"]), "trg": _ints(trg["flens_spc"]), "src_par": _ints(src["flens_spc_par"]),
-                "trg_par": _ints(trg["flens_spc_par"])}
+        spc = {k: plan.hold(v.to(device=dev, dtype=torch.int64).contiguous()) for k, v in spc.items()}
+        flen = {"src": ints(src["flens"]), "trg": ints(trg["flens"])}
+        nspc = {"src": ints(src["flens_spc"]), "trg": ints(trg["flens_spc"]), "src_par": ints(src["flens_spc_par"]),
+                "trg_par": ints(trg["flens_spc_par"])}
         B, Cin = feat["src"].shape[0], feat["src"].shape[2]
         Co = Cin - sd
         for s in ("src", "trg"):
@@ -163,156 +153,75 @@ class ValidationPass(object):
             if max(nspc[s]) > spc[s].shape[1] or min(nspc[s]) < 1:
                 raise ValueError("flens_spc of %s %s do not fit %d speech-frame indices" % (s, nspc[s], spc[s].shape[1]))
 
-        # the f64 arena: [results | packed DTW operands | aligned | frames], and the int64 twf rows
-        cursor = [0]
-
-        def take(n):
-            at = cursor[0]
-            cursor[0] += int(n)
-            return at
-        jobs1, jobs2, probs, where = [], [], [], {}
-
-        def scalar(name, j):
-            where[(name, j)] = (take(1), 1)
-            return where[(name, j)][0]
-
-        # lay the arena out first (offsets), then turn offsets into addresses
-        lay = []
+        # per utterance: result regions, jobs and alignments, declared together
+        idx_of = lambda side, j: spc[side].data_ptr() + 8 * j * spc[side].shape[1]
+        stat, out = plan.stat, []
         for j in range(B):
-            e = {}
-            for g in GV_TERMS:
-                where[(g, j)] = (take(Co - 1), Co - 1)
-            for n in LOSS_TERMS + DB_TERMS:
-                scalar(n, j)
-            for n in ("cd_srctrg_a", "cd_srctrg_b", "cd_trgsrc_a", "cd_trgsrc_b", "ld_srctrg_a", "ld_srctrg_b", "ld_trgsrc_a", "ld_trgsrc_b",
-                      "al_mean_0", "al_mean_1", "al_mean_2", "al_mean_3"):       # (al_mean_*: mean costs nobody reads)
-                scalar(n, j)
-            lay.append(e)
-        n_out = cursor[0]
-        twf_len = [0]
-
-        def mat(rows, cols):
-            return (take(rows * cols), rows, cols)
-        for j, e in enumerate(lay):
-            ns, nt, nsp, ntp = nspc["src"][j], nspc["trg"][j], nspc["src_par"][j], nspc["trg_par"][j]
-            e["g_lat_srctrg"], e["g_lat_src"] = mat(nsp, 2 * L), mat(ns, 2 * L)
-            e["g_lat_trgsrc"], e["g_lat_trg"] = mat(ntp, 2 * L), mat(nt, 2 * L)
-            e["g_trj_trg_src"], e["g_feat_trg_par"] = mat(nt, Co), mat(ntp, Co)
-            e["g_trj_src_trg"], e["g_feat_src_par"] = mat(ns, Co), mat(nsp, Co)
-            e["al_srctrg1"], e["al_srctrg2"] = mat(nsp, 2 * L), mat(ns, 2 * L)
-            e["al_trgsrc1"], e["al_trgsrc2"] = mat(ntp, 2 * L), mat(nt, 2 * L)
-            # frames / twf rows of the twelve alignments: T2 each
-            t2s = [nsp, ns, ns, nsp, ntp, nt, nt, ntp, ntp, ntp, nsp, nsp]
-            e["frames"] = [take(t) for t in t2s]
-            e["twf"] = []
-            for t in t2s:
-                e["twf"].append(twf_len[0])
-                twf_len[0] += t
-        arena = torch.empty(cursor[0], dtype=torch.float64, device=dev)
-        twf = torch.empty(twf_len[0], dtype=torch.int64, device=dev)
-        a0, w0 = arena.data_ptr(), twf.data_ptr()
-        A = lambda off: a0 + 8 * off
-
-        def row(t, j, col=0):
-            """address of t[j, 0, col] of a contiguous [B, T, C] fp32 tensor, and its row stride"""
-            return t.data_ptr() + 4 * (j * t.shape[1] * t.shape[2] + col), t.shape[2]
-
-        def job(kind, rows_, c0, c1, a, lda, b=None, ldb=0, idx=None, dst=None, out_off=0, src_rows=0):
-            return _cabi.StatJob(kind, rows_, c0, c1, src_rows, 0, a, b, lda, ldb, idx, dst, out_off)
-
-        def idx_of(side, j):
-            return spc[side].data_ptr() + 8 * j * spc[side].shape[1]
-
-        for j, e in enumerate(lay):
-            fs, ft = flen["src"][j], flen["trg"][j]
+            fs, ft, o, g = flen["src"][j], flen["trg"][j], {}, {}
             # :888-893
-            for g, t, n in (("gv_src_src", "trj_src_src", fs), ("gv_src_trg", "trj_src_trg", fs), ("gv_src_trg_src", "trj_src_trg_src", fs),
-                            ("gv_trg_trg", "trj_trg_trg", ft), ("gv_trg_src", "trj_trg_src", ft), ("gv_trg_src_trg", "trj_trg_src_trg", ft)):
+            for n, t, nfr in (("gv_src_src", "trj_src_src", fs), ("gv_src_trg", "trj_src_trg", fs), ("gv_src_trg_src", "trj_src_trg_src", fs),
+                              ("gv_trg_trg", "trj_trg_trg", ft), ("gv_trg_src", "trj_trg_src", ft), ("gv_trg_src_trg", "trj_trg_src_trg", ft)):
                 a, lda = row(P[t], j)
-                jobs1.append(job(_cabi.STAT_GV, n, 1, Co, a, lda, out_off=where[(g, j)][0]))
+                o[n] = plan.vec(Co - 1)
+                stat(1, _cabi.STAT_GV, nfr, 1, Co, a, lda, out=o[n])
             # :929-948 calc_mcd on the speech frames, with and without the power coefficient
             for side, names in (("trg", ("trg_trg", "trg_src_trg")), ("src", ("src_src", "src_trg_src"))):
                 fa, lfa = row(feat[side], j, sd)
                 for n in names:
                     b, ldb = row(P["trj_" + n], j)
                     for pre, c0 in (("mcdpow_", 0), ("mcd_", 1)):
-                        jobs1.append(job(_cabi.STAT_MCD_SPC, nspc[side][j], c0, Co, fa, lfa, b, ldb, idx_of(side, j),
-                                         out_off=where[(pre + n, j)][0], src_rows=feat[side].shape[1]))
+                        o[pre + n] = plan.vec()
+                        stat(1, _cabi.STAT_MCD_SPC, nspc[side][j], c0, Co, fa, lfa, b, ldb, idx_of(side, j), out=o[pre + n],
+                             src_rows=feat[side].shape[1])
             # :1006-1013 (the trg_src / src_trg conversions are held against the utterance's OWN features, as the script does)
             for n, side, nfr in (("trg_trg", "trg", ft), ("trg_src", "trg", ft), ("src_src", "src", fs), ("src_trg", "src", fs),
                                  ("trg_src_trg", "trg", ft), ("src_trg_src", "src", fs)):
                 a, lda = row(P["trj_" + n], j)
                 b, ldb = row(feat[side], j, sd)
-                jobs1.append(job(_cabi.STAT_MCD_L1, nfr, 0, Co, a, lda, b, ldb, out_off=where[("loss_mcd_" + n, j)][0]))
+                o["loss_mcd_" + n] = plan.vec()
+                stat(1, _cabi.STAT_MCD_L1, nfr, 0, Co, a, lda, b, ldb, out=o["loss_mcd_" + n])
             # :1015-1019
             for n, t, nfr in (("loss_lat_trg", "lat_trg", ft), ("loss_lat_src", "lat_src", fs), ("loss_lat_trg_cv", "lat_trg_src", ft),
                               ("loss_lat_src_cv", "lat_src_trg", fs)):
                 a, lda = row(P[t], j)
-                jobs1.append(job(_cabi.STAT_KL, nfr, 0, L, a, lda, out_off=where[(n, j)][0]))
+                o[n] = plan.vec()
+                stat(1, _cabi.STAT_KL, nfr, 0, L, a, lda, out=o[n])
             # :895-896, :912-913, :938-939, :950-951: the f64 DTW operands
-            for key, t, side, col, c1 in (("g_lat_srctrg", P["lat_srctrg"], "src_par", 0, 2 * L), ("g_lat_src", P["lat_src"], "src", 0, 2 * L),
-                                          ("g_lat_trgsrc", P["lat_trgsrc"], "trg_par", 0, 2 * L), ("g_lat_trg", P["lat_trg"], "trg", 0, 2 * L),
-                                          ("g_trj_trg_src", P["trj_trg_src"], "trg", 0, Co), ("g_feat_trg_par", feat["trg_par"], "trg_par", sd, Co),
-                                          ("g_trj_src_trg", P["trj_src_trg"], "src", 0, Co), ("g_feat_src_par", feat["src_par"], "src_par", sd, Co)):
+            for key, t, side, col, c1 in (("lat_srctrg", P["lat_srctrg"], "src_par", 0, 2 * L), ("lat_src", P["lat_src"], "src", 0, 2 * L),
+                                          ("lat_trgsrc", P["lat_trgsrc"], "trg_par", 0, 2 * L), ("lat_trg", P["lat_trg"], "trg", 0, 2 * L),
+                                          ("trj_trg_src", P["trj_trg_src"], "trg", 0, Co), ("feat_trg_par", feat["trg_par"], "trg_par", sd, Co),
+                                          ("trj_src_trg", P["trj_src_trg"], "src", 0, Co), ("feat_src_par", feat["src_par"], "src_par", sd, Co)):
                 a, lda = row(t, j, col)
-                off, r, c = e[key]
-                jobs1.append(job(_cabi.STAT_GATHER64, r, 0, c1, a, lda, idx=idx_of(side, j), dst=A(off), src_rows=t.shape[1]))
-
-            def prob(org, trg_, k, mcd, aligned=None, mean=None, c0=0):
-                (oo, r1, c), (to, r2, _) = e[org], e[trg_]
-                return _cabi.DtwProblem(A(oo + c0), A(to + c0), c, c, r1, r2, c - c0, mcd, None if aligned is None else A(e[aligned][0]),
-                                        w0 + 8 * e["twf"][k], A(e["frames"][k]), A(mean))
-            # :897-902, :914-919 -- mel-cd alignments give the aligned latents, cosine alignments their mean cost
-            W = lambda n: where[(n, j)][0]
-            probs += [prob("g_lat_src", "g_lat_srctrg", 0, -1, "al_srctrg1", W("al_mean_0")),
-                      prob("g_lat_srctrg", "g_lat_src", 1, 0, None, W("cd_srctrg_a")),
-                      prob("g_lat_srctrg", "g_lat_src", 2, -1, "al_srctrg2", W("al_mean_1")),
-                      prob("g_lat_src", "g_lat_srctrg", 3, 0, None, W("cd_srctrg_b")),
-                      prob("g_lat_trg", "g_lat_trgsrc", 4, -1, "al_trgsrc1", W("al_mean_2")),
-                      prob("g_lat_trgsrc", "g_lat_trg", 5, 0, None, W("cd_trgsrc_a")),
-                      prob("g_lat_trgsrc", "g_lat_trg", 6, -1, "al_trgsrc2", W("al_mean_3")),
-                      prob("g_lat_trg", "g_lat_trgsrc", 7, 0, None, W("cd_trgsrc_b")),
-                      # :938-939, :950-951 -- the converted trajectory against the parallel utterance, with and without coefficient 0
-                      prob("g_trj_trg_src", "g_feat_trg_par", 8, -1, None, W("mcdpow_trg_src")),
-                      prob("g_trj_trg_src", "g_feat_trg_par", 9, -1, None, W("mcd_trg_src"), c0=1),
-                      prob("g_trj_src_trg", "g_feat_src_par", 10, -1, None, W("mcdpow_src_trg")),
-                      prob("g_trj_src_trg", "g_feat_src_par", 11, -1, None, W("mcd_src_trg"), c0=1)]
-            # :898, :901, :915, :918
-            for n, al, ref in (("ld_srctrg_a", "al_srctrg1", "g_lat_srctrg"), ("ld_srctrg_b", "al_srctrg2", "g_lat_src"),
-                               ("ld_trgsrc_a", "al_trgsrc1", "g_lat_trgsrc"), ("ld_trgsrc_b", "al_trgsrc2", "g_lat_trg")):
-                (ao, r, c), (ro, _, _) = e[al], e[ref]
-                jobs2.append(job(_cabi.STAT_LATDIST, r, 0, c, A(ao), c, A(ro), c, out_off=W(n)))
-
-        n1, n2 = len(jobs1), len(jobs2)
-        raw = bytes((_cabi.StatJob * (n1 + n2))(*(jobs1 + jobs2)))
-        jdev = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(dev)
-        work_bytes = lib.dtw_batch_work_bytes(len(probs), max(p.T1 for p in probs), max(p.T2 for p in probs))
-        work = torch.empty(work_bytes, dtype=torch.uint8, device=dev)
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if profile is not None else None
-        mark = (lambda k: ev[k].record()) if ev else (lambda k: None)
-        mark(0)
-        lib.eval_stats(jdev.data_ptr(), n1, a0, st)
-        mark(1)
-        lib.dtw_batch(probs, work.data_ptr(), work_bytes, st)
-        mark(2)
-        lib.eval_stats(jdev.data_ptr() + n1 * C.sizeof(_cabi.StatJob), n2, a0, st)
-        mark(3)
-        host = arena[:n_out].cpu().numpy()          # the ONE D2H copy (waits for the stream)
-        if ev:
-            profile.update(stats=ev[0].elapsed_time(ev[1]), dtw=ev[1].elapsed_time(ev[2]), latdist=ev[2].elapsed_time(ev[3]),
-                           jobs=n1 + n2, problems=len(probs), work_bytes=int(work_bytes))
+                g[key] = plan.mat(nspc[side][j], c1)
+                stat(1, _cabi.STAT_GATHER64, g[key].rows, 0, c1, a, lda, idx=idx_of(side, j), dst=g[key], src_rows=t.shape[1])
+            # :897-906, :914-923
+            o["srctrg"] = plan.latent_distance(g["lat_src"], g["lat_srctrg"])
+            o["trgsrc"] = plan.latent_distance(g["lat_trg"], g["lat_trgsrc"])
+            # :938-939, :950-951 -- the converted trajectory against the parallel utterance, with and without coefficient 0
+            for n, org, par in (("trg_src", "trj_trg_src", "feat_trg_par"), ("src_trg", "trj_src_trg", "feat_src_par")):
+                for pre, c0 in (("mcdpow_", 0), ("mcd_", 1)):
+                    o[pre + n] = plan.vec()
+                    plan.align(g[org], g[par], -1, None, o[pre + n], c0=c0)
+            out.append(o)
+        plan.finalise()
+        plan.begin()
+        plan.stats(1)
+        plan.dtw()
+        plan.stats(2)
+        host = plan.results().cpu().numpy()          # the ONE D2H copy (waits for the stream)
+        if profile is not None:
+            ms = plan.times()
+            profile.update(stats=ms["stats1"], dtw=ms["dtw"], latdist=ms["stats2"], jobs=len(plan.table), problems=len(plan.probs),
+                           work_bytes=int(plan.work_bytes))
         gru_vae.check_status()
         res = {}
-        col = lambda n: np.array([host[where[(n, j)][0]] for j in range(B)])
         for n in LOSS_TERMS + DB_TERMS:
-            res[n] = col(n)
-        for g in GV_TERMS:
-            res[g] = np.stack([host[where[(g, j)][0]:where[(g, j)][0] + Co - 1] for j in range(B)])
-        # :904-906, :921-923
-        res["lat_dist_srctrg1"] = (col("ld_srctrg_a") + col("ld_srctrg_b")) / 2
-        res["lat_dist_srctrg2"] = (col("cd_srctrg_a") + col("cd_srctrg_b")) / 2
-        res["lat_dist_trgsrc1"] = (col("ld_trgsrc_a") + col("ld_trgsrc_b")) / 2
-        res["lat_dist_trgsrc2"] = (col("cd_trgsrc_a") + col("cd_trgsrc_b")) / 2
+            res[n] = np.array([host[o[n].off] for o in out])
+        for n in GV_TERMS:
+            res[n] = np.stack([o[n].of(host) for o in out])
+        for n in ("srctrg", "trgsrc"):               # :904-906, :921-923
+            rmse_a, rmse_b, cos_a, cos_b = (np.array([host[o[n][k].off] for o in out]) for k in range(4))
+            res["lat_dist_%s1" % n], res["lat_dist_%s2" % n] = (rmse_a + rmse_b) / 2, (cos_a + cos_b) / 2
         return res
 
     def batch(self, src_items, trg_items, y_in_pp, y_in_src, y_in_trg, eps=None):

@@ -13,7 +13,7 @@ from conftest import have_hdf5
 import _cabi
 import stage5_util as S
 import validation_util as VU
-from emu_util import emu_lib
+from emu_util import bind_emulator, emu_lib
 
 
 @pytest.fixture(scope="module")
@@ -23,25 +23,7 @@ def be():
 
 @pytest.fixture
 def emu_gru_vae(monkeypatch):
-    """gru_vae bound to the emulator build for this test (the pattern of tests/test_validation_cpu.py): "device" tensors are CPU
-    tensors."""
-    import torch
-    import emu_util
-    import gru_vae
-    monkeypatch.setattr(_cabi, "DEFAULT_LIB", emu_util.build_emu())
-    for name, v in (("_LIB", None), ("_SINK", None), ("_LIBS", {}), ("_SINKS", {})):
-        monkeypatch.setattr(gru_vae, name, v)
-    monkeypatch.setattr(gru_vae, "_need_cuda", lambda t, what: None)
-    monkeypatch.setattr(gru_vae, "_stream", lambda: 0)
-
-    class _NoStream(object):
-        cuda_stream = 0
-
-        def synchronize(self):
-            pass
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda *a, **k: _NoStream())
-    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
-    return gru_vae
+    return bind_emulator(monkeypatch)
 
 
 def test_abi_stays_10_and_the_export_is_bound(be):

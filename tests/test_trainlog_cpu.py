@@ -13,7 +13,7 @@ import pytest
 
 import _cabi
 import trainlog_util as U
-from emu_util import emu_lib
+from emu_util import bind_emulator, emu_lib
 
 
 @pytest.fixture(scope="module")
@@ -45,7 +45,7 @@ def test_window_kernel_refuses_bad_arguments(be):
 
 @pytest.fixture
 def emu_gru_vae(monkeypatch):
-    return U.bind_emulator(monkeypatch)
+    return bind_emulator(monkeypatch)
 
 
 @pytest.mark.parametrize("with_sentinel", [True, False], ids=["sentinel_between_batches", "two_batches_one_pass"])

@@ -9,7 +9,7 @@ import pytest
 
 import _cabi
 import validation_util as U
-from emu_util import emu_lib
+from emu_util import bind_emulator, emu_lib
 
 
 @pytest.fixture(scope="module")
@@ -98,25 +98,7 @@ def test_eval_stats_jobs(be):
 
 @pytest.fixture
 def emu_gru_vae(monkeypatch):
-    """gru_vae bound to the emulator build for this test (what tests/emu_bench_backend.install() does for a whole process):
-    "device" tensors are CPU tensors."""
-    import torch
-    import emu_util
-    import gru_vae
-    monkeypatch.setattr(_cabi, "DEFAULT_LIB", emu_util.build_emu())
-    for name, v in (("_LIB", None), ("_SINK", None), ("_LIBS", {}), ("_SINKS", {})):
-        monkeypatch.setattr(gru_vae, name, v)
-    monkeypatch.setattr(gru_vae, "_need_cuda", lambda t, what: None)
-    monkeypatch.setattr(gru_vae, "_stream", lambda: 0)
-
-    class _NoStream(object):
-        cuda_stream = 0
-
-        def synchronize(self):
-            pass
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda *a, **k: _NoStream())
-    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
-    return gru_vae
+    return bind_emulator(monkeypatch)
 
 
 def test_validation_pass_end_to_end(emu_gru_vae):

@@ -164,32 +164,6 @@ def check_refusals(be):
         be.lib.trainlog_window(a, be.stream)
 
 
-def bind_emulator(monkeypatch):
-    """gru_vae bound to the emulator build for one test (what tests/emu_bench_backend.install() does for a whole process): "device"
-    tensors are CPU tensors."""
-    import torch
-    import emu_util
-    import gru_vae
-    monkeypatch.setattr(_cabi, "DEFAULT_LIB", emu_util.build_emu())
-    for name, v in (("_LIB", None), ("_SINK", None), ("_LIBS", {}), ("_SINKS", {})):
-        monkeypatch.setattr(gru_vae, name, v)
-    monkeypatch.setattr(gru_vae, "_need_cuda", lambda t, what: None)
-    monkeypatch.setattr(gru_vae, "_stream", lambda: 0)
-    monkeypatch.setattr(gru_vae, "_backward_overlap", False)       # (no side stream: the backward returns its gradients to autograd)
-
-    class _NoStream(object):
-        cuda_stream = 0
-
-        def synchronize(self):
-            pass
-
-        def wait_event(self, ev):
-            pass
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda *a, **k: _NoStream())
-    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
-    return gru_vae
-
-
 # ---- (b) TrainLog end to end ---------------------------------------------------------------------------------------------------
 
 H64 = dict(in_dim=30, out_dim=26, lat_dim=8, hidden=64, n_cyc=2, bias_scale=0.1)
