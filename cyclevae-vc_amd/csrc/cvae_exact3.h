@@ -29,6 +29,7 @@
 // profiles/r02_notes_exact3_kernel.md.)
 #pragma once
 #include <cvae_intrin.h>
+#include <type_traits>
 
 // CVAE_V6_IN_AGPR(x): from here on the value lives in accumulator registers.  The MFMA takes its A / B operands from either
 // register file on gfx950, so a weight tuple that is only ever an MFMA operand needs no architectural VGPR -- but left to itself
@@ -66,10 +67,12 @@ struct Step6Params {
     int Co;
     int rts;             // row tiles handled concurrently by the grid (grid = H/8 * rts blocks)
     int want_f32;        // write the fp32 copy of every new state to hbuf (the raw-projection / h_last paths read it; the limb projection does not)
-    int exp;             // measurement-only switches (bit 0: operands from slot 0 every step; bit 1: XCD-aware block mapping; bits 2-3: reporting wave; bits 8..: poll back-off override)
+    int exp;             // measurement-only switches (bit 0: operands from slot 0 every step; bit 1: XCD-aware block mapping; bits 2-3: reporting wave; bit 7, host side: slot 0 poisoned behind the prologue, a test aid; bits 8..: poll back-off override)
     int backoff;         // x 64 cycles a block with ONE row tile sleeps before the first flag poll of a step (swept per front-end width, cvae_lib.hip)
     const float* gx;     // KFW == 0 (hoisted front-end): the input-side pre-activations of every frame, cfold included, from the front-end GEMM:
     long gx_bstride;     //   row b, frame t, gate column n at gx[b * gx_bstride + t * 3H + n]; rows < B only
+    int h0_zero;         // slot 0 is all zeros (no cell carries a state in: the prologue's fresh-pass branch): the tasks of frame 0 request no
+                         //   state operand and issue no recurrent MFMA -- each would add an exact +0 -- and h_{-1} = 0 without the hbuf load
 };
 
 // wrec3[c][wave][s][m][lane][e]: the folded recurrent weights (wrec2, fp32) of unit octet c as fp16 triples in the operand
@@ -232,8 +235,9 @@ __global__ __launch_bounds__(256, 1) void k_gru_steps_v6(Step6Params p) {
     f32x4 x4[2 * RF];                   // ring slot s % RF: limbs 0, 1 of 16-k step s
     f32x2 x2[RF];                       //                   limb 2 (8 bytes)
     const unsigned char* xw = nullptr;
-    auto set_x = [&](int k) {
-        const int tt = k / ntile, ii = ti + (k % ntile) * rts;
+    // (a task is named by its frame and by which of the block's tiles it is: k = frame * ntile + q, carried along, never divided)
+    auto set_x = [&](int tt, int q) {
+        const int ii = ti + q * rts;
         xw = (const unsigned char*)p.xt + (((long)ii * p.Tp + tt) * (p.Cp >> 3) + 2 * (wave * KFW) + kh) * 1280;
     };
     auto load_x = [&](int s) {
@@ -243,8 +247,8 @@ __global__ __launch_bounds__(256, 1) void k_gru_steps_v6(Step6Params p) {
     };
     // HOIST: the gate inputs of task k, one (row, unit) per thread, three fp32 loads (rows beyond B: none, their gates are not formed)
     float gq0 = 0.f, gq1 = 0.f, gq2 = 0.f;
-    auto load_g = [&](int k) {
-        const int tt = k / ntile, gr = (ti + (k % ntile) * rts) * 32 + row;
+    auto load_g = [&](int tt, int q) {
+        const int gr = (ti + q * rts) * 32 + row;
         if (gr < p.B) {
             const float* g = p.gx + (long)gr * p.gx_bstride + (long)tt * 3 * H + j;
             gq0 = g[0]; gq1 = g[H]; gq2 = g[2 * H];
@@ -268,18 +272,26 @@ __global__ __launch_bounds__(256, 1) void k_gru_steps_v6(Step6Params p) {
     float hkeep0 = 0.f, hkeep1 = 0.f;   // h_{t-1} of this thread's (row, unit), per tile for up to two tiles per block
     const int backoff = (p.exp >> 8) ? (p.exp >> 8) - 1 : p.backoff;     // x 64 cycles before the first poll (exp: measurement override)
     if constexpr (HOIST) {
-        if (ntask > 0) load_g(0);
+        if (ntask > 0) load_g(0, 0);
     } else if (ntask > 0) {
-        set_x(0);
+        set_x(0, 0);
 #pragma unroll
         for (int s = 0; s < RF; ++s) load_x(s);
     }
     if constexpr (FPRE && FW0_EARLY) { if (ntask > 0) load_fw(0); }
     unsigned fpre = 0u;                 // flags of the NEXT task, read at the end of the current one (several tiles per block)
-    for (int k = 0; k < ntask; ++k) {
+    // One task = one (frame, row tile of this block).  REC = false is the task of FRAME 0 IN A FRESH PASS (p.h0_zero): the state it would
+    // multiply is zero in every limb, so it requests no state operand (nor, W2S, third weight limbs), issues no recurrent MFMA -- each
+    // would add an exact +0 to the front-end sums -- and takes h_{-1} = 0 without the hbuf load.  Everything else of it is the same
+    // statements.  Those tasks stand in front of the task loop as straight-line code (below): a branch around the recurrent stretch
+    // inside the loop cost the H = 1024 instances 68-228 B of scratch per lane and the operand ring its counted waits.
+    auto task = [&](const int k, const int frame, const int q, auto rec_c) __attribute__((always_inline)) {
+        constexpr bool REC = decltype(rec_c)::value;
         long long c0 = 0;
         if constexpr (PROF) c0 = cvae_clock();
-        const int t = k / ntile, i = ti + (k % ntile) * rts;
+        const int t = REC ? frame : 0, i = ti + q * rts;
+        const bool wrap = q + 1 == ntile;
+        const int tn = wrap ? t + 1 : t, qn = wrap ? 0 : q + 1;      // the next task
         const unsigned row0 = (unsigned)(t * p.Bp + i * 32), tile0 = row0 >> 5;   // (Bp is a multiple of 32)
         f32x16 a0 = cvae_zero16(), a1 = cvae_zero16(), a2 = cvae_zero16(), a3 = cvae_zero16();   // S0 | S1 | S2 (two chains)
         if constexpr (FPRE && !FW0_EARLY) load_fw(0);
@@ -313,7 +325,7 @@ __global__ __launch_bounds__(256, 1) void k_gru_steps_v6(Step6Params p) {
         if (t > 0 && !pre_ok) {   // the octets (two per 16-unit chunk) of this wave's K share are published?
             unsigned spins = 0;
             if (ntile == 1)
-                for (int q = 0; q < backoff; ++q) cvae_sleep_64();
+                for (int b = 0; b < backoff; ++b) cvae_sleep_64();
             for (;;) {
                 unsigned f = (unsigned)t;
                 if (lane < 2 * KPW && 2 * s_lo + lane < NB) f = cvae_atomic_load_agent(p.flags + (long)i * NB + 2 * s_lo + lane);
@@ -340,8 +352,9 @@ __global__ __launch_bounds__(256, 1) void k_gru_steps_v6(Step6Params p) {
                     const float* g0p = p.gx0 + (long)grow * 3 * H + j;
                     gxr += g0p[0]; gxz += g0p[H]; gxn += g0p[2 * H];
                 } else if (t == 0 && p.dy) cvae_t0_fix(p.wyT, p.dy, p.Co, H, j, grow, gxr, gxz, gxn);
-                if (t == 0) {               // slot 0 comes from the prologue
-                    hold = cvae_buf_load_f1_sc1(hb, (unsigned)(row * 64 + (j & 15) * 4), ((unsigned)(j >> 4) * mtot + row0) * 64u);
+                if (t == 0) {               // slot 0 comes from the prologue (a fresh pass: zeros, nothing to read)
+                    if constexpr (REC) hold = cvae_buf_load_f1_sc1(hb, (unsigned)(row * 64 + (j & 15) * 4), ((unsigned)(j >> 4) * mtot + row0) * 64u);
+                    else hold = 0.0f;
                 } else if (ntile > 2) {     // more than two tiles per block: re-read the own h from the exchange buffer (exact)
                     const unsigned so = ((unsigned)(j >> 4) * tstride + tile0) * 2560u, okh = (unsigned)((j >> 3) & 1);
                     const unsigned vo = okh * 512u + (unsigned)(row * 16 + (u >> 1) * 4);
@@ -375,15 +388,15 @@ __global__ __launch_bounds__(256, 1) void k_gru_steps_v6(Step6Params p) {
         f32x2 w2r[W2S ? RW : 1];
         const float* w2base = W2S ? p.w2s + ((long)c * 4 + wave) * KPW * 128 + lane * 2 : nullptr;
         auto load_w2 = [&](int s) { w2r[s % RW] = *(const f32x2*)(w2base + s * 128); };
-        if constexpr (W2S) {
+        if constexpr (W2S && REC) {
 #pragma unroll
             for (int s = 0; s < RW; ++s) load_w2(s);
         }
 #pragma unroll
-        for (int s = 0; s < RD; ++s) load_h(s);
+        for (int s = 0; s < (REC ? RD : 0); ++s) load_h(s);
         if constexpr (KPW < 32) gate_inputs();
 #pragma unroll
-        for (int s = 0; s < KPW; ++s) {
+        for (int s = 0; s < (REC ? KPW : 0); ++s) {
             const f32x4 l0 = hc[2 * (s % RD)], l1 = hc[2 * (s % RD) + 1];
             a0 = cvae_mfma_32x32x16_f16(l0, w0[s], a0);
             a1 = cvae_mfma_32x32x16_f16(l0, w1[s], a1);
@@ -406,9 +419,9 @@ __global__ __launch_bounds__(256, 1) void k_gru_steps_v6(Step6Params p) {
         // under reduce + gates + publish), 1 = every wave after the publish, 2 = wave 0 (the publisher) after, the others here
         const int xmode = HOIST ? 0 : (p.exp >> 5) & 3;
         if constexpr (HOIST) {
-            if (k + 1 < ntask) load_g(k + 1);      // (this task's values were copied into gxr .. gxn above)
+            if (k + 1 < ntask) load_g(tn, qn);      // (this task's values were copied into gxr .. gxn above)
         } else {
-            if (k + 1 < ntask) set_x(k + 1);
+            if (k + 1 < ntask) set_x(tn, qn);
             if (k + 1 < ntask && (xmode == 0 || (xmode == 2 && wave != 0))) {
 #pragma unroll
                 for (int s = 0; s < RF; ++s) load_x(s);
@@ -465,13 +478,29 @@ __global__ __launch_bounds__(256, 1) void k_gru_steps_v6(Step6Params p) {
             }
         }
         if (ntile > 1 && k + 1 < ntask) {   // (behind wave 0's publish, so its drain never waits for this load)
-            const int kn = k + 1, tn = kn / ntile, in_ = ti + (kn % ntile) * rts;
+            const int in_ = ti + qn * rts;
             fpre = (unsigned)tn;
             if (tn > 0 && lane < 2 * KPW && 2 * s_lo + lane < NB)
                 fpre = cvae_atomic_load_agent(p.flags + (long)in_ * NB + 2 * s_lo + lane);
         }
         if constexpr (FPRE && FW0_EARLY) { if (k + 1 < ntask) load_fw(0); }
         if constexpr (PROF) { const long long c1 = cvae_clock(); pc[3] += c1 - c0; c0 = c1; }
+    };
+    // Frame 0 of a fresh pass: the first ntile tasks, without their recurrent stretch.  Straight-line for up to NPEEL tiles per block (a
+    // block of the 64- and 128-row passes has one and two); tiles beyond that take frame 0 in the loop, zeros multiplied as before.
+    // (Not a loop of its own: tools/v6_loop_census.py takes the first loop that holds an MFMA for the task loop.)
+    constexpr int NPEEL = 3;
+    int k0 = 0;
+    if (p.h0_zero) {
+        if (ntile > 0) task(0, 0, 0, std::false_type());
+        if (ntile > 1) task(1, 0, 1, std::false_type());
+        if (ntile > 2) task(2, 0, 2, std::false_type());
+        k0 = ntile < NPEEL ? ntile : NPEEL;
+    }
+    int frame = k0 > 0 && k0 == ntile ? 1 : 0, q = frame ? 0 : k0;
+    for (int k = k0; k < ntask; ++k) {
+        task(k, frame, q, std::true_type());
+        if (++q == ntile) q = 0, ++frame;
     }
     if constexpr (PROF) {
         if (p.prof && tid == 64 * ((p.exp >> 2) & 3))    // measurement: exp bits 2-3 pick the reporting wave

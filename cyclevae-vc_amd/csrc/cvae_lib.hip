@@ -31,7 +31,7 @@ thread_local char g_err[512] = "";
 // Tuning / diagnostic switches (cvae_set_option): the library reads NO environment variable.
 enum OptId {
     OPT_V6_LIMBS_H64, OPT_NO_LL, OPT_MAX_RT, OPT_LL_BACKOFF, OPT_EXP, OPT_GEMM_FORCE, OPT_GEMM_LOG, OPT_TRAIN_OLD_GEMM,
-    OPT_GEMM_TRACE, OPT_TRAIN_PER_STEP, OPT_TRAIN_PROF, OPT_TRAIN_BACKOFF, OPT_TRAIN_FP32_MFMA, OPT_TRAIN_BWD_PER_STEP, OPT_TRAIN_KERNEL, OPT_X3_TILE, OPT_BWD_OVERFLOW_AT, OPT_GEMM_MAX_SPLIT, OPT_BWD_KS, OPT_COOP_LAUNCH, OPT_V6_LIMBS_H2048, OPT_V6_W2S_H64, OPT_STEP_COL_TILES, OPT_TRAIN_PROFILE, OPT_TRAIN_XMAP, OPT_MASKS_ON_SIDE, OPT_V6_BACKOFF, OPT_TRAIN_BWD_BACKOFF, OPT_LL_ROW_PAD, OPT_GEMM_MIN_DEPTH, OPT_TRAIN_BWD_GEOM, OPT_BWD_W3_L1_H64, OPT_TRAIN_FWD_GEOM, OPT_TRAIN_FWD_BACKOFF, OPT_EXACT_RANGE_AT, OPT_DTW_BATCH_COST, OPT_COUNT
+    OPT_GEMM_TRACE, OPT_TRAIN_PER_STEP, OPT_TRAIN_PROF, OPT_TRAIN_BACKOFF, OPT_TRAIN_FP32_MFMA, OPT_TRAIN_BWD_PER_STEP, OPT_TRAIN_KERNEL, OPT_X3_TILE, OPT_BWD_OVERFLOW_AT, OPT_GEMM_MAX_SPLIT, OPT_BWD_KS, OPT_COOP_LAUNCH, OPT_V6_LIMBS_H2048, OPT_V6_W2S_H64, OPT_STEP_COL_TILES, OPT_TRAIN_PROFILE, OPT_TRAIN_XMAP, OPT_MASKS_ON_SIDE, OPT_V6_BACKOFF, OPT_TRAIN_BWD_BACKOFF, OPT_LL_ROW_PAD, OPT_GEMM_MIN_DEPTH, OPT_TRAIN_BWD_GEOM, OPT_BWD_W3_L1_H64, OPT_TRAIN_FWD_GEOM, OPT_TRAIN_FWD_BACKOFF, OPT_EXACT_RANGE_AT, OPT_DTW_BATCH_COST, OPT_V6_SKIP_T0, OPT_COUNT
 };
 struct OptEntry { const char* name; long dflt; };
 const OptEntry g_opt[OPT_COUNT] = {      // names and DEFAULTS (immutable); the values live in the context
@@ -71,6 +71,7 @@ const OptEntry g_opt[OPT_COUNT] = {      // names and DEFAULTS (immutable); the 
     {"train_fwd_backoff", -1},    // x 64 cycles before the first flag poll of a task of the exact forward training recurrences (16-row-tile kernels); -1: 24 when a block has ONE tile (nothing else covers the hand-off and early polls slow the publishes they wait for), 0 with two or more
     {"exact_range_at", 65504},    // |x| from which an exchanged value (normalised input, carried-in state) of the limb-operand eval kernels raises CVAE_STATUS_RANGE: 65504 = the first limb overflows; 2048 = the third limb (a bf8 byte) stops being exact
     {"dtw_batch_cost", 1},        // cvae_dtw_batch: 1 = local costs of a chunk written first by one grid-wide kernel (f64 slab per problem), 0 = computed cell by cell inside the path kernel; same bits (profiles/validation_notes.md)
+    {"v6_skip_t0", 1},            // k_gru_steps_v6 in a pass no cell of which carries a state in: 1 = the tasks of frame 0 leave out the recurrent product of the all-zero slot 0 (no operand request, no MFMA; same bits), 0 = they run it (profiles/v6_launch_ramp_notes.md)
 };
 
 // hipEvent pairs recorded around the recurrent kernel when CVAE_FLAG_PROFILE is set
@@ -405,6 +406,7 @@ struct EvalPlan {
     bool pairs;                           // the prologue writes the fp16-pair copies (SPLIT_F16 off V6; V6: the limb triples instead)
     bool gx0_ready;                       // the prologue forms the frame-0 feedback correction (else k_gru_steps_v6 does: cvae_t0_fix)
     bool want_f32;                        // V6 also writes the fp32 state copy
+    bool h0_zero;                         // V6 / V6H: slot 0 is all zeros (the prologue's fresh-pass branch) and frame 0 skips its recurrent product
     int prologue, proj;                   // PRO_*, PROJ_*
 };
 
@@ -470,6 +472,8 @@ EvalPlan plan_eval_pass(const Dims& m, int Brows, int T, int flags, int cus, boo
     // k_gru_steps_ll or on an fp32-operand kernel has nothing to report (limbs)
     pn.pairs = !v6 && (flags & CVAE_FLAG_SPLIT_F16);
     pn.gx0_ready = v6 && !f.h_in;
+    // no cell carries a state in <=> k_prologue zero-fills slot 0 (its !any_h branch reads the same pointers PassFacts was built from)
+    pn.h0_zero = v6 && !f.h_in && opt(OPT_V6_SKIP_T0) != 0;
     // the fp32 state copy of a V6 pass is only read by the raw projection (y_last), k_hlast and the projections off the limb triples
     pn.want_f32 = v6 && (i6->limbs != 3 || f.y_last || f.h_last || (opt(OPT_EXP) & 16));      // (exp bit 4: always write it, for A/B measurements)
     // (V6H: the input goes through the fp32 GEMM -- no limb copy of it, the row-wise prologue; its range word then covers h_in only)
@@ -533,6 +537,16 @@ __global__ void k_clear_words(int32_t* p, int n) {
 inline hipError_t clear_words(void* p, int n, hipStream_t st) {
     hipLaunchKernelGGL((k_clear_words), dim3(1), dim3(64), 0, st, (int32_t*)p, n);
     return hipGetLastError();
+}
+
+// Test aid (exp bit 7): slot 0 of a V6 pass's state buffers -- the limb triples and the fp32 copy -- overwritten with 0xFF bytes (NaN as
+// half, as bf8 and as fp32) behind the prologue: a fresh pass whose frame 0 skips the recurrent product (v6_skip_t0) reads none of it.
+// One block per 16-unit chunk: Bp * 80 B of triples and Bp * 64 B of fp32 state, both runs inside the chunk's (T + 1) * Bp rows.
+__global__ void k_poison_slot0(unsigned* hx, unsigned* hbuf, long mtot, int Bp) {
+    unsigned* a = hx + (long)blockIdx.x * mtot * 20;
+    unsigned* b = hbuf + (long)blockIdx.x * mtot * 16;
+    for (int i = threadIdx.x; i < Bp * 20; i += blockDim.x) a[i] = 0xffffffffu;
+    for (int i = threadIdx.x; i < Bp * 16; i += blockDim.x) b[i] = 0xffffffffu;
 }
 
 int cu_count() {
@@ -795,6 +809,8 @@ int run_pass(const Dims& m, const cvae_net_desc* d, const float* P, const Cell* 
         o.gx0 = pn.gx0_ready ? ws + wl.gx0 : nullptr;
         o.ll_counter = pn.form == CVAE_EVAL_LL ? (unsigned*)(ws + wl.status) + 16 : nullptr;
         run_prologue(m, d, P, pl, rows, o, st);
+        if (triples && (opt(OPT_EXP) & 128))
+            hipLaunchKernelGGL((k_poison_slot0), dim3(m.nch), dim3(256), 0, st, (unsigned*)(ws + wl.hs), (unsigned*)hbuf, wl.mtot, wl.Bp);
     }
 
     const size_t lds2 = (4 * 16 * 84 + 16 * 16) * sizeof(float);
@@ -837,6 +853,7 @@ int run_pass(const Dims& m, const cvae_net_desc* d, const float* P, const Cell* 
         q.wyT = P + pl.wyT; q.dy = dy; q.Co = m.Co;
         q.gx0 = pn.gx0_ready ? ws + wl.gx0 : nullptr;
         q.want_f32 = pn.want_f32 ? 1 : 0;
+        q.h0_zero = pn.h0_zero ? 1 : 0;
         q.rts = pn.rts;
         q.exp = (int)opt(OPT_EXP);   // measurement switches only
         q.backoff = pn.backoff;

@@ -218,6 +218,9 @@ int cvae_set_draw_parts(cvae_ctx* ctx, int32_t parts);
  *                                per cell).  Same bits either way; profiles/validation_notes.md holds the measurement.
  *   "masks_on_side"     1        train-mode forward with a side stream set: the dropout mask of the recurrence's feedback operand is
  *                                drawn on the side stream, beside the prologue and the front-end GEMMs (0: on the launch stream)
+ *   "v6_skip_t0"        1        k_gru_steps_v6 in a pass no cell of which carries a state in (slot 0 is all zeros): 1 = the tasks of
+ *                                frame 0 request no state operand and issue no recurrent MFMA (each would add an exact +0: same bits);
+ *                                0 = they multiply the zeros (profiles/v6_launch_ramp_notes.md)
  */
 int cvae_set_option(cvae_ctx* ctx, const char* name, int64_t value);
 int cvae_get_option(cvae_ctx* ctx, const char* name, int64_t* value);
