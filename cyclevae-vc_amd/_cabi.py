@@ -176,6 +176,10 @@ class _Bound(object):
         return fn
 
 
+# Test queries added WITHOUT an ABI bump: a library of the same ABI version built before one of them still loads (every kernel entry
+# point is there), and calling the missing query raises CvaeError.  The shipped library must export them (__graft_entry__.build and
+# tests/test_cabi_exports.py check all of EXPORTS).
+ADDITIVE = ("cvae_plan_pass_deep_tiles",)
 NO_CONTEXT = ("cvae_last_error_string", "cvae_abi_version", "cvae_ctx_create", "cvae_ctx_destroy")
 _CDLLS = {}     # path -> (CDLL with argtypes declared): one load per process, any number of contexts
 
@@ -245,6 +249,9 @@ class CvaeLib(object):
         L.cvae_plan_pass.argtypes = [C.POINTER(NetDesc), C.c_int, C.c_int, C.c_int]
         L.cvae_plan_pass_deep.restype = C.c_int
         L.cvae_plan_pass_deep.argtypes = [C.POINTER(NetDesc), C.c_int, C.c_int, C.c_int, C.c_int]
+        if hasattr(L, "cvae_plan_pass_deep_tiles"):      # (ADDITIVE, below)
+            L.cvae_plan_pass_deep_tiles.restype = C.c_int
+            L.cvae_plan_pass_deep_tiles.argtypes = [C.POINTER(NetDesc), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32 * 4)]
         L.cvae_gru_rnn_forward_deep.restype = C.c_int
         L.cvae_gru_rnn_forward_deep.argtypes = [C.POINTER(NetDesc), C.c_int, _fp, C.POINTER(PassInput), _fp, _fp, C.c_int, C.c_int,
                                                 C.c_int, _fp, _fp, _fp, _fp, C.c_size_t, C.c_int, _fp]
@@ -372,7 +379,7 @@ class CvaeLib(object):
         L.cvae_ctx_destroy.restype = C.c_int
         L.cvae_ctx_destroy.argtypes = [C.c_void_p]
         for name in EXPORTS:
-            if name not in NO_CONTEXT:
+            if name not in NO_CONTEXT and (name not in ADDITIVE or hasattr(L, name)):
                 fn = getattr(L, name)
                 fn.argtypes = [C.c_void_p] + list(fn.argtypes or [])
         return L
@@ -490,6 +497,15 @@ class CvaeLib(object):
         if rc < 0:
             self._check(rc, "cvae_plan_pass_deep")
         return rc
+
+    def plan_pass_deep_tiles(self, d, n_layers, B, T, flags=0):
+        """[path, Bp, rts, tiles]: the whole plan cvae_plan_pass_deep reports the path of (tiles: the most row tiles one block handles
+        per frame -- 32-row tiles on the resident kernel, 16-row tiles on the any-H kernel)."""
+        if not hasattr(self.lib, "cvae_plan_pass_deep_tiles"):
+            raise CvaeError("%s was built before cvae_plan_pass_deep_tiles was added: rebuild it" % self.path)
+        out = (C.c_int32 * 4)()
+        self._check(self.lib.cvae_plan_pass_deep_tiles(C.byref(d), n_layers, B, T, flags, C.byref(out)), "cvae_plan_pass_deep_tiles")
+        return list(out)
 
     def gru_rnn_forward_deep(self, d, n_layers, prepared, pin, y_in, h_in, B, T, clamp_lat_dim, trj_out, y_last, h_last, ws, ws_bytes,
                              flags=0, stream=0):
@@ -755,4 +771,4 @@ EXPORTS = ("cvae_last_error_string", "cvae_abi_version", "cvae_ctx_create", "cva
            "cvae_dtw_batch_work_bytes", "cvae_dtw_batch", "cvae_eval_stats", "cvae_latent_mean",
            "cvae_mc2e_batch_work_bytes", "cvae_mc2e_batch", "cvae_decode_jobs", "cvae_trainlog_window",
            "cvae_net_prepared_bytes_deep", "cvae_net_prepare_scratch_bytes_deep", "cvae_net_prepare_deep", "cvae_pass_workspace_bytes_deep",
-           "cvae_plan_pass", "cvae_plan_pass_deep", "cvae_gru_rnn_forward_deep", "cvae_net_prepared_in_range")
+           "cvae_plan_pass", "cvae_plan_pass_deep", "cvae_plan_pass_deep_tiles", "cvae_gru_rnn_forward_deep", "cvae_net_prepared_in_range")

@@ -36,9 +36,15 @@ DeepPrep deep_prep_layout(const Dims& m, int L) {
 //             at most four 32-row tiles per block
 //   GENERIC   k_gru_steps_deep as ONE launch: any H % 16 == 0, any L, H/4 blocks resident (H <= 1024 on 256 CUs)
 //   PER_STEP  the same kernel, one launch per sub-step: what is left (H = 2048; callers without CVAE_FLAG_PERSISTENT)
+// The four-tile cap.  A resident block (layer l, octet c, tile set ti of `rts` sets in flight) takes the row tiles ti, ti + rts, ..
+// of every frame, and keeps the state it carries from frame to frame -- h_{l,t-1} of its thread's (row, unit), per tile -- in the
+// four registers hk0 .. hk3 of k_gru_steps_deep3.  So a block can own at most four tiles: ceil(Bp/32 / rts) <= 4, and a pass with
+// more rows than 4 * rts * 32 takes the any-H kernel.  `tiles` is that largest count (block ti = 0 has it); cvae_plan_pass_deep_tiles
+// reports the whole plan.
 enum { DEEP_PER_STEP = 0, DEEP_GENERIC = 1, DEEP_RESIDENT = 2 };
 struct DeepPlan {
     int path, Bp, rts;
+    int tiles;      // RESIDENT: most 32-row tiles one block owns; else the 16-row tiles a block of k_gru_steps_deep walks, four a trip
 };
 
 DeepPlan plan_deep_pass(const Dims& m, int L, int B, int T, int flags) {
@@ -46,15 +52,17 @@ DeepPlan plan_deep_pass(const Dims& m, int L, int B, int T, int flags) {
     pn.Bp = (int)up(B, 32);
     pn.rts = 1;
     pn.path = DEEP_PER_STEP;
+    pn.tiles = pn.Bp / 16;
     const int cus = cu_count();
     if (!(flags & CVAE_FLAG_PERSISTENT)) return pn;
     const int nrt32 = pn.Bp / 32, NB = m.H / 8;
     const long mtot = (long)(T + 1) * pn.Bp;
     if (!(flags & CVAE_FLAG_GENERIC_STEP) && deep3_ok(m) && cus >= L * NB && (long)L * m.nch * mtot * 80 < (1L << 31)) {
         const int rts = row_tiles_per_block(cus, L * NB, nrt32);
-        if ((nrt32 + rts - 1) / rts <= 4) {
+        if ((nrt32 + rts - 1) / rts <= 4) {      // hk0 .. hk3 (above)
             pn.path = DEEP_RESIDENT;
             pn.rts = rts;
+            pn.tiles = (nrt32 + rts - 1) / rts;
             return pn;
         }
     }
@@ -257,6 +265,17 @@ int cvae_plan_pass_deep(cvae_ctx* ctx, const cvae_net_desc* d, int n_layers, int
     if (int rc = deep_layers_ok(n_layers)) return rc;
     if (n_layers < 2 || B < 1 || T < 1) return fail(-1, "bad sizes: n_layers=%d B=%d T=%d", n_layers, B, T);
     return plan_deep_pass(m, n_layers, B, T, flags).path;
+}
+
+int cvae_plan_pass_deep_tiles(cvae_ctx* ctx, const cvae_net_desc* d, int n_layers, int B, int T, int flags, int32_t out[4]) {
+    CVAE_ENTER(ctx);
+    Dims m;
+    if (int rc = make_dims(d, &m)) return rc;
+    if (int rc = deep_layers_ok(n_layers)) return rc;
+    if (n_layers < 2 || B < 1 || T < 1 || !out) return fail(-1, "bad arguments: n_layers=%d B=%d T=%d out=%p", n_layers, B, T, (void*)out);
+    const DeepPlan pn = plan_deep_pass(m, n_layers, B, T, flags);
+    out[0] = pn.path; out[1] = pn.Bp; out[2] = pn.rts; out[3] = pn.tiles;
+    return 0;
 }
 
 int cvae_gru_rnn_forward_deep(cvae_ctx* ctx, const cvae_net_desc* d, int n_layers, const void* prepared, const cvae_pass_input* in,

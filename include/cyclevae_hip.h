@@ -415,6 +415,10 @@ int cvae_gru_rnn_forward_stacked_carry(cvae_ctx* ctx, const cvae_net_desc* d, co
  * n_layers == 1: each of these entry points IS its one-layer counterpart (same image, same workspace, same kernels; `upper` unused).
  * cvae_plan_pass_deep reports the recurrence a pass would take: 0 one launch per sub-step, 1 the any-H kernel as one launch,
  * 2 the resident exact-operand kernel (H = 1024 or 64, n_layers * H/8 blocks resident); negative = error.
+ * cvae_plan_pass_deep_tiles (additive, tests): the whole plan of the same rule, out (HOST int32[4]) = {path as above, Bp = rows
+ * padded to 32, rts = row-tile sets in flight (1 off the resident kernel), tiles = the most row tiles one block handles per frame:
+ * 32-row tiles of a resident block, ceil(Bp/32 / rts) <= 4 (a block carries its tiles' states in four registers; more rows than that
+ * take the any-H kernel), else the Bp/16 16-row tiles every block of the any-H kernel walks, four a trip}.  Returns 0 or an error.
  */
 typedef struct cvae_gru_layer {
     const float* w_ih;  /* gru.weight_ih_l{l}  [3H, H]  */
@@ -428,6 +432,7 @@ int cvae_net_prepare_deep(cvae_ctx* ctx, const cvae_net_desc* d, int n_layers, c
                           void* prepared, size_t prepared_bytes, void* scratch, size_t scratch_bytes, void* stream);
 size_t cvae_pass_workspace_bytes_deep(cvae_ctx* ctx, const cvae_net_desc* d, int n_layers, int B, int T);
 int cvae_plan_pass_deep(cvae_ctx* ctx, const cvae_net_desc* d, int n_layers, int B, int T, int flags);
+int cvae_plan_pass_deep_tiles(cvae_ctx* ctx, const cvae_net_desc* d, int n_layers, int B, int T, int flags, int32_t out[4]);
 int cvae_gru_rnn_forward_deep(cvae_ctx* ctx, const cvae_net_desc* d, int n_layers, const void* prepared, const cvae_pass_input* in,
                               const float* y_in, const float* h_in, int B, int T, int clamp_lat_dim, float* trj_out, float* y_last,
                               float* h_last, void* workspace, size_t workspace_bytes, int flags, void* stream);

@@ -23,6 +23,7 @@ def test_header_binding_and_library_agree():
     names = declared_functions()
     assert len(names) >= 20
     assert sorted(_cabi.EXPORTS) == names, (sorted(set(names) - set(_cabi.EXPORTS)), sorted(set(_cabi.EXPORTS) - set(names)))
+    assert set(_cabi.ADDITIVE) <= set(_cabi.EXPORTS)      # optional when an older build of the same ABI loads, never in this one
     lib = ctypes.CDLL(LIB)
     for n in names:
         assert hasattr(lib, n), "libcyclevae_hip.so does not export " + n
@@ -40,6 +41,23 @@ def test_size_queries_answer_without_a_gpu():
     with pytest.raises(_cabi.CvaeError):
         lib.prepared_bytes(bad)
     assert lib.lib.cvae_last_error_string() not in (None, b"")
+
+
+def test_deep_plan_query_answers_without_a_gpu():
+    """cvae_plan_pass_deep_tiles on the shipped library: the path cvae_plan_pass_deep reports, Bp, and a tiling that covers Bp (which
+    one depends on the device's CU count: tests/stacked_cases.py holds every case to the MI355X's)."""
+    import pytest
+    lib = _cabi.CvaeLib(LIB)
+    d = lib.desc(6, 8, 64, 3, 2, True, False)
+    for flags in (0, _cabi.FLAG_PERSISTENT, _cabi.FLAG_PERSISTENT | _cabi.FLAG_GENERIC_STEP):
+        path, Bp, rts, tiles = lib.plan_pass_deep_tiles(d, 2, 70, 3, flags)
+        assert path == lib.plan_pass_deep(d, 2, 70, 3, flags) and Bp == 96
+        if path == _cabi.DEEP_RESIDENT:
+            assert 1 <= rts <= 3 and tiles == -(-3 // rts) <= 4
+        else:
+            assert (rts, tiles) == (1, 6)
+    with pytest.raises(_cabi.CvaeError):
+        lib.plan_pass_deep_tiles(d, 1, 70, 3, 0)
 
 
 def test_recurrent_kernels_do_not_spill():
