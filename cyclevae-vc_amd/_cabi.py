@@ -18,6 +18,18 @@ FLAG_EXACT3 = 512
 STATUS_RANGE = 7        # CVAE_STATUS_RANGE: an operand of a limb-operand eval kernel was outside the window of its fp16 limbs (ABI 8)
 STATUS_RANGE_WORD = 3   # the status word that carries it (word 0: time-outs, status 5)
 CLAMP_LAPLACE = 1 << 30     # OR into a clamp_lat_dim argument: clamp_vae_laplace's floor (gru_vae.py:417) instead of ln(1e-6)
+DRAW_LAPLACE = 1 << 30      # OR into a lat_dim argument (pass_input, cycle_forward*, latent_mean, sample_cat*, stage4_loss): the Laplace
+                            # posterior -- z = mu + exp(s) * u(eps), loss_vae_laplace's KL (gru_vae.py:101-112, :130-139)
+POSTERIORS = ("gauss", "laplace")
+
+
+def posterior_flags(posterior, lat_dim):
+    """(lat_dim argument of the draws and the loss, clamp_lat_dim argument of the encoder passes) of a posterior choice."""
+    if posterior not in POSTERIORS:
+        raise ValueError("posterior=%r: expected one of %s" % (posterior, ", ".join(repr(p) for p in POSTERIORS)))
+    if posterior == "laplace":
+        return lat_dim | DRAW_LAPLACE, lat_dim | CLAMP_LAPLACE
+    return lat_dim, lat_dim
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.environ.get("CYCLEVAE_LIB") or os.path.join(_HERE, "libcyclevae_hip.so")   # (variable: A/B builds of the same library)

@@ -62,6 +62,31 @@ __device__ __forceinline__ float cvae_randn(uint64_t seed, uint64_t draw, uint64
     return (dim & 1) ? zs : zc;
 }
 
+// The Laplace posterior of the sibling recipes (sampling_vae_laplace, gru_vae.py:101-112; CVAE_DRAW_LAPLACE in a lat_dim argument):
+// one standard Laplace variate from e in (-0.5, 0.5) by the inverse CDF, u(e) = -sign(e) * log1p(-2|e|), so that the draw is
+// z = mu + exp(log_scale) * u.  e is supplied (the reference's uniform in (-0.4999, 0.5)) or comes from the Philox block of
+// (frame, dim quad, draw): word dim & 3, mapped and clamped as k_sample_laplace does -- the same bits for the same key.
+__device__ __forceinline__ float cvae_laplace_u(float e) {
+    const float sgn = e > 0.f ? 1.f : (e < 0.f ? -1.f : 0.f);
+    return -sgn * log1pf(-2.0f * fabsf(e));
+}
+__device__ __forceinline__ float cvae_laplace_unif(uint32_t w) {
+    const float e = -0.4999f + 0.9999f * (((float)w + 0.5f) * 2.3283064365386963e-10f);
+    return fminf(fmaxf(e, -0.4999f), 0.49999997f);
+}
+__device__ __forceinline__ void cvae_laplace4(uint64_t seed, uint64_t draw, uint64_t frame, uint32_t quad, float u[4]) {
+    uint32_t o[4];
+    cvae_philox((uint32_t)frame, quad, (uint32_t)draw, (uint32_t)(frame >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), o);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) u[j] = cvae_laplace_u(cvae_laplace_unif(o[j]));
+}
+// the uniform of one dim (what k_sample_laplace leaves in eps_out)
+__device__ __forceinline__ float cvae_laplace_eps(uint64_t seed, uint64_t draw, uint64_t frame, uint32_t dim) {
+    uint32_t o[4];
+    cvae_philox((uint32_t)frame, dim >> 2, (uint32_t)draw, (uint32_t)(frame >> 32), (uint32_t)seed, (uint32_t)(seed >> 32), o);
+    return cvae_laplace_unif(o[dim & 3]);
+}
+
 // ------------------------------------------------------------------------------------------------------
 // prepare-time kernels (run when the weights change)
 // ------------------------------------------------------------------------------------------------------
@@ -235,6 +260,8 @@ struct ProCell {
 struct ProParams {
     ProCell cell[CVAE_MAX_CELLS];
     int ncell, L;
+    unsigned laplace;    // bit c: cell c draws from the Laplace posterior (CVAE_DRAW_LAPLACE in its lat_dim): z = mu + exp(s) * u, not
+                         //   mu + exp(s/2) * eps (a mask here, not a field of ProCell: 32 cells of 120 bytes would pass the 4 KiB)
     uint64_t frame0;     // global frame index of this pass's (row 0, frame 0): draw-origin row * T
     const float* sin_w;  // [C][C] or null
     const float* sin_b;
@@ -294,8 +321,9 @@ static_assert(sizeof(ProParams) <= 4096, "ProParams is a kernel argument: 4 KiB 
 //              recurrent matrix assumes y_{-1} = out_1(h_{-1})
 //   zeroing  : xnp slack read by the K padding, barrier / flag words
 // one value of a pass's input row: [seg0 ; seg1 | z] (z: reparameterised draw, single or the mean of n_draws)
-// emean: null, or the block's mean draw per latent dim (cvae_mean_draws)
-__device__ __forceinline__ float cvae_input_value(const ProParams& p, const ProCell& c, int b, int t, int q, const float* emean = nullptr) {
+// emean: null, or the block's mean draw per latent dim (cvae_mean_draws); lap: the cell's bit of p.laplace
+__device__ __forceinline__ float cvae_input_value(const ProParams& p, const ProCell& c, bool lap, int b, int t, int q,
+                                                  const float* emean = nullptr) {
     const long fr = (long)b * p.T + t;
     if (q < c.seg0.width) return c.seg0.ptr[fr * c.seg0.row_stride + q];
     if (!c.lat) return c.seg1.ptr[fr * c.seg1.row_stride + (q - c.seg0.width)];
@@ -306,20 +334,29 @@ __device__ __forceinline__ float cvae_input_value(const ProParams& p, const ProC
     } else if (c.n_draws > 1) {    // mean of the draws (decode_gru-cyclevae_gauss.py:304-305: mean of n_smpl_dec samples)
         e = 0.0f;
         const long es = c.eps_stride ? c.eps_stride : (long)p.B * p.T * p.L;
-        for (int k = 0; k < c.n_draws; ++k)
-            e += c.eps ? c.eps[(long)k * es + fr * p.L + l]
-                       : cvae_randn(c.seed, c.draw + (uint64_t)k, (uint64_t)(fr + c.draw_frame0) + p.frame0, (uint32_t)l);
+        if (lap)
+            for (int k = 0; k < c.n_draws; ++k)
+                e += cvae_laplace_u(c.eps ? c.eps[(long)k * es + fr * p.L + l]
+                                          : cvae_laplace_eps(c.seed, c.draw + (uint64_t)k, (uint64_t)(fr + c.draw_frame0) + p.frame0, (uint32_t)l));
+        else
+            for (int k = 0; k < c.n_draws; ++k)
+                e += c.eps ? c.eps[(long)k * es + fr * p.L + l]
+                           : cvae_randn(c.seed, c.draw + (uint64_t)k, (uint64_t)(fr + c.draw_frame0) + p.frame0, (uint32_t)l);
         e *= 1.0f / (float)c.n_draws;
+    } else if (lap) {
+        e = cvae_laplace_u(c.eps ? c.eps[fr * p.L + l]
+                                 : cvae_laplace_eps(c.seed, c.draw, (uint64_t)(fr + c.draw_frame0) + p.frame0, (uint32_t)l));
     } else {
         e = c.eps ? c.eps[fr * p.L + l] : cvae_randn(c.seed, c.draw, (uint64_t)(fr + c.draw_frame0) + p.frame0, (uint32_t)l);
     }
-    return c.lat[fr * 2 * p.L + l] + expf(c.lat[fr * 2 * p.L + p.L + l] * 0.5f) * e;
+    const float s = c.lat[fr * 2 * p.L + p.L + l];      // log-variance, or the Laplace posterior's log-scale
+    return c.lat[fr * 2 * p.L + l] + expf(lap ? s : s * 0.5f) * e;
 }
 
 // The mean of a frame's n_draws draws with all 256 threads of a block: slice s of the draws (k = s, s + nsl, ...) per latent dim
 // in parallel, the slices added in fixed order (300 Philox + Box-Muller evaluations in one lane made the stage-6 prologue 540 us).
 // part: [256] floats, emean: [L] floats of LDS.  Every thread of the block must call it.
-__device__ __forceinline__ void cvae_mean_draws(const ProParams& p, const ProCell& c, int b, int t, float* part, float* emean) {
+__device__ __forceinline__ void cvae_mean_draws(const ProParams& p, const ProCell& c, bool lap, int b, int t, float* part, float* emean) {
     // thread = (dim quad, slice of the draws); part: [256 / (L/4) slices][L] floats (<= 1024), emean: [L]; L % 4 == 0
     const int tid = threadIdx.x, L = p.L, nq = L >> 2, nsl = 256 / nq, qd = tid % nq, sl = tid / nq;
     const long fr = (long)b * p.T + t;
@@ -331,6 +368,9 @@ __device__ __forceinline__ void cvae_mean_draws(const ProParams& p, const ProCel
             if (c.eps) {
                 const float* ep = c.eps + (long)k * es + fr * p.L + 4 * qd;
                 z[0] = ep[0]; z[1] = ep[1]; z[2] = ep[2]; z[3] = ep[3];
+                if (lap) { z[0] = cvae_laplace_u(z[0]); z[1] = cvae_laplace_u(z[1]); z[2] = cvae_laplace_u(z[2]); z[3] = cvae_laplace_u(z[3]); }
+            } else if (lap) {
+                cvae_laplace4(c.seed, c.draw + (uint64_t)k, (uint64_t)(fr + c.draw_frame0) + p.frame0, (uint32_t)qd, z);
             } else {
                 cvae_randn4(c.seed, c.draw + (uint64_t)k, (uint64_t)(fr + c.draw_frame0) + p.frame0, (uint32_t)qd, z);
             }
@@ -369,6 +409,7 @@ __global__ void k_prologue(ProParams p) {
                 if (bb >= p.ncell * p.B) continue;
                 const ProCell& c = p.cell[bb / p.B];
                 if (!c.lat || c.n_draws <= 1 || !CVAE_FRAME_VALID(p, c, t)) continue;
+                const bool lap = (p.laplace >> (bb / p.B)) & 1u;
                 const long fr = (long)(bb % p.B) * p.T + t, es = c.eps_stride ? c.eps_stride : (long)p.B * p.T * p.L;
                 float e[4] = {0.f, 0.f, 0.f, 0.f};
                 for (int k = 0; k < c.n_draws; ++k) {
@@ -376,6 +417,9 @@ __global__ void k_prologue(ProParams p) {
                     if (c.eps) {
                         const float* ep = c.eps + (long)k * es + fr * p.L + 4 * qd;
                         z[0] = ep[0]; z[1] = ep[1]; z[2] = ep[2]; z[3] = ep[3];
+                        if (lap) { z[0] = cvae_laplace_u(z[0]); z[1] = cvae_laplace_u(z[1]); z[2] = cvae_laplace_u(z[2]); z[3] = cvae_laplace_u(z[3]); }
+                    } else if (lap) {
+                        cvae_laplace4(c.seed, c.draw + (uint64_t)k, (uint64_t)(fr + c.draw_frame0) + p.frame0, (uint32_t)qd, z);
                     } else {
                         cvae_randn4(c.seed, c.draw + (uint64_t)k, (uint64_t)(fr + c.draw_frame0) + p.frame0, (uint32_t)qd, z);
                     }
@@ -392,7 +436,8 @@ __global__ void k_prologue(ProParams p) {
             float v = 0.0f;
             if (bb < p.ncell * p.B) {
                 const ProCell& c = p.cell[bb / p.B];
-                if (CVAE_FRAME_VALID(p, c, t)) v = cvae_input_value(p, c, bb % p.B, t, q, quads ? tmean + r * p.L : nullptr);
+                if (CVAE_FRAME_VALID(p, c, t))
+                    v = cvae_input_value(p, c, (p.laplace >> (bb / p.B)) & 1u, bb % p.B, t, q, quads ? tmean + r * p.L : nullptr);
             }
             raw[r * (p.C + 1) + q] = v;
         }
@@ -475,7 +520,7 @@ __global__ void k_prologue(ProParams p) {
             const ProCell& c = p.cell[bb / p.B];
             if (c.lat && c.n_draws > 1 && p.L <= 256 && (p.L & 3) == 0 && CVAE_FRAME_VALID(p, c, t)) {
                 float* part = (float*)CVAE_SMEM + p.C;
-                cvae_mean_draws(p, c, bb % p.B, t, part, part + 1024);
+                cvae_mean_draws(p, c, (p.laplace >> (bb / p.B)) & 1u, bb % p.B, t, part, part + 1024);
                 emean = part + 1024;
             }
         }
@@ -490,7 +535,7 @@ __global__ void k_prologue(ProParams p) {
         const bool valid = real_row && CVAE_FRAME_VALID(p, c, t);
         const long fr = (long)b * p.T + t;
         if (valid)
-            for (int q = tid; q < p.C; q += 64) row[q] = cvae_input_value(p, c, b, t, q, emean);
+            for (int q = tid; q < p.C; q += 64) row[q] = cvae_input_value(p, c, (p.laplace >> ci) & 1u, b, t, q, emean);
         __syncthreads();
         bool bad = false;
         for (int q = tid; q < p.Cp; q += 64) {

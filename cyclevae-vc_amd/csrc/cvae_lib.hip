@@ -163,6 +163,10 @@ inline long up(long x, long m) { return (x + m - 1) / m * m; }
 // log-scale floor of the Laplace variant (clamp_vae_laplace, gru_vae.py:417)
 inline int clamp_dim(int v) { return v < 0 ? -1 : (v & ~CVAE_CLAMP_LAPLACE); }
 inline float clamp_floor(int v) { return v >= 0 && (v & CVAE_CLAMP_LAPLACE) ? -7.2543288692621097f : -13.815510557964274f; }
+// lat_dim argument of the draws and of the stage-4 loss: L, or L | CVAE_DRAW_LAPLACE for the Laplace posterior (sampling_vae_laplace /
+// loss_vae_laplace, gru_vae.py:101-112, :130-139)
+inline int draw_dim(int v) { return v < 0 ? v : (v & ~CVAE_DRAW_LAPLACE); }
+inline bool draw_laplace(int v) { return v >= 0 && (v & CVAE_DRAW_LAPLACE) != 0; }
 inline unsigned nblk(long n, int per) { return (unsigned)((n + per - 1) / per); }
 
 struct Dims {
@@ -617,7 +621,7 @@ int check_cells(const Dims& m, const PassRows& r) {
     if (ncell > CVAE_MAX_CELLS) return fail(-1, "at most %d stacked cells per pass", CVAE_MAX_CELLS);
     for (int c = 0; c < ncell; ++c) {
         const cvae_pass_input* in = cells[c].in;
-        const int w_in = in->seg0.width + (in->lat ? in->lat_dim : in->seg1.width);
+        const int w_in = in->seg0.width + (in->lat ? draw_dim(in->lat_dim) : in->seg1.width);
         if (w_in != m.C) return fail(-1, "cell %d: pass input width %d != in_dim %d", c, w_in, m.C);
         if (in->frames < 0 || in->frames > T) return fail(-1, "cell %d: frames %d outside [0, T=%d]", c, in->frames, T);
         if (in->ctx_before < 0 || in->ctx_after < 0 || in->draw_frame0 < 0 || in->eps_draw_stride < 0)
@@ -675,7 +679,8 @@ void run_prologue(const Dims& m, const cvae_net_desc* d, const float* P, const P
         pp.cell[c].n_draws = in->n_draws;
         pp.cell[c].ctx_before = in->ctx_before; pp.cell[c].ctx_after = in->ctx_after;
         pp.cell[c].draw_frame0 = (long)in->draw_frame0; pp.cell[c].eps_stride = (long)in->eps_draw_stride;
-        if (in->lat) pp.L = in->lat_dim;
+        if (in->lat) pp.L = draw_dim(in->lat_dim);
+        if (in->lat && draw_laplace(in->lat_dim)) pp.laplace |= 1u << c;
     }
     pp.ncell = ncell;
     pp.frame0 = (uint64_t)cx().draw_row0 * (uint64_t)T;
@@ -1267,9 +1272,13 @@ size_t cvae_cycle_workspace_bytes(cvae_ctx* ctx, const cvae_net_desc* enc, const
 static int cycle_forward_impl(const cvae_net_desc* enc, const void* enc_prepared, const cvae_net_desc* dec,
                        const void* dec_prepared, const float* x, const float* cvx, int stdim, const float* code_src,
                        const float* code_trg, int ncode, const float* y_in_enc, const float* y_in_dec, int B, int T,
-                       int n_cyc, int lat_dim, const float* eps, uint64_t seed, float* out_lat, float* out_rec,
+                       int n_cyc, int lat_dim_arg, const float* eps, uint64_t seed, float* out_lat, float* out_rec,
                        float* out_cv, float* out_latcv, float* out_reccyc, void* workspace, size_t workspace_bytes,
                        int flags, void* stream, const cvae_cycle_state* sin, const cvae_cycle_state* sout) {
+    // lat_dim_arg: L, or L | CVAE_DRAW_LAPLACE -- the three draws of a cycle are then Laplace draws (the flag travels in the decoder
+    // passes' cvae_pass_input.lat_dim) and the encoder passes clamp at the Laplace floor
+    const int lat_dim = draw_dim(lat_dim_arg);
+    const int enc_clamp = draw_laplace(lat_dim_arg) ? (lat_dim | CVAE_CLAMP_LAPLACE) : lat_dim;
     Dims me, md;
     if (int rc = make_dims(enc, &me)) return rc;
     if (int rc = make_dims(dec, &md)) return rc;
@@ -1321,13 +1330,13 @@ static int cycle_forward_impl(const cvae_net_desc* enc, const void* enc_prepared
         }
         {
             const Cell c{&in, sin ? ye(sin, i, 0) : y_in_enc, he(sin, i, 0), lat, ye(sout, i, 0), he(sout, i, 0)};
-            if ((rc = run_pass(me, enc, (const float*)enc_prepared, &c, 1, B, T, lat_dim, pws, status, flags, st, i == 0))) return rc;
+            if ((rc = run_pass(me, enc, (const float*)enc_prepared, &c, 1, B, T, enc_clamp, pws, status, flags, st, i == 0))) return rc;
         }
         // rec = D([code_src ; z1]) and cv = D([code_trg ; z2]) share the decoder and do not depend on each other
         // (train...:1335-1336): one stacked pass, 2B rows
         memset(&in, 0, sizeof(in));
         in.seg0 = cvae_seg{code_src, ncode, ncode};
-        in.lat = lat; in.lat_dim = lat_dim;
+        in.lat = lat; in.lat_dim = lat_dim_arg;
         in.eps = eps ? eps + (i * 3 + 0) * neps : nullptr;
         in.seed = seed; in.draw_id = (uint64_t)(i * 3 + 0);
         in2 = in;
@@ -1345,12 +1354,12 @@ static int cycle_forward_impl(const cvae_net_desc* enc, const void* enc_prepared
         in.seg1 = cvae_seg{cv, md.Co, md.Co};
         {
             const Cell c{&in, sin ? ye(sin, i, 1) : y_in_enc, he(sin, i, 1), latcv, ye(sout, i, 1), he(sout, i, 1)};
-            if ((rc = run_pass(me, enc, (const float*)enc_prepared, &c, 1, B, T, lat_dim, pws, status, flags, st))) return rc;
+            if ((rc = run_pass(me, enc, (const float*)enc_prepared, &c, 1, B, T, enc_clamp, pws, status, flags, st))) return rc;
         }
         // rec_cyc = D([code_src ; z3])                            (train...:1338)
         memset(&in, 0, sizeof(in));
         in.seg0 = cvae_seg{code_src, ncode, ncode};
-        in.lat = latcv; in.lat_dim = lat_dim;
+        in.lat = latcv; in.lat_dim = lat_dim_arg;
         in.eps = eps ? eps + (i * 3 + 2) * neps : nullptr;
         in.seed = seed; in.draw_id = (uint64_t)(i * 3 + 2);
         {

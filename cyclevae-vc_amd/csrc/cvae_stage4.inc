@@ -5,6 +5,7 @@
 namespace {
 
 // out[p*B + b][t] = [ code_p[b][t][:ncode] ; mu + exp(s/2) * eps_p ]   for p < parts (rec || cv stacked along the batch axis)
+// laplace: [ code ; mu + exp(s) * u(eps_p) ] with eps_p the uniform of sampling_vae_laplace (cvae_laplace_u, cvae_kernels.h)
 struct SampleCatParams {
     const float* lat;          // [B][T][2L]
     const float* code[2];      // [B][T][ncode]
@@ -12,7 +13,7 @@ struct SampleCatParams {
     uint64_t seed, draw[2], frame0;
     float* out;                // [parts*B][T][ncode + L]
     float* eps_out;            // [parts][B][T][L]: the eps used (the backward needs them)
-    int B, T, L, ncode, parts;
+    int B, T, L, ncode, parts, laplace;
 };
 
 __global__ void k_sample_cat(SampleCatParams p) {
@@ -29,25 +30,35 @@ __global__ void k_sample_cat(SampleCatParams p) {
         return;
     }
     const int l = c - p.ncode;
+    if (p.laplace) {
+        const float e = p.eps_in[part] ? p.eps_in[part][bt * p.L + l]
+                                       : cvae_laplace_eps(p.seed, p.draw[part], (uint64_t)bt + p.frame0, (uint32_t)l);
+        p.eps_out[((long)part * p.B * p.T + bt) * p.L + l] = e;
+        p.out[idx] = p.lat[bt * 2 * p.L + l] + expf(p.lat[bt * 2 * p.L + p.L + l]) * cvae_laplace_u(e);
+        return;
+    }
     const float e = p.eps_in[part] ? p.eps_in[part][bt * p.L + l] : cvae_randn(p.seed, p.draw[part], (uint64_t)bt + p.frame0, (uint32_t)l);
     p.eps_out[((long)part * p.B * p.T + bt) * p.L + l] = e;
     p.out[idx] = p.lat[bt * 2 * p.L + l] + expf(p.lat[bt * 2 * p.L + p.L + l] * 0.5f) * e;
 }
 
 // d lat[b][t][l] = sum_p dout[p][b][t][ncode + l];   d lat[b][t][L + l] = sum_p dout[..] * eps_p * 0.5 * exp(s/2)
+// laplace: d lat[b][t][L + l] = sum_p dout[..] * u(eps_p) * exp(s)
 __global__ void k_sample_cat_bwd(const float* dout, const float* lat, const float* eps, float* dlat, int B, int T, int L, int ncode,
-                                 int parts) {
+                                 int parts, int laplace) {
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (long)B * T * L) return;
     const int l = (int)(idx % L);
     const long bt = idx / L;
     const int W = ncode + L;
-    const float hs = 0.5f * expf(lat[bt * 2 * L + L + l] * 0.5f);
+    const float sv = lat[bt * 2 * L + L + l];
+    const float hs = laplace ? expf(sv) : 0.5f * expf(sv * 0.5f);
     float dm = 0.f, ds = 0.f;
     for (int part = 0; part < parts; ++part) {
         const float g = dout[((long)part * B * T + bt) * W + ncode + l];
+        const float e = eps[((long)part * B * T + bt) * L + l];
         dm += g;
-        ds += g * eps[((long)part * B * T + bt) * L + l] * hs;
+        ds += g * (laplace ? cvae_laplace_u(e) : e) * hs;
     }
     dlat[bt * 2 * L + l] = dm;
     dlat[bt * 2 * L + L + l] = ds;
@@ -57,6 +68,8 @@ __global__ void k_sample_cat_bwd(const float* dout, const float* lat, const floa
 //   w[b][t]      = 1/n_j for the first n_j frames of a selected utterance, else 0   (mean over frames, sum over utterances)
 //   loss(b,t)    = w * ( K * (|rec - tgt|_1 + |reccyc - tgt|_1) + kl_scale * KL(lat) + latcv_w[b] * KL(latcv) )
 //   K = 10/ln10 * sqrt2 (gru_vae.py:525), KL = 0.5 sum (exp(s) + mu^2 - s - 1) (gru_vae.py:123)
+//   laplace: KL = sum (-s + b exp(-|mu|/b) + |mu| - 1), b = exp(s) (loss_vae_laplace, gru_vae.py:130-139);
+//            d/d mu = sign(mu) (1 - exp(-|mu|/b)) with sign(0) = 0 as torch.abs differentiates, d/d s = -1 + exp(-|mu|/b) (b + |mu|)
 struct Stage4LossParams {
     const float *rec, *reccyc, *lat, *latcv;   // reccyc / latcv null: half cycle (train...:283-287)
     const float* x;                            // target = x[b][t][stdim : stdim + D]
@@ -64,7 +77,7 @@ struct Stage4LossParams {
     const float* w;                            // [B][T]
     const float* latcv_w;                      // [B]
     float kl_scale;
-    int B, T, D, L;
+    int B, T, D, L, laplace;
     float *d_rec, *d_reccyc, *d_lat, *d_latcv;
     float* frame_loss;                         // [B*T]
 };
@@ -73,6 +86,14 @@ __device__ __forceinline__ float cvae_wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) v += cvae_shfl(v, (int)((threadIdx.x & 63) ^ o));
     return v;
+}
+
+// one latent dim's Laplace KL term and its two derivatives
+__device__ __forceinline__ float cvae_kl_laplace(float mu, float s, float& dmu, float& dsc) {
+    const float b = expf(s), am = fabsf(mu), ex = expf(-am / b);
+    dmu = mu > 0.f ? 1.0f - ex : (mu < 0.f ? ex - 1.0f : 0.0f);
+    dsc = -1.0f + ex * (b + am);
+    return -s + b * ex + am - 1.0f;
 }
 
 __global__ __launch_bounds__(64) void k_stage4_loss(Stage4LossParams p) {
@@ -93,6 +114,18 @@ __global__ __launch_bounds__(64) void k_stage4_loss(Stage4LossParams p) {
         }
     }
     for (int l = lane; l < p.L; l += 64) {
+        if (p.laplace) {
+            float dmu, dsc;
+            acc += p.kl_scale * cvae_kl_laplace(p.lat[bt * 2 * p.L + l], p.lat[bt * 2 * p.L + p.L + l], dmu, dsc);
+            p.d_lat[bt * 2 * p.L + l] = wt * p.kl_scale * dmu;
+            p.d_lat[bt * 2 * p.L + p.L + l] = wt * p.kl_scale * dsc;
+            if (p.latcv) {
+                acc += wc * cvae_kl_laplace(p.latcv[bt * 2 * p.L + l], p.latcv[bt * 2 * p.L + p.L + l], dmu, dsc);
+                p.d_latcv[bt * 2 * p.L + l] = wt * wc * dmu;
+                p.d_latcv[bt * 2 * p.L + p.L + l] = wt * wc * dsc;
+            }
+            continue;
+        }
         {
             const float mu = p.lat[bt * 2 * p.L + l], s = p.lat[bt * 2 * p.L + p.L + l], es = expf(s);
             acc += p.kl_scale * 0.5f * (es + mu * mu - s - 1.0f);
@@ -246,6 +279,8 @@ int cvae_sample_cat(cvae_ctx* ctx, const float* lat, const float* code0, const f
                     uint64_t draw0, uint64_t draw1, int B, int T, int lat_dim, int ncode, int parts, float* out, float* eps_out,
                     void* stream) {
     CVAE_ENTER(ctx);
+    const int laplace = draw_laplace(lat_dim);
+    lat_dim = draw_dim(lat_dim);
     if (!lat || !code0 || !out || !eps_out || B < 1 || T < 1 || lat_dim < 1 || ncode < 0 || parts < 1 || parts > 2 ||
         (parts == 2 && !code1))
         return fail(-1, "cvae_sample_cat: bad argument");
@@ -253,7 +288,7 @@ int cvae_sample_cat(cvae_ctx* ctx, const float* lat, const float* code0, const f
     p.lat = lat; p.code[0] = code0; p.code[1] = code1; p.eps_in[0] = eps0; p.eps_in[1] = eps1;
     p.seed = seed; p.draw[0] = draw0; p.draw[1] = draw1;
     p.frame0 = (uint64_t)cx().draw_row0 * (uint64_t)T;     // Philox keyed by the GLOBAL frame (cvae_set_draw_origin)
-    p.out = out; p.eps_out = eps_out; p.B = B; p.T = T; p.L = lat_dim; p.ncode = ncode; p.parts = parts;
+    p.out = out; p.eps_out = eps_out; p.B = B; p.T = T; p.L = lat_dim; p.ncode = ncode; p.parts = parts; p.laplace = laplace;
     const long n = (long)parts * B * T * (ncode + lat_dim);
     hipLaunchKernelGGL((k_sample_cat), dim3(nblk(n, 256)), dim3(256), 0, (hipStream_t)stream, p);
     CVAE_HIP_OK(hipGetLastError());
@@ -263,10 +298,12 @@ int cvae_sample_cat(cvae_ctx* ctx, const float* lat, const float* code0, const f
 int cvae_sample_cat_backward(cvae_ctx* ctx, const float* dout, const float* lat, const float* eps, int B, int T, int lat_dim, int ncode, int parts,
                              float* dlat, void* stream) {
     CVAE_ENTER(ctx);
+    const int laplace = draw_laplace(lat_dim);
+    lat_dim = draw_dim(lat_dim);
     if (!dout || !lat || !eps || !dlat || B < 1 || T < 1 || lat_dim < 1 || ncode < 0 || parts < 1 || parts > 2)
         return fail(-1, "cvae_sample_cat_backward: bad argument");
     hipLaunchKernelGGL((k_sample_cat_bwd), dim3(nblk((long)B * T * lat_dim, 256)), dim3(256), 0, (hipStream_t)stream, dout, lat, eps, dlat,
-                       B, T, lat_dim, ncode, parts);
+                       B, T, lat_dim, ncode, parts, laplace);
     CVAE_HIP_OK(hipGetLastError());
     return 0;
 }
@@ -275,13 +312,15 @@ int cvae_stage4_loss(cvae_ctx* ctx, const float* rec, const float* reccyc, const
                      const float* w, const float* latcv_w, float kl_scale, int B, int T, int D, int lat_dim, float* d_rec,
                      float* d_reccyc, float* d_lat, float* d_latcv, float* frame_loss, float* loss, int accumulate, void* stream) {
     CVAE_ENTER(ctx);
+    const int laplace = draw_laplace(lat_dim);
+    lat_dim = draw_dim(lat_dim);
     if (!rec || !lat || !x || !w || !d_rec || !d_lat || !frame_loss || !loss || B < 1 || T < 1 || D < 1 || lat_dim < 1)
         return fail(-1, "cvae_stage4_loss: bad argument");
     if ((reccyc && !d_reccyc) || (latcv && (!d_latcv || !latcv_w))) return fail(-1, "cvae_stage4_loss: missing gradient / weight pointer");
     if (x_stride < stdim + D) return fail(-1, "cvae_stage4_loss: x_stride %d < stdim + D = %d", x_stride, stdim + D);
     Stage4LossParams p;
     p.rec = rec; p.reccyc = reccyc; p.lat = lat; p.latcv = latcv; p.x = x; p.x_stride = x_stride; p.stdim = stdim; p.w = w;
-    p.latcv_w = latcv_w; p.kl_scale = kl_scale; p.B = B; p.T = T; p.D = D; p.L = lat_dim;
+    p.latcv_w = latcv_w; p.kl_scale = kl_scale; p.B = B; p.T = T; p.D = D; p.L = lat_dim; p.laplace = laplace;
     p.d_rec = d_rec; p.d_reccyc = d_reccyc; p.d_lat = d_lat; p.d_latcv = d_latcv; p.frame_loss = frame_loss;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL((k_stage4_loss), dim3((unsigned)((long)B * T)), dim3(64), 0, st, p);

@@ -7,7 +7,7 @@ namespace {
 enum { LATMEAN_MAX_JOBS = 32 };      // jobs per launch: one row tile's worth of cells, like CVAE_MAX_CELLS
 struct LatMeanParams {
     cvae_latmean_job job[LATMEAN_MAX_JOBS];
-    int L, n_draws;
+    int L, n_draws, laplace;      // laplace: out = mu + exp(s) * mean_k u(eps_k) (CVAE_DRAW_LAPLACE in lat_dim)
     uint64_t seed;
 };
 static_assert(sizeof(LatMeanParams) <= 4096, "LatMeanParams is a kernel argument: 4 KiB at most");
@@ -28,7 +28,9 @@ __global__ __launch_bounds__(256) void k_latent_mean(LatMeanParams p) {
             float z[4] = {0.f, 0.f, 0.f, 0.f};
             if (jb.eps) {
                 const float* ep = jb.eps + ((long)k * jb.frames + t) * L + l0;
-                for (int j = 0; j < w; ++j) z[j] = ep[j];
+                for (int j = 0; j < w; ++j) z[j] = p.laplace ? cvae_laplace_u(ep[j]) : ep[j];
+            } else if (p.laplace) {
+                cvae_laplace4(p.seed, jb.draw_id + (uint64_t)k, (uint64_t)t, (uint32_t)qd, z);
             } else {
                 cvae_randn4(p.seed, jb.draw_id + (uint64_t)k, (uint64_t)t, (uint32_t)qd, z);
             }
@@ -36,7 +38,10 @@ __global__ __launch_bounds__(256) void k_latent_mean(LatMeanParams p) {
             for (int j = 0; j < 4; ++j) e[j] += z[j];
         }
         const float* row = jb.lat + t * 2 * L;
-        for (int j = 0; j < w; ++j) jb.out[t * L + l0 + j] = row[l0 + j] + expf(row[L + l0 + j] * 0.5f) * (e[j] * inv);
+        for (int j = 0; j < w; ++j) {
+            const float s = row[L + l0 + j];
+            jb.out[t * L + l0 + j] = row[l0 + j] + expf(p.laplace ? s : s * 0.5f) * (e[j] * inv);
+        }
     }
 }
 
@@ -46,6 +51,8 @@ extern "C" {
 
 int cvae_latent_mean(cvae_ctx* ctx, const cvae_latmean_job* jobs, int n_jobs, int lat_dim, int n_draws, uint64_t seed, void* stream) {
     CVAE_ENTER(ctx);
+    const int laplace = draw_laplace(lat_dim);
+    lat_dim = draw_dim(lat_dim);
     if (!jobs || n_jobs < 1 || lat_dim < 1 || n_draws < 1)
         return fail(-1, "cvae_latent_mean: bad argument (n_jobs=%d lat_dim=%d n_draws=%d)", n_jobs, lat_dim, n_draws);
     for (int q = 0; q < n_jobs; ++q)
@@ -62,6 +69,7 @@ int cvae_latent_mean(cvae_ctx* ctx, const cvae_latmean_job* jobs, int n_jobs, in
         }
         p.L = lat_dim;
         p.n_draws = n_draws;
+        p.laplace = laplace;
         p.seed = seed;
         const unsigned bx = nblk(items, 256) < 1024u ? nblk(items, 256) : 1024u;      // (grid-stride beyond: 32 jobs already fill the chip)
         hipLaunchKernelGGL((k_latent_mean), dim3(bx, n), dim3(256), 0, (hipStream_t)stream, p);

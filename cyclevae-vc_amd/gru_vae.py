@@ -990,10 +990,15 @@ class TWFSEloss(nn.Module):
 
 class CycleChain(object):
     """Fused n_cyc reconversion loop in eval form (the four hand-written copies of it in the reference's
-    train_gru_cyclevae_gauss_batch.py:1299-1338, 1491-1510, 856-885 collapse to one C-ABI call)."""
+    train_gru_cyclevae_gauss_batch.py:1299-1338, 1491-1510, 856-885 collapse to one C-ABI call).
+    posterior: "gauss" (the recipe: sampling_vae_batch draws, encoder outputs clamped as clamp_vae does) or "laplace" (the sibling
+    recipes: sampling_vae_laplace draws, eps then the uniform in (-0.4999, 0.5), and the clamp_vae_laplace floor), in the fresh, the
+    carry and the stacked-GRU form alike."""
 
-    def __init__(self, model_encoder, model_decoder, lat_dim, n_cyc=2):
+    def __init__(self, model_encoder, model_decoder, lat_dim, n_cyc=2, posterior="gauss"):
         self.enc, self.dec, self.lat_dim, self.n_cyc = model_encoder, model_decoder, lat_dim, n_cyc
+        self.posterior = posterior
+        self._draw_dim, self._clamp = _cabi.posterior_flags(posterior, lat_dim)     # (ValueError for an unknown posterior)
         self._ws = None
 
     def __call__(self, x, cvx, code_src, code_trg, y_in_enc, y_in_dec, eps=None, seed=None, outputs=True, state=None,
@@ -1042,7 +1047,7 @@ class CycleChain(object):
         if state is None and not return_state:
             lib.cycle_forward(de, ie.data_ptr(), dd, idd.data_ptr(), x.data_ptr(), cvx.data_ptr(), cvx.shape[2],
                               code_src.data_ptr(), code_trg.data_ptr(), code_src.shape[2], ye.data_ptr(), yd.data_ptr(),
-                              B, T, n, L, None if e is None else e.data_ptr(), _draw_seed() if seed is None else seed,
+                              B, T, n, self._draw_dim, None if e is None else e.data_ptr(), _draw_seed() if seed is None else seed,
                               p("lat"), p("rec"), p("cv"), p("latcv"), p("reccyc"), self._ws.data_ptr(), self._ws.numel(),
                               _flags(), _stream())
             return out
@@ -1059,7 +1064,7 @@ class CycleChain(object):
         ptrs = lambda d_: None if d_ is None else tuple(d_[k].data_ptr() for k in keys)
         lib.cycle_forward_carry(de, ie.data_ptr(), dd, idd.data_ptr(), x.data_ptr(), cvx.data_ptr(), cvx.shape[2],
                                 code_src.data_ptr(), code_trg.data_ptr(), code_src.shape[2], ye.data_ptr(), yd.data_ptr(),
-                                B, T, n, L, None if e is None else e.data_ptr(), _draw_seed() if seed is None else seed,
+                                B, T, n, self._draw_dim, None if e is None else e.data_ptr(), _draw_seed() if seed is None else seed,
                                 p("lat"), p("rec"), p("cv"), p("latcv"), p("reccyc"), self._ws.data_ptr(), self._ws.numel(),
                                 _flags(), _stream(), ptrs(s_in), ptrs(s_out))
         return (out, s_out) if return_state else out
@@ -1072,6 +1077,7 @@ class CycleChain(object):
         dev = x.device
         B, T, Ce = x.shape
         n, L, Co, enc, dec = self.n_cyc, self.lat_dim, self.dec.out_dim, self.enc, self.dec
+        Ld, clamp = self._draw_dim, self._clamp
         stdim, ncode = cvx.shape[2], code_src.shape[2]
         if enc.out_dim != 2 * L or dec.in_dim != ncode + L or enc.in_dim != stdim + Co or Ce != enc.in_dim:
             raise ValueError("CycleChain: encoder %d -> %d, decoder %d -> %d do not fit lat_dim %d, stdim %d, %d code columns"
@@ -1095,13 +1101,13 @@ class CycleChain(object):
                 pin = lib.pass_input((x.data_ptr(), Ce, Ce))
             else:
                 pin = lib.pass_input((x.data_ptr(), stdim, Ce), (prev.data_ptr(), Co, Co))
-            run(enc, de, ie, wse, pin, ye, L, o["lat"])
-            run(dec, dd, idd, wsd, lib.pass_input((code_src.data_ptr(), ncode, ncode), lat=o["lat"].data_ptr(), lat_dim=L, eps=ep(0),
+            run(enc, de, ie, wse, pin, ye, clamp, o["lat"])
+            run(dec, dd, idd, wsd, lib.pass_input((code_src.data_ptr(), ncode, ncode), lat=o["lat"].data_ptr(), lat_dim=Ld, eps=ep(0),
                                                   seed=seed, draw_id=3 * i), yd, -1, o["rec"])
-            run(dec, dd, idd, wsd, lib.pass_input((code_trg.data_ptr(), ncode, ncode), lat=o["lat"].data_ptr(), lat_dim=L, eps=ep(1),
+            run(dec, dd, idd, wsd, lib.pass_input((code_trg.data_ptr(), ncode, ncode), lat=o["lat"].data_ptr(), lat_dim=Ld, eps=ep(1),
                                                   seed=seed, draw_id=3 * i + 1), yd, -1, o["cv"])
-            run(enc, de, ie, wse, lib.pass_input((cvx.data_ptr(), stdim, stdim), (o["cv"].data_ptr(), Co, Co)), ye, L, o["latcv"])
-            run(dec, dd, idd, wsd, lib.pass_input((code_src.data_ptr(), ncode, ncode), lat=o["latcv"].data_ptr(), lat_dim=L, eps=ep(2),
+            run(enc, de, ie, wse, lib.pass_input((cvx.data_ptr(), stdim, stdim), (o["cv"].data_ptr(), Co, Co)), ye, clamp, o["latcv"])
+            run(dec, dd, idd, wsd, lib.pass_input((code_src.data_ptr(), ncode, ncode), lat=o["latcv"].data_ptr(), lat_dim=Ld, eps=ep(2),
                                                   seed=seed, draw_id=3 * i + 2), yd, -1, o["reccyc"])
             prev = o["reccyc"]          # (read by the next cycle's first pass, rewritten by its last)
         return out if outputs else {}

@@ -9,6 +9,8 @@ draw + concatenation that builds a decoder input, the loss with its gradients an
 """
 import torch
 
+import _cabi
+
 K_MCD_L1 = (10.0 / 2.3025850929940456840179914546844) * 1.4142135623730950488016887242097   # gru_vae.py:525
 
 TRAINABLE = ("conv.conv.0.weight", "conv.conv.0.bias", "conv.conv.1.weight", "conv.conv.1.bias", "gru.weight_ih_l0",
@@ -18,12 +20,27 @@ TRAINABLE = ("conv.conv.0.weight", "conv.conv.0.bias", "conv.conv.1.weight", "co
 PASS_SLOTS = ("lat", "rec", "cv", "latcv", "reccyc")     # the five passes of a cycle, in the reference's order (train...:1328-1338)
 
 
-def torch_dec_input(lat, codes, eps, lat_dim, cycle):
+def _check_posterior(posterior):
+    _cabi.posterior_flags(posterior, 0)      # (ValueError for anything but "gauss" / "laplace")
+    return posterior == "laplace"
+
+
+def torch_dec_input(lat, codes, eps, lat_dim, cycle, posterior="gauss"):
     """[code ; sampling_vae_batch(lat)] for one decoder pass, or for several stacked along the batch axis (gru_vae.py:96 + the
-    torch.cat of train...:1335-1338); eps: one [B,T,L] tensor per part, or None to draw on the device."""
+    torch.cat of train...:1335-1338); eps: one [B,T,L] tensor per part, or None to draw on the device.
+    posterior="laplace": [code ; sampling_vae_laplace(lat)] (gru_vae.py:101-112), eps then the uniform in (-0.4999, 0.5): the
+    module's own sampling_vae_laplace for fp32 device tensors, the same formula as torch ops elsewhere (the float64 checker)."""
     L = lat_dim
+    laplace = _check_posterior(posterior)
 
     def draw(e):
+        if laplace:
+            if e is None or (lat.is_cuda and lat.dtype == torch.float32):
+                import gru_vae
+                z = gru_vae.sampling_vae_laplace(lat.reshape(-1, 2 * L), lat_dim=L, training=True,
+                                                 eps=None if e is None else e.reshape(-1, L))
+                return z.reshape(lat.shape[:-1] + (L,))
+            return lat[:, :, :L] - torch.exp(lat[:, :, L:]) * torch.sign(e) * torch.log1p(-2 * torch.abs(e))
         if e is None:           # no eps supplied: the module's own sampling_vae_batch, as the script calls it (on-device Philox)
             import gru_vae
             return gru_vae.sampling_vae_batch(lat, lat_dim=L)
@@ -56,7 +73,7 @@ class _SplitRows(torch.autograd.Function):
 
 
 def chain_forward(run_pass, x, cvx, code_src, code_trg, y_in_enc, y_in_dec, eps, lat_dim, n_cyc=2, masks=None, carry=None,
-                  stack_rec_cv=False, dec_input=torch_dec_input):
+                  stack_rec_cv=False, dec_input=None, posterior="gauss"):
     """The passes of one frame window (train...:1299-1338).  Returns (trajs, state): trajs[i] = {"lat", "rec", "cv", "latcv",
     "reccyc"} of cycle i, state = {(cycle, slot): (y_last, h_last)} when run_pass returns them.
 
@@ -65,8 +82,14 @@ def chain_forward(run_pass, x, cvx, code_src, code_trg, y_in_enc, y_in_dec, eps,
     carry: None for a fresh window (y_in_* are the initial feedbacks, h = 0), or the state of the previous window of the same
     utterances (:1299-1311: every pass continues from its own detached state).
     stack_rec_cv: the two decoder passes of :1335-1336 share weights and do not depend on each other, so they run as ONE call on
-    2B rows (rows [0,B) = rec, [B,2B) = cv; run_pass is told kind "dec2")."""
+    2B rows (rows [0,B) = rec, [B,2B) = cv; run_pass is told kind "dec2").
+    posterior="laplace": the draws are sampling_vae_laplace's (dec_input None = torch_dec_input of that posterior) and the encoder
+    passes are told the Laplace clamp, lat_dim | _cabi.CLAMP_LAPLACE (clamp_vae_laplace, gru_vae.py:415-417)."""
     L, stdim = lat_dim, cvx.shape[2]
+    laplace = _check_posterior(posterior)
+    if dec_input is None:
+        dec_input = torch_dec_input if not laplace else (lambda *a: torch_dec_input(*a, posterior="laplace"))
+    Lc = (L | _cabi.CLAMP_LAPLACE) if laplace else L
     B = x.shape[0]
     ie = idc = 0
     prev = y2 = None
@@ -87,7 +110,7 @@ def chain_forward(run_pass, x, cvx, code_src, code_trg, y_in_enc, y_in_dec, eps,
 
     for i in range(n_cyc):
         e_in = x if i == 0 else torch.cat((x[:, :, :stdim], prev), 2)
-        lat = one("enc", "lat", i, e_in, y_in_enc, L, mk("enc", ie)); ie += 1
+        lat = one("enc", "lat", i, e_in, y_in_enc, Lc, mk("enc", ie)); ie += 1
         if stack_rec_cv:
             xin = dec_input(lat, (code_src, code_trg), (ep(i, 0), ep(i, 1)), L, (i, 0))
             ma, mb = mk("dec", idc), mk("dec", idc + 1)     # (conv mask [B,T,9C], gru mask [T,B,H]) per pass
@@ -108,7 +131,7 @@ def chain_forward(run_pass, x, cvx, code_src, code_trg, y_in_enc, y_in_dec, eps,
         else:
             rec = one("dec", "rec", i, dec_input(lat, (code_src,), (ep(i, 0),), L, (i, 0)), y_in_dec, -1, mk("dec", idc)); idc += 1
             cv = one("dec", "cv", i, dec_input(lat, (code_trg,), (ep(i, 1),), L, (i, 1)), y_in_dec, -1, mk("dec", idc)); idc += 1
-        latcv = one("enc", "latcv", i, torch.cat((cvx, cv), 2), y_in_enc, L, mk("enc", ie)); ie += 1
+        latcv = one("enc", "latcv", i, torch.cat((cvx, cv), 2), y_in_enc, Lc, mk("enc", ie)); ie += 1
         reccyc = one("dec", "reccyc", i, dec_input(latcv, (code_src,), (ep(i, 2),), L, (i, 2)), y_in_dec, -1, mk("dec", idc)); idc += 1
         prev = reccyc
         trajs.append({"lat": lat, "rec": rec, "cv": cv, "latcv": latcv, "reccyc": reccyc})
@@ -132,7 +155,7 @@ def frame_weights(B, T, flen_acc=None, select_utt_idx=None):
     return w, last, len(sel)
 
 
-def loss_terms(trajs, x, stdim, lat_dim, flen_acc=None, select_utt_idx=None, half_cyc=False):
+def loss_terms(trajs, x, stdim, lat_dim, flen_acc=None, select_utt_idx=None, half_cyc=False, posterior="gauss"):
     """Batch loss of one frame window from the trajectories of chain_forward, as the reference computes it (:1363-1410).
 
     Utterance j of select_utt_idx contributes the first n = flen_acc[j] frames of the window (Python slice clipping: at most T); the
@@ -141,8 +164,9 @@ def loss_terms(trajs, x, stdim, lat_dim, flen_acc=None, select_utt_idx=None, hal
     utterances and cycles -- with the reference's quirk at :1393 kept: for more than one selected utterance the `lat_src_cv` list is
     rebuilt from the `lat_src` list, so its sum is (sum of KL(lat) over the utterances) + KL(latcv of the LAST utterance) (SURVEY
     App. C.2; harmless at the recipe's batch_size_utt = 1).  half_cyc (n_cyc < 1 in the reference, :283-287) drops the rec_cyc /
-    latcv terms."""
+    latcv terms.  posterior="laplace": the KL terms are loss_vae_laplace's (gru_vae.py:130-139), everything else as above."""
     L = lat_dim
+    laplace = _check_posterior(posterior)
     B, T = x.shape[0], x.shape[1]
     wl, lastl, n_sel = frame_weights(B, T, flen_acc, select_utt_idx)
     w = torch.tensor(wl, dtype=torch.float32, device=x.device)
@@ -150,6 +174,12 @@ def loss_terms(trajs, x, stdim, lat_dim, flen_acc=None, select_utt_idx=None, hal
     tgt = x[:, :, stdim:]
     mcd = lambda trj: (K_MCD_L1 * (trj - tgt).abs().sum(2) * w).sum()                          # gru_vae.py:525-527
     kl_rows = lambda par: ((0.5 * (par[:, :, L:].exp() + par[:, :, :L] ** 2 - par[:, :, L:] - 1.0).sum(2)) * w).sum(1)   # :123
+    if laplace:      # :130-139, as gru_vae.loss_vae_laplace forms it per utterance
+
+        def kl_rows(par):
+            ma, s = par[:, :, :L].abs(), par[:, :, L:]
+            b = torch.exp(s)
+            return ((-s + b * torch.exp(-ma / b) + ma - 1).sum(2) * w).sum(1)
     loss = 0.0
     for tr in trajs:
         kl_lat = kl_rows(tr["lat"])
@@ -202,14 +232,15 @@ def script_loss_loop(trajs, x, stdim, lat_dim, flen_acc=None, select_utt_idx=Non
 
 
 def chain_loss(run_pass, x, cvx, code_src, code_trg, y_in_enc, y_in_dec, eps, lat_dim, n_cyc=2, masks=None,
-               flen_acc=None, select_utt_idx=None, half_cyc=False, carry=None, return_state=False, stack_rec_cv=False):
+               flen_acc=None, select_utt_idx=None, half_cyc=False, carry=None, return_state=False, stack_rec_cv=False,
+               posterior="gauss"):
     """chain_forward + loss_terms: the batch loss of one frame window (train...:1299-1338 forward, :1363-1410 loss).
     x is the WINDOW of the padded utterance batch (batch_src[:, s:e+1]); flen_acc / select_utt_idx: the generator's bookkeeping
     (windows.plan_windows, reference train...:45-149).  return_state=True additionally returns the state dict for the next window
     and the five trajectories per cycle."""
     trajs, state = chain_forward(run_pass, x, cvx, code_src, code_trg, y_in_enc, y_in_dec, eps, lat_dim, n_cyc, masks, carry,
-                                 stack_rec_cv)
-    loss = loss_terms(trajs, x, cvx.shape[2], lat_dim, flen_acc, select_utt_idx, half_cyc)
+                                 stack_rec_cv, posterior=posterior)
+    loss = loss_terms(trajs, x, cvx.shape[2], lat_dim, flen_acc, select_utt_idx, half_cyc, posterior)
     if return_state:
         return loss, state, trajs
     return loss
@@ -223,10 +254,11 @@ def freeze_scalers(*modules):
 
 
 class _SampleCat(torch.autograd.Function):
-    """[code ; mu + exp(s/2) eps] for one decoder pass or two stacked ones, one launch forward and one backward."""
+    """[code ; mu + exp(s/2) eps] for one decoder pass or two stacked ones, one launch forward and one backward.
+    flag: 0, or _cabi.DRAW_LAPLACE for [code ; mu + exp(s) u(eps)]."""
 
     @staticmethod
-    def forward(ctx, lat, codes, eps, seed, draws):
+    def forward(ctx, lat, codes, eps, seed, draws, flag=0):
         import gru_vae
         lib = gru_vae._lib()
         B, T, L2 = lat.shape
@@ -237,9 +269,9 @@ class _SampleCat(torch.autograd.Function):
         out = torch.empty(parts * B, T, ncode + L, dtype=torch.float32, device=lat.device)
         eps_used = torch.empty(parts, B, T, L, dtype=torch.float32, device=lat.device)
         lib.sample_cat(latc.data_ptr(), [c.data_ptr() for c in cs], [None if e is None else e.data_ptr() for e in es], seed, draws,
-                       B, T, L, ncode, out.data_ptr(), eps_used.data_ptr(), gru_vae._stream())
+                       B, T, L | flag, ncode, out.data_ptr(), eps_used.data_ptr(), gru_vae._stream())
         ctx.save_for_backward(latc, eps_used)
-        ctx.dims = (B, T, L, ncode, parts)
+        ctx.dims = (B, T, L | flag, ncode, parts)
         return out
 
     @staticmethod
@@ -250,7 +282,7 @@ class _SampleCat(torch.autograd.Function):
         dlat = torch.empty_like(latc)
         gru_vae._lib().sample_cat_backward(dout.contiguous().data_ptr(), latc.data_ptr(), eps_used.data_ptr(), B, T, L, ncode, parts,
                                            dlat.data_ptr(), gru_vae._stream())
-        return dlat, None, None, None, None
+        return dlat, None, None, None, None, None
 
 
 class Stage4Step(object):
@@ -276,14 +308,22 @@ class Stage4Step(object):
     5.3 ms at one utterance -- the device is the bottleneck either way, the mode exists for loops that must not block)."""
 
     def __init__(self, enc, dec, lat_dim, n_cyc=2, lr=1e-4, dist=None, stack_rec_cv=True, overlap_wgrad=True, fused=None,
-                 betas=(0.9, 0.999), eps=1e-8, sync=True, force_collectives=False, script_loss=False):
+                 betas=(0.9, 0.999), eps=1e-8, sync=True, force_collectives=False, script_loss=False, posterior="gauss"):
         """stack_rec_cv: rec || cv as one decoder launch (chain_forward).  overlap_wgrad: parameter gradients accumulate straight
         into the flat gradient buffer and the recurrent weight-gradient GEMMs of every backward pass run on a second stream, under
         the next pass's reverse recurrence (gru_vae.set_side_stream); joined before the all-reduce / optimizer step.
         force_collectives: issue the gradient all-reduce and the status MAX-reduce even in a process group of ONE rank (bench.py
         --force-dist: the RCCL path executes on a one-GPU box).  script_loss (fused=False only): form the loss with the training
-        script's own per-utterance loop and its host read-backs (script_loss_loop) instead of the vectorised loss_terms."""
+        script's own per-utterance loop and its host read-backs (script_loss_loop) instead of the vectorised loss_terms.
+        posterior: "gauss", or "laplace" for the Laplace posterior of the sibling recipes in both step forms (fused: the flag
+        _cabi.DRAW_LAPLACE in cvae_sample_cat and cvae_stage4_loss; unfused: sampling_vae_laplace and loss_vae_laplace's KL); the
+        encoder passes then clamp as clamp_vae_laplace does.  script_loss_loop is Gaussian only."""
         import shard
+        self.posterior = posterior
+        self._laplace = _check_posterior(posterior)
+        if self._laplace and script_loss:
+            raise NotImplementedError("script_loss=True forms the Gaussian loss only (script_loss_loop); posterior='laplace' takes "
+                                      "loss_terms or the fused loss")
         for m in (enc, dec):
             if getattr(m, "hidden_layers", 1) > 1:
                 raise NotImplementedError("hidden_layers=%d: training a stacked GRU (Stage4Step) is not implemented; the eval passes, "
@@ -372,7 +412,9 @@ class Stage4Step(object):
         if parts > 1:
             gru_vae.set_draw_parts(parts)
         try:
-            out = m(x, y_in, do=True, clamp_vae=clamp >= 0, lat_dim=self.lat_dim, h_in=h_in)
+            # (clamp: -1, lat_dim, or lat_dim | _cabi.CLAMP_LAPLACE as chain_forward passes it for the Laplace posterior)
+            out = m(x, y_in, do=True, clamp_vae=clamp >= 0 and not self._laplace, clamp_vae_laplace=clamp >= 0 and self._laplace,
+                    lat_dim=self.lat_dim, h_in=h_in)
         finally:
             if parts > 1:
                 gru_vae.set_draw_parts(1)
@@ -380,7 +422,8 @@ class Stage4Step(object):
 
     def _dec_input(self, lat, codes, eps, lat_dim, cycle):
         i, k = cycle
-        return _SampleCat.apply(lat, codes, eps, self._seed, [i * 3 + k + q for q in range(len(codes))])
+        return _SampleCat.apply(lat, codes, eps, self._seed, [i * 3 + k + q for q in range(len(codes))],
+                                _cabi.DRAW_LAPLACE if self._laplace else 0)
 
     def _weights(self, B, T, flen_acc, select_utt_idx, dev):
         key = (B, T, None if flen_acc is None else tuple(int(v) for v in flen_acc),
@@ -415,7 +458,8 @@ class Stage4Step(object):
                 d_reccyc, d_latcv = torch.empty_like(reccyc), torch.empty_like(latcv)
             p = lambda t_: None if t_ is None else t_.data_ptr()
             lib.stage4_loss(p(rec), p(reccyc), p(lat), p(latcv), xc.data_ptr(), xc.shape[2], stdim, w.data_ptr(), last.data_ptr(), kl_scale,
-                            B, T, D, L, p(d_rec), p(d_reccyc), p(d_lat), p(d_latcv), frame_loss.data_ptr(), loss.data_ptr(), i > 0,
+                            B, T, D, L | (_cabi.DRAW_LAPLACE if self._laplace else 0), p(d_rec), p(d_reccyc), p(d_lat), p(d_latcv),
+                            frame_loss.data_ptr(), loss.data_ptr(), i > 0,
                             gru_vae._stream())
             outs += [tr["rec"], tr["lat"]]
             grads += [d_rec, d_lat]
@@ -455,11 +499,13 @@ class Stage4Step(object):
                                      half_cyc, stack):
         import gru_vae
         trajs, state = chain_forward(self._run, x, cvx, code_src, code_trg, y_in_enc, y_in_dec, eps, self.lat_dim, self.n_cyc, masks,
-                                     carry, stack, self._dec_input if self.fused else torch_dec_input)
+                                     carry, stack, self._dec_input if self.fused else None, self.posterior)
         loss = None
         if not self.fused:
-            loss = (script_loss_loop if self.script_loss else loss_terms)(trajs, x, cvx.shape[2], self.lat_dim, flen_acc,
-                                                                          select_utt_idx, half_cyc)
+            if self.script_loss:
+                loss = script_loss_loop(trajs, x, cvx.shape[2], self.lat_dim, flen_acc, select_utt_idx, half_cyc)
+            else:
+                loss = loss_terms(trajs, x, cvx.shape[2], self.lat_dim, flen_acc, select_utt_idx, half_cyc, self.posterior)
         if self.overlap_wgrad:
             for m in self.mods.values():
                 m._grad_sink = True

@@ -126,7 +126,7 @@ def dtw_many(problems):
     return outs
 
 
-def _encode_pairs(model_encoder, pairs, y_in_pp, lat_dim):
+def _encode_pairs(model_encoder, pairs, y_in_pp, lat_dim, posterior="gauss"):
     """First half of convert_pairs on the current stream: all 2N encoder passes as one pass over 2N stacked rows.  Returns what the
     decoder half needs."""
     N = len(pairs)
@@ -149,17 +149,19 @@ def _encode_pairs(model_encoder, pairs, y_in_pp, lat_dim):
     for (a, b), (ta, tb) in zip(feats, lens):
         pins += [lib.pass_input((a.data_ptr(), Cin, Cin), frames=ta), lib.pass_input((b.data_ptr(), Cin, Cin), frames=tb)]
     # (hidden_layers >= 2: the same cells pass by pass, gru_vae.run_cells)
-    gru_vae.run_cells(model_encoder, de, ie, pins, [ypp.data_ptr()] * (2 * N), T, L, [lat[r].data_ptr() for r in range(2 * N)], ws,
+    clamp = _cabi.posterior_flags(posterior, L)[1]
+    gru_vae.run_cells(model_encoder, de, ie, pins, [ypp.data_ptr()] * (2 * N), T, clamp, [lat[r].data_ptr() for r in range(2 * N)], ws,
                       gru_vae._flags(model_encoder.hidden_layers), st)
     return {"N": N, "lens": lens, "T": T, "lat": lat, "dev": dev, "keep": (feats, ypp, ws)}
 
 
-def _decode_pairs(model_decoder, enc, y_in_src, y_in_trg, lat_dim, n_smpl_dec, eps, seed, pair_ids=None):
+def _decode_pairs(model_decoder, enc, y_in_src, y_in_trg, lat_dim, n_smpl_dec, eps, seed, pair_ids=None, posterior="gauss"):
     """Second half of convert_pairs on the current stream: the n_smpl_dec-draw latent means and all 3N decoder passes as one pass
     over 3N stacked rows."""
     lib = gru_vae._lib()
     N, lens, T, lat, dev = enc["N"], enc["lens"], enc["T"], enc["lat"], enc["dev"]
     L, Co = lat_dim, model_decoder.out_dim
+    Ld = _cabi.posterior_flags(posterior, L)[0]
     f = lambda t: t.to(torch.float32).contiguous()
     st = torch.cuda.current_stream().cuda_stream
     dd, idd = model_decoder.prepared(dev)
@@ -186,7 +188,7 @@ def _decode_pairs(model_decoder, enc, y_in_src, y_in_trg, lat_dim, n_smpl_dec, e
         keep += [es, et]
 
         def cell(code_row, lat_row, e, frames, draw0):
-            return lib.pass_input((codes[code_row].data_ptr(), 2, 0), lat=lat[lat_row].data_ptr(), lat_dim=L,
+            return lib.pass_input((codes[code_row].data_ptr(), 2, 0), lat=lat[lat_row].data_ptr(), lat_dim=Ld,
                                   eps=None if e is None else e.data_ptr(), seed=sd, draw_id=draw0, frames=frames, n_draws=n)
 
         # cvmcep and cvmcep_src share ONE sampling of lat_src (decode...:304-305), cvmcep_trg has its own (:307-308)
@@ -203,7 +205,7 @@ def _decode_pairs(model_decoder, enc, y_in_src, y_in_trg, lat_dim, n_smpl_dec, e
 
 
 def convert_pairs(model_encoder, model_decoder, pairs, y_in_pp, y_in_src, y_in_trg, lat_dim, n_smpl_dec=300, eps=None, seed=None,
-                  window=None):
+                  window=None, posterior="gauss"):
     """The network part of stage 6 (reference decode_gru-cyclevae_gauss.py:302-323) for SEVERAL (source, target) utterance pairs
     at once.  For every pair:
 
@@ -219,16 +221,20 @@ def convert_pairs(model_encoder, model_decoder, pairs, y_in_pp, y_in_src, y_in_t
     window (frames, or a list of window lengths; ONE pair only): run the pair as a pass-level wavefront over windows of that many
     frames, the decoder of window w beside the encoder of window w+1 (_convert_pair_windowed): same values bit for bit, lower
     latency (3.15 -> 2.8-2.9 ms for a 637 / 660-frame pair at window=224).
+    posterior="laplace": the Laplace posterior of the sibling recipes -- the encoder passes clamp as clamp_vae_laplace does, z is the
+    mean over n_smpl_dec draws of sampling_vae_laplace(lat) (mu + exp(s) * mean_k u(eps_k)), supplied eps are its uniforms.
     Returns a list of (cvmcep [Ts,Co], cvmcep_src [Ts,Co], cvmcep_trg [Tt,Co], lat_src [Ts,2L], lat_trg [Tt,2L]) (fp32, device).
     """
+    _cabi.posterior_flags(posterior, lat_dim)
     gru_vae.check_status()
     if seed is None and eps is None and gru_vae._range_policy == "retry":
         seed = gru_vae._draw_seed()      # (a call repeated on the fp32-operand kernels draws what the first try drew)
     return gru_vae._with_range_retry(lambda: _convert_pairs(model_encoder, model_decoder, pairs, y_in_pp, y_in_src, y_in_trg, lat_dim,
-                                                            n_smpl_dec, eps, seed, window))
+                                                            n_smpl_dec, eps, seed, window, posterior))
 
 
-def _convert_pairs(model_encoder, model_decoder, pairs, y_in_pp, y_in_src, y_in_trg, lat_dim, n_smpl_dec, eps, seed, window):
+def _convert_pairs(model_encoder, model_decoder, pairs, y_in_pp, y_in_src, y_in_trg, lat_dim, n_smpl_dec, eps, seed, window,
+                   posterior="gauss"):
     """convert_pairs behind its status check and range policy (gru_vae.set_range_policy)."""
     if window and len(pairs) != 1:
         raise ValueError("convert_pairs(window=...) runs ONE pair as a wavefront of windows, got %d pairs" % len(pairs))
@@ -238,9 +244,9 @@ def _convert_pairs(model_encoder, model_decoder, pairs, y_in_pp, y_in_src, y_in_
                                       "stacked networks without window" % (model_encoder.hidden_layers, model_decoder.hidden_layers))
         gru_vae._need_cuda(pairs[0][0], "convert_pairs(feat_src)")
         return _convert_pair_windowed(model_encoder, model_decoder, pairs[0], y_in_pp, y_in_src, y_in_trg, lat_dim, n_smpl_dec,
-                                      None if eps is None else eps[0], seed, window)
-    enc = _encode_pairs(model_encoder, pairs, y_in_pp, lat_dim)
-    return _decode_pairs(model_decoder, enc, y_in_src, y_in_trg, lat_dim, n_smpl_dec, eps, seed)[1]
+                                      None if eps is None else eps[0], seed, window, posterior)
+    enc = _encode_pairs(model_encoder, pairs, y_in_pp, lat_dim, posterior)
+    return _decode_pairs(model_decoder, enc, y_in_src, y_in_trg, lat_dim, n_smpl_dec, eps, seed, posterior=posterior)[1]
 
 
 def _window_edges(Tmax, window, reach):
@@ -283,7 +289,8 @@ def _decoder_window_schedule(nfr, edges, reach):
     return out
 
 
-def _convert_pair_windowed(model_encoder, model_decoder, pair, y_in_pp, y_in_src, y_in_trg, lat_dim, n_smpl_dec, eps, seed, window):
+def _convert_pair_windowed(model_encoder, model_decoder, pair, y_in_pp, y_in_src, y_in_trg, lat_dim, n_smpl_dec, eps, seed, window,
+                           posterior="gauss"):
     """convert_pairs for ONE utterance pair as a pass-level wavefront: the utterances are cut into windows of `window` frames, the
     encoder launch of window w+1 runs on a second stream beside the decoder launch of window w (the decoder lags by the conv
     front-end's reach, (ks^layers - 1) / 2 = 4 frames in the recipe: its window w needs latent frames up to the end of encoder window w).  A window is a pass with
@@ -295,6 +302,7 @@ def _convert_pair_windowed(model_encoder, model_decoder, pair, y_in_pp, y_in_src
     dev = fs.device
     lens = (fs.shape[0], ft.shape[0])
     Tmax, L, Cin, Co, H = max(lens), lat_dim, model_encoder.in_dim, model_decoder.out_dim, model_encoder.hidden_units
+    Ld, clamp = _cabi.posterior_flags(posterior, L)
     reach = (model_decoder.kernel_size ** model_decoder.dilation_size - 1) // 2      # the front-end's padding (ks^layers - 1) / 2
     reach_enc = (model_encoder.kernel_size ** model_encoder.dilation_size - 1) // 2
     if reach_enc != reach:
@@ -339,7 +347,7 @@ def _convert_pair_windowed(model_encoder, model_decoder, pair, y_in_pp, y_in_src
         enc_calls.append((de, ie.data_ptr(),
                           [lib.pass_input((feats[r].data_ptr() + start * Cin * 4, Cin, Cin), frames=k, ctx_before=start,
                                           ctx_after=lens[r] - start - k) for r, k in zip(alive, fr)],
-                          [ypp.data_ptr() if w == 0 else None] * len(alive), [None if w == 0 else h_enc[r].data_ptr() for r in alive], 1, T, L,
+                          [ypp.data_ptr() if w == 0 else None] * len(alive), [None if w == 0 else h_enc[r].data_ptr() for r in alive], 1, T, clamp,
                           [lat[r].data_ptr() + start * 2 * L * 4 for r in alive], [h_enc[r].data_ptr() for r in alive], ws.data_ptr(), ws.numel()))
         rows, spans = dec_sched[w]
         if not rows:
@@ -350,7 +358,7 @@ def _convert_pair_windowed(model_encoder, model_decoder, pair, y_in_pp, y_in_src
         for i, k in zip(rows, spans):
             crow, lr, e, nfr, draw0, _ = drows[i]
             d0 = done[i]
-            pins.append(lib.pass_input((codes[crow].data_ptr(), 2, 0), lat=lat[lr].data_ptr() + d0 * 2 * L * 4, lat_dim=L,
+            pins.append(lib.pass_input((codes[crow].data_ptr(), 2, 0), lat=lat[lr].data_ptr() + d0 * 2 * L * 4, lat_dim=Ld,
                                        eps=None if e is None else e.data_ptr() + d0 * L * 4, seed=sd, draw_id=draw0, frames=k, n_draws=n,
                                        ctx_before=d0, ctx_after=nfr - d0 - k, draw_frame0=d0, eps_draw_stride=0 if e is None else e.shape[1] * L))
         ws = torch.empty(lib.pass_workspace_bytes(dd, len(rows), T), dtype=torch.uint8, device=dev)
@@ -387,7 +395,7 @@ _pipe_streams = {}
 
 
 def convert_list(model_encoder, model_decoder, groups, y_in_pp, y_in_src, y_in_trg, lat_dim, n_smpl_dec=300, eps=None, seeds=None,
-                 pair_ids=None):
+                 pair_ids=None, posterior="gauss"):
     """convert_pairs over a LIST of calls (the file list one GPU gets, decode...:190-195), software-pipelined over two streams: the
     encoder pass of group g+1 runs side by side with the decoder pass of group g.  Both are hand-off-bound recurrences that leave
     most of every CU idle: one utterance pair per group (the word-exchange kernels, <= 3 rows per pass) runs two such passes side
@@ -397,7 +405,8 @@ def convert_list(model_encoder, model_decoder, groups, y_in_pp, y_in_src, y_in_t
     (tests/test_gpu_parity.py).  groups: list of lists of (feat_src, feat_trg); eps / seeds: None or
     one entry per group, as convert_pairs takes them; pair_ids: None or per group the list positions that key the pairs' draws
     (_decode_pairs).  Returns one convert_pairs result per group; everything is ordered behind the current stream on entry and
-    ahead of it on return."""
+    ahead of it on return.  posterior: as convert_pairs takes it."""
+    _cabi.posterior_flags(posterior, lat_dim)
     if not groups:
         return []
     gru_vae._need_cuda(groups[0][0][0], "convert_list(feat_src)")
@@ -405,10 +414,11 @@ def convert_list(model_encoder, model_decoder, groups, y_in_pp, y_in_src, y_in_t
     if seeds is None and eps is None and gru_vae._range_policy == "retry":
         seeds = [gru_vae._draw_seed() for _ in groups]      # (a repeated call draws what the first try drew)
     return gru_vae._with_range_retry(lambda: _convert_list(model_encoder, model_decoder, groups, y_in_pp, y_in_src, y_in_trg, lat_dim,
-                                                           n_smpl_dec, eps, seeds, pair_ids))
+                                                           n_smpl_dec, eps, seeds, pair_ids, posterior))
 
 
-def _convert_list(model_encoder, model_decoder, groups, y_in_pp, y_in_src, y_in_trg, lat_dim, n_smpl_dec, eps, seeds, pair_ids):
+def _convert_list(model_encoder, model_decoder, groups, y_in_pp, y_in_src, y_in_trg, lat_dim, n_smpl_dec, eps, seeds, pair_ids,
+                  posterior="gauss"):
     """convert_list behind its status check and range policy: everything joins the current stream before it returns, so the
     policy's wait for the current stream covers both pipeline streams."""
     dev = groups[0][0][0].device
@@ -425,7 +435,7 @@ def _convert_list(model_encoder, model_decoder, groups, y_in_pp, y_in_src, y_in_
         nxt = None
         if g < len(groups):
             with torch.cuda.stream(s_enc):
-                enc = _encode_pairs(model_encoder, groups[g], y_in_pp, lat_dim)
+                enc = _encode_pairs(model_encoder, groups[g], y_in_pp, lat_dim, posterior)
                 ev = torch.cuda.Event()
                 ev.record(s_enc)
             nxt = (g, enc, ev)
@@ -439,7 +449,7 @@ def _convert_list(model_encoder, model_decoder, groups, y_in_pp, y_in_src, y_in_
                         x.record_stream(s_dec)
                 out, res = _decode_pairs(model_decoder, enc_p, y_in_src, y_in_trg, lat_dim, n_smpl_dec,
                                          None if eps is None else eps[gi], None if seeds is None else seeds[gi],
-                                         None if pair_ids is None else pair_ids[gi])
+                                         None if pair_ids is None else pair_ids[gi], posterior)
                 out.record_stream(cur)
                 enc_p["lat"].record_stream(cur)
             results.append(res)
@@ -588,8 +598,8 @@ def convert_files(model_encoder, model_decoder, file_pairs, devices, y_in_pp, y_
 
 
 def convert_pair(model_encoder, model_decoder, feat_src, feat_trg, y_in_pp, y_in_src, y_in_trg, lat_dim, n_smpl_dec=300,
-                 eps_src=None, eps_trg=None, seed=None, window=None):
+                 eps_src=None, eps_trg=None, seed=None, window=None, posterior="gauss"):
     """convert_pairs for ONE utterance pair: two launches of dependent steps instead of the five passes of decode...:303-323."""
     e = None if eps_src is None and eps_trg is None else [(eps_src, eps_trg)]
     return convert_pairs(model_encoder, model_decoder, [(feat_src, feat_trg)], y_in_pp, y_in_src, y_in_trg, lat_dim, n_smpl_dec,
-                         e, seed, window)[0]
+                         e, seed, window, posterior)[0]

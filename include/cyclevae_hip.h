@@ -78,6 +78,10 @@ typedef struct cvae_seg {
  * gru_vae.py:85-98): eps is read from `eps`[B,T,lat_dim] if non-NULL, else drawn on device with
  * Philox4x32-10 keyed by (seed, draw_id, frame b*T+t, dim / 4): one block yields the four N(0,1) values of a dim quad (Box-Muller,
  * cosine and sine branch of word pairs (0,1) and (2,3)).
+ * lat_dim | CVAE_DRAW_LAPLACE: the Laplace posterior instead (sampling_vae_laplace, gru_vae.py:101-112): lat holds [mu ; log-scale],
+ * z = mu + exp(s) * u(eps) with u(e) = -sign(e) * log1p(-2|e|); eps is the reference's uniform in (-0.4999, 0.5) if supplied, else
+ * word dim & 3 of the same Philox block mapped as cvae_sample_laplace maps it (the same bits for the same seed, draw_id, frame,
+ * dim).  With n_draws > 1: z = mu + exp(s) * mean_k u(eps_k).
  */
 typedef struct cvae_pass_input {
     cvae_seg seg0, seg1;
@@ -455,6 +459,16 @@ int cvae_sample_laplace(cvae_ctx* ctx, const float* lat, int rows, int lat_dim, 
                         float* z, float* eps_out, void* stream);
 int cvae_sample_laplace_backward(cvae_ctx* ctx, const float* dz, const float* lat, const float* z, int rows, int lat_dim, float* dlat,
                                  void* stream);
+
+/*
+ * The Laplace posterior inside the fused paths: OR this into a lat_dim value, as CVAE_CLAMP_LAPLACE is OR-ed into clamp_lat_dim.
+ * It is honoured by cvae_pass_input.lat_dim (the draw inside a pass prologue, single or the mean of n_draws), by the lat_dim of
+ * cvae_cycle_forward / cvae_cycle_forward_carry (the three draws of every cycle are Laplace draws and the encoder passes clamp at
+ * the Laplace floor), of cvae_latent_mean, of cvae_sample_cat / cvae_sample_cat_backward (d mu = dz, d s = dz * exp(s) * u(eps)) and
+ * of cvae_stage4_loss (KL = sum_d(-s + b exp(-|mu|/b) + |mu| - 1), b = exp(s): loss_vae_laplace, gru_vae.py:130-139).  Every entry
+ * strips the flag before it validates or uses the dimension; without it nothing changes.
+ */
+#define CVAE_DRAW_LAPLACE (1 << 30)
 
 /* Bytes of workspace the fused cycle chain needs. */
 size_t cvae_cycle_workspace_bytes(cvae_ctx* ctx, const cvae_net_desc* enc, const cvae_net_desc* dec, int B, int T, int n_cyc);
