@@ -73,6 +73,11 @@ def upper_layer_keys(n_layers):
 
 DEEP_PER_STEP, DEEP_GENERIC, DEEP_RESIDENT = 0, 1, 2      # cvae_plan_pass_deep
 EVAL_PER_STEP, EVAL_GENERIC, EVAL_V2, EVAL_V4, EVAL_V5, EVAL_V6, EVAL_LL, EVAL_V6H = range(8)      # cvae_plan_pass (cvae_eval_form)
+# cvae_plan_train_pass: the forward / reverse forms (FwdForm / BwdForm of csrc/cvae_train.inc) and the fields of its answer
+TRAIN_FWD_LL, TRAIN_FWD_W3, TRAIN_FWD_X3, TRAIN_FWD_X3H, TRAIN_FWD_PAIR, TRAIN_FWD_FP32, TRAIN_FWD_STEPS = range(7)
+TRAIN_BWD_LL, TRAIN_BWD_W3, TRAIN_BWD_X3, TRAIN_BWD_PAIR, TRAIN_BWD_STEPS = range(5)
+TRAIN_PLAN_FIELDS = ("Bp", "fwd", "fwd_rts", "fwd_tiles", "fwd_col_tiles", "fwd_full_writes", "bwd", "bwd_rts", "bwd_per_launch", "bwd_tiles",
+                     "bwd_writes_gates", "variants")
 MAX_LAYERS = 8                                              # CVAE_DEEP_MAX_LAYERS
 
 
@@ -191,7 +196,7 @@ class _Bound(object):
 # Test queries added WITHOUT an ABI bump: a library of the same ABI version built before one of them still loads (every kernel entry
 # point is there), and calling the missing query raises CvaeError.  The shipped library must export them (__graft_entry__.build and
 # tests/test_cabi_exports.py check all of EXPORTS).
-ADDITIVE = ("cvae_plan_pass_deep_tiles",)
+ADDITIVE = ("cvae_plan_pass_deep_tiles", "cvae_plan_train_pass")
 NO_CONTEXT = ("cvae_last_error_string", "cvae_abi_version", "cvae_ctx_create", "cvae_ctx_destroy")
 _CDLLS = {}     # path -> (CDLL with argtypes declared): one load per process, any number of contexts
 
@@ -291,6 +296,9 @@ class CvaeLib(object):
         L.cvae_net_prepare_train_v.argtypes = [C.POINTER(NetDesc), C.POINTER(NetWeights), _fp, C.c_size_t, C.c_float, C.c_int, _fp]
         L.cvae_train_variants_needed.restype = C.c_int
         L.cvae_train_variants_needed.argtypes = [C.POINTER(NetDesc), C.c_int, C.c_int]
+        if hasattr(L, "cvae_plan_train_pass"):           # (ADDITIVE, below)
+            L.cvae_plan_train_pass.restype = C.c_int
+            L.cvae_plan_train_pass.argtypes = [C.POINTER(NetDesc), C.c_int, C.c_int, C.POINTER(C.c_int32 * 12)]
         for fn in ("cvae_train_tape_bytes", "cvae_train_scratch_bytes"):
             getattr(L, fn).restype = C.c_size_t
             getattr(L, fn).argtypes = [C.POINTER(NetDesc), C.c_int, C.c_int]
@@ -578,6 +586,15 @@ class CvaeLib(object):
     def train_variants_needed(self, d, B, T):
         return self.lib.cvae_train_variants_needed(C.byref(d), B, T)
 
+    def plan_train_pass(self, d, B, T):
+        """dict of TRAIN_PLAN_FIELDS: the recurrence forms (TRAIN_FWD_* / TRAIN_BWD_*) and row tiling a train-mode pass of this shape
+        takes under the context's options, and the two memset decisions that follow from them."""
+        if not hasattr(self.lib, "cvae_plan_train_pass"):
+            raise CvaeError("%s was built before cvae_plan_train_pass was added: rebuild it" % self.path)
+        out = (C.c_int32 * 12)()
+        self._check(self.lib.cvae_plan_train_pass(C.byref(d), B, T, C.byref(out)), "cvae_plan_train_pass")
+        return dict(zip(TRAIN_PLAN_FIELDS, out))
+
     def train_tape_bytes(self, d, B, T):
         return self.lib.cvae_train_tape_bytes(C.byref(d), B, T)
 
@@ -775,7 +792,7 @@ EXPORTS = ("cvae_last_error_string", "cvae_abi_version", "cvae_ctx_create", "cva
            "cvae_set_option", "cvae_get_option", "cvae_reset_options", "cvae_selftest_limbs", "cvae_selftest_occupy", "cvae_selftest_gemm_work_bytes", "cvae_selftest_gemm", "cvae_set_side_stream", "cvae_join_side_stream", "cvae_net_prepared_bytes", "cvae_net_prepare_scratch_bytes",
            "cvae_net_prepare", "cvae_pass_workspace_bytes", "cvae_gru_rnn_forward", "cvae_gru_rnn_forward_stacked", "cvae_gru_rnn_forward_stacked_carry", "cvae_sample", "cvae_sample_laplace", "cvae_sample_laplace_backward",
            "cvae_cycle_workspace_bytes", "cvae_cycle_forward", "cvae_cycle_forward_carry", "cvae_profile_collect", "cvae_profile_collect_launches", "cvae_train_profile_collect", "cvae_step_timing", "cvae_workspace_status",
-           "cvae_train_image_bytes", "cvae_net_prepare_train", "cvae_net_prepare_train_v", "cvae_train_variants_needed", "cvae_train_tape_bytes", "cvae_train_scratch_bytes",
+           "cvae_train_image_bytes", "cvae_net_prepare_train", "cvae_net_prepare_train_v", "cvae_train_variants_needed", "cvae_plan_train_pass", "cvae_train_tape_bytes", "cvae_train_scratch_bytes",
            "cvae_gru_rnn_forward_train", "cvae_gru_rnn_backward", "cvae_adam_step", "cvae_adam_step_counted", "cvae_train_debug_counters",
            "cvae_sample_cat", "cvae_sample_cat_backward", "cvae_stage4_loss", "cvae_mcd_l1", "cvae_mcd_l1_backward", "cvae_kl_gauss",
            "cvae_kl_gauss_backward",

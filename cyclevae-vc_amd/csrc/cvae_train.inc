@@ -52,6 +52,9 @@ struct TrainPlan {
     int bwd_per_launch;      // row tiles per launch of BWD_W3 / BWD_X3 (0: the whole pass in one)
     bool bwd_writes_gates;   // every row of dgi / dgh written by the reverse recurrence (dead rows as zeros): no memset
     int variants;            // the weight images the forms of this shape may need, their fall-backs included
+    // what cvae_plan_train_pass reports on top (tests): the most row tiles one block row owns -- per step in the forward (32-row
+    // tiles of FWD_X3, 16-row tiles otherwise), per launch in the reverse; 0 for the forms without row tiles (LL, STEPS)
+    int fwd_tiles, bwd_tiles;
 };
 
 // THE place where a training pass's recurrence forms are chosen: forward and backward of a pass call it with the same shape and
@@ -147,6 +150,8 @@ TrainPlan plan_train_pass(const Dims& m, int B, int T) {
         if (!per_step && T > 1) p.variants |= fp32 ? TV_FP32 : exact && ok ? TV_EXACT | TV_PAIR : TV_PAIR;
         if (!bwd_per_step && T > 1 && ok) p.variants |= exact ? TV_EXACT : TV_PAIR;
     }
+    if (p.fwd_rts > 0) p.fwd_tiles = ((p.fwd == FWD_X3 ? nrt32 : nt16) + p.fwd_rts - 1) / p.fwd_rts;
+    if (p.bwd_rts > 0) p.bwd_tiles = ((p.bwd_per_launch && p.bwd_per_launch < nt16 ? p.bwd_per_launch : nt16) + p.bwd_rts - 1) / p.bwd_rts;
     return p;
 }
 
@@ -606,6 +611,18 @@ int cvae_train_variants_needed(cvae_ctx* ctx, const cvae_net_desc* d, int B, int
     Dims m;
     if (make_train_dims(d, &m) || B < 1 || T < 1) return TV_ALL;
     return plan_train_pass(m, B, T).variants;
+}
+
+int cvae_plan_train_pass(cvae_ctx* ctx, const cvae_net_desc* d, int B, int T, int32_t out[12]) {
+    CVAE_ENTER(ctx);
+    Dims m;
+    if (int rc = make_train_dims(d, &m)) return rc;
+    if (B < 1 || T < 1 || !out) return fail(-1, "bad arguments: B=%d T=%d out=%p", B, T, (void*)out);
+    const TrainPlan pn = plan_train_pass(m, B, T);
+    out[0] = pn.Bp; out[1] = pn.fwd; out[2] = pn.fwd_rts; out[3] = pn.fwd_tiles; out[4] = pn.fwd_col_tiles; out[5] = pn.fwd_full_writes;
+    out[6] = pn.bwd; out[7] = pn.bwd_rts; out[8] = pn.bwd_per_launch; out[9] = pn.bwd_tiles; out[10] = pn.bwd_writes_gates;
+    out[11] = pn.variants;
+    return 0;
 }
 
 int cvae_net_prepare_train_v(cvae_ctx* ctx, const cvae_net_desc* d, const cvae_net_weights* w, void* image, size_t image_bytes, float gru_drop_p,

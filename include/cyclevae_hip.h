@@ -558,6 +558,17 @@ int cvae_net_prepare_train(cvae_ctx* ctx, const cvae_net_desc* d, const cvae_net
 int cvae_net_prepare_train_v(cvae_ctx* ctx, const cvae_net_desc* d, const cvae_net_weights* w, void* image, size_t image_bytes, float gru_drop_p,
                              int variants, void* stream);
 int cvae_train_variants_needed(cvae_ctx* ctx, const cvae_net_desc* d, int B, int T);
+/* cvae_plan_train_pass (additive, tests): the recurrence forms a train-mode pass of that shape takes under the current options, as
+ * the rule the passes themselves consult computes them.  out (HOST int32[12]) = {Bp = rows per frame of the time-major buffers;
+ * forward form: 0 word exchange, 1 exact operands in 16-unit blocks, 2 in 8-unit blocks with 32-row tiles, 3 with 16-row tiles,
+ * 4 fp16 pairs, 5 fp32 MFMA, 6 T per-step launches; forward row tiles side by side; the most row tiles one forward block row owns
+ * per step (32-row tiles of form 2, 16-row tiles otherwise; 0 for forms 0 and 6); 16-column tiles per block of the per-step forward;
+ * 1 when the forward writes the gate tape and the state copies in full (no memset); reverse form: 0 word exchange, 1 exact
+ * operands in 16-unit blocks, 2 in 8-unit blocks, 3 fp16 pairs, 4 2T per-step launches; reverse row tiles side by side; 16-row tiles
+ * per launch of the reverse recurrence (0: the whole pass in one); the most tiles one reverse block row owns in one launch (0 for
+ * forms 0 and 4); 1 when the reverse recurrence writes every row of the gate gradients (no memset); the image variants as
+ * cvae_train_variants_needed}.  Returns 0 or an error. */
+int cvae_plan_train_pass(cvae_ctx* ctx, const cvae_net_desc* d, int B, int T, int32_t out[12]);
 size_t cvae_train_tape_bytes(cvae_ctx* ctx, const cvae_net_desc* d, int B, int T);     /* per pass, kept until its backward */
 size_t cvae_train_scratch_bytes(cvae_ctx* ctx, const cvae_net_desc* d, int B, int T);  /* shared by all passes */
 

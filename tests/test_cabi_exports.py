@@ -60,6 +60,27 @@ def test_deep_plan_query_answers_without_a_gpu():
         lib.plan_pass_deep_tiles(d, 1, 70, 3, 0)
 
 
+def test_train_plan_query_answers_without_a_gpu():
+    """cvae_plan_train_pass on the shipped library: Bp, forms of the enum's range, a tiling that covers Bp in both directions (which
+    one depends on the device's CU count: tests/train_cases.py holds every case to the MI355X's), per-step launches for one frame."""
+    import pytest
+    lib = _cabi.CvaeLib(LIB)
+    assert "cvae_plan_train_pass" in _cabi.ADDITIVE and len(_cabi.TRAIN_PLAN_FIELDS) == 12
+    d = lib.desc(6, 8, 64, 3, 2, True, False)
+    p = lib.plan_train_pass(d, 70, 3)
+    assert list(p) == list(_cabi.TRAIN_PLAN_FIELDS) and p["Bp"] == 96
+    assert _cabi.TRAIN_FWD_LL < p["fwd"] <= _cabi.TRAIN_FWD_STEPS and _cabi.TRAIN_BWD_LL < p["bwd"] <= _cabi.TRAIN_BWD_STEPS
+    if p["fwd"] != _cabi.TRAIN_FWD_STEPS:
+        assert p["fwd_rts"] >= 1 and p["fwd_rts"] * p["fwd_tiles"] >= (3 if p["fwd"] == _cabi.TRAIN_FWD_X3 else 6) and p["fwd_full_writes"] == 1
+    if p["bwd"] != _cabi.TRAIN_BWD_STEPS:
+        assert p["bwd_rts"] >= 1 and p["bwd_rts"] * p["bwd_tiles"] >= min(6, p["bwd_per_launch"] or 6) and p["bwd_tiles"] <= 2
+    one = lib.plan_train_pass(d, 70, 1)
+    assert (one["fwd"], one["bwd"], one["fwd_tiles"], one["bwd_tiles"]) == (_cabi.TRAIN_FWD_STEPS, _cabi.TRAIN_BWD_STEPS, 0, 0)
+    assert lib.plan_train_pass(lib.desc(6, 8, 48, 3, 2, True, False), 5, 4)["fwd"] == _cabi.TRAIN_FWD_STEPS      # no persistent form off 64 / 1024
+    with pytest.raises(_cabi.CvaeError):
+        lib.plan_train_pass(d, 0, 3)
+
+
 def test_recurrent_kernels_do_not_spill():
     """hipcc's kernel-resource-usage remarks of the shipped build: the all-resident recurrent kernels of the default paths use no
     scratch (a private segment puts a ~240 us gap in front of every launch on MI355X and turns register traffic into memory

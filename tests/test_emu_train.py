@@ -111,20 +111,55 @@ def test_adam_step_matches_torch(lib):
         assert float(np.max(np.abs(p - pt.detach().numpy()))) <= 2e-7
 
 
+PLAN_KEYS = ("Bp", "fwd", "fwd_rts", "fwd_tiles", "bwd", "bwd_rts", "bwd_per_launch", "bwd_tiles")
+
+
+def variant_plan(env):
+    """[fwd, fwd_rts, fwd_tiles, bwd, bwd_rts, bwd_per_launch, bwd_tiles] of the 18-row pass (two 16-row tiles, ONE 32-row tile) that
+    plan_train_pass must give for an option set of test_train_recurrence_variants_agree: what each option is in the matrix for."""
+    rts = 1 if env.get("max_rt") == 1 else 2
+    tiles = 2 // rts
+    if env.get("train_per_step"):
+        fwd = [_cabi.TRAIN_FWD_STEPS, 0, 0]
+    elif env.get("train_fp32_mfma"):
+        fwd = [_cabi.TRAIN_FWD_FP32, rts, tiles]
+    elif env.get("train_kernel"):
+        fwd = [_cabi.TRAIN_FWD_PAIR, rts, tiles]
+    elif env.get("train_fwd_geom") == 1:
+        fwd = [_cabi.TRAIN_FWD_W3, rts, tiles]
+    elif env.get("x3_tile") == 32:
+        fwd = [_cabi.TRAIN_FWD_X3, 1, 1]
+    else:
+        fwd = [_cabi.TRAIN_FWD_X3H, rts, tiles]
+    if env.get("train_bwd_per_step"):
+        bwd = [_cabi.TRAIN_BWD_STEPS, 0, 0, 0]
+    elif env.get("train_kernel"):
+        bwd = [_cabi.TRAIN_BWD_PAIR, rts, 0, tiles]
+    elif env.get("train_bwd_geom") == 1:
+        bwd = [_cabi.TRAIN_BWD_W3, 1, 0, 2]          # (two tiles per block wherever the pass has two)
+    else:
+        bwd = [_cabi.TRAIN_BWD_X3, rts, 0, tiles]
+    return fwd + bwd
+
+
 @pytest.mark.parametrize("env", [{"max_rt": 1}, {"train_per_step": 1}, {"train_per_step": 1, "step_col_tiles": 2}, {"train_old_gemm": 1},
                                  {"train_fp32_mfma": 1}, {"train_fp32_mfma": 1, "max_rt": 1},
                                  {"train_bwd_per_step": 1}, {}, {"train_bwd_geom": 1}, {"train_bwd_geom": 1, "max_rt": 1}, {"train_bwd_geom": 1, "bwd_w3_l1_h64": 1},
                                  {"train_fwd_geom": 1}, {"train_fwd_geom": 1, "max_rt": 1, "train_bwd_geom": 1}, {"train_fwd_geom": 1, "bwd_w3_l1_h64": 1}, {"train_kernel": 1}, {"train_kernel": 1, "max_rt": 1}, {"x3_tile": 16}, {"x3_tile": 32},
                                  {"x3_tile": 16, "max_rt": 1}])
 def test_train_recurrence_variants_agree(lib, golden, options, env):
-    """Persistent train recurrences (split-fp16 default, all-fp32 MFMA form) with one / two row tiles per block, and the
-    per-step fallback and the simple GEMM kernels kept as unaligned-operand fallbacks, against the reference.  The backward
-    recurrence is the persistent k_train_bwd_steps by default (one launch, folded feedback path, gate gradients exchanged as
-    scaled fp16 pairs; option max_rt = 1: two row tiles per block) or 2T per-step launches (option train_bwd_per_step)."""
+    """The option matrix of the training recurrences on one 18-row pass (two 16-row tiles) against the reference; what each option
+    set must plan is asserted with cvae_plan_train_pass (variant_plan): by default the exact-operand 8-unit forms k_train_fwd_steps_x3h /
+    k_train_bwd_steps_x3 with one tile per block, max_rt = 1 two per block, x3_tile = 32 one 32-row tile on k_train_fwd_steps_x3,
+    train_fwd_geom / train_bwd_geom = 1 the 16-unit forms, train_kernel = 1 the fp16-pair forms, train_fp32_mfma the fp32-MFMA
+    forward, train_per_step / train_bwd_per_step the per-step launches of one direction (train_old_gemm and step_col_tiles change
+    GEMM and per-step kernels, not the plan)."""
     options(**env)
     g = golden("train_h64")
     P = synth.CycleVAEProblem(B=18, T=7, in_dim=6, out_dim=4, lat_dim=4, hidden=64, n_cyc=1, bias_scale=0.1, tag="train_h64")
     enc = TrainNet(lib, P.enc, 6, 8, 64)
+    plan = lib.plan_train_pass(enc.d, 18, 7)
+    assert [plan[k] for k in PLAN_KEYS] == [32] + variant_plan(env), (env, plan)
     cot = synth.normal("train_h64/cot_enc", (18, 7, 8))
     out, yl, hl, dx, grads = enc.run(P.x, P.y_in_enc, None, g["enc_cmask"], g["enc_gmask"], cot, 4)
     assert rel_err(out, g["enc_out"]) <= 5e-5 and rel_err(dx, g["enc_dx"]) <= 1e-4
@@ -207,10 +242,22 @@ def test_stage4_loss_kernel_matches_the_torch_loss(lib, half, select, flen_acc):
     assert float(loss[0]) > float(ref) or n_sel == 0
 
 
+# (B, geom, train_kernel) -> the plan of test_exact_operand_train_recurrence_several_tiles, as PLAN_KEYS
+SEVERAL_TILE_PLANS = {
+    (70, 0, 0): [96, _cabi.TRAIN_FWD_X3H, 1, 6, _cabi.TRAIN_BWD_X3, 1, 2, 2], (70, 1, 0): [96, _cabi.TRAIN_FWD_W3, 1, 6, _cabi.TRAIN_BWD_W3, 1, 2, 2],
+    (40, 1, 0): [64, _cabi.TRAIN_FWD_W3, 4, 1, _cabi.TRAIN_BWD_W3, 2, 0, 2], (130, 0, 0): [160, _cabi.TRAIN_FWD_X3H, 1, 10, _cabi.TRAIN_BWD_X3, 1, 2, 2],
+    (70, 0, 1): [96, _cabi.TRAIN_FWD_PAIR, 1, 6, _cabi.TRAIN_BWD_PAIR, 1, 0, 6], (70, 1, 1): [96, _cabi.TRAIN_FWD_PAIR, 1, 6, _cabi.TRAIN_BWD_PAIR, 1, 0, 6],
+    (40, 1, 1): [64, _cabi.TRAIN_FWD_PAIR, 4, 1, _cabi.TRAIN_BWD_PAIR, 4, 0, 1], (130, 0, 1): [160, _cabi.TRAIN_FWD_PAIR, 1, 10, _cabi.TRAIN_BWD_PAIR, 1, 0, 10]}
+
+
 @pytest.mark.parametrize("B,T,max_rt,tile,geom", [(70, 4, 1, 16, 0), (70, 4, 1, 32, 1), (40, 5, 0, 16, 1), (130, 3, 1, 32, 0)])
 def test_exact_operand_train_recurrence_several_tiles(lib, options, B, T, max_rt, tile, geom):
-    """k_train_fwd_steps_x3 with one, three and (130 rows, one tile group) five-tile blocks -- the last falls back to the pair kernel
-    (at most four tiles per block keep h in registers) -- against the stock-torch checker and against the pair-form kernel:
+    """The exact-operand recurrences with several tiles per block, in the forms asserted with cvae_plan_train_pass
+    (SEVERAL_TILE_PLANS): 70 rows on one block row as six 16-row tiles -- on the 8-unit forms (k_train_fwd_steps_x3h re-reading its h;
+    k_train_bwd_steps_x3 in launches of two tiles) and, geom 1, on the 16-unit forms (k_train_fwd_steps_w3 / k_train_bwd_steps_w3
+    likewise) --, 40 rows on the 16-unit forms with one tile per block forward and two in reverse, and 130 rows with x3_tile 32 on one
+    block row: five 32-row tiles exceed what k_train_fwd_steps_x3 keeps in registers (four), so the plan sends the pass to the
+    16-row-tile kernel k_train_fwd_steps_x3h with ten tiles.  Against the stock-torch checker and against the pair-form kernels:
     outputs, h_last, dx and every parameter gradient."""
     import torch
     from oracle import torch_stock as ts
@@ -223,9 +270,11 @@ def test_exact_operand_train_recurrence_several_tiles(lib, options, B, T, max_rt
     (out_r * torch.from_numpy(cot)).sum().backward()
     res = {}
     for kern in (0, 1):
-        # (geom 1: the 16-unit forward and reverse recurrences, five / three tiles per block)
+        # (geom 1: the 16-unit forward and reverse recurrences -- 70 rows: six tiles per block forward, two per launch in reverse; 40 rows: one / two)
         options(train_kernel=kern, max_rt=max_rt, x3_tile=tile, train_bwd_geom=geom, train_fwd_geom=geom)
         enc = TrainNet(lib, P.enc, 6, 8, 64)
+        plan = lib.plan_train_pass(enc.d, B, T)
+        assert [plan[k] for k in PLAN_KEYS] == SEVERAL_TILE_PLANS[(B, geom, kern)], (B, geom, kern, plan)
         res[kern] = enc.run(P.x, P.y_in_enc, h_in, cm, gm, cot, 4)
     for kern, (out, yl, hl, dx, grads) in res.items():
         assert rel_err(out, out_r.detach().numpy()) <= 2e-5 and rel_err(hl, h_r.detach().numpy()) <= 2e-5, kern

@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+import _cabi
 import synth
 from train_util import TRAINABLE, chain_loss, cpu_step, make_masks
 
@@ -419,12 +420,23 @@ def test_step_outside_the_exchange_range_is_repeated_on_the_fp32_reverse_recurre
     assert step.fallbacks == 1 and step.step_no == 1 and np.isfinite(float(loss)) and bool(torch.isfinite(step.grads.flat).all())
 
 
+# (B, train_kernel) -> [Bp, fwd, fwd_rts, fwd_tiles, bwd, bwd_rts, bwd_per_launch, bwd_tiles] of test_train_pass_many_row_tiles
+MANY_TILE_PLANS = {(200, 0): [224, _cabi.TRAIN_FWD_W3, 4, 4, _cabi.TRAIN_BWD_W3, 4, 8, 2],
+                   (200, 1): [224, _cabi.TRAIN_FWD_PAIR, 2, 7, _cabi.TRAIN_BWD_PAIR, 2, 0, 7],
+                   (100, 0): [128, _cabi.TRAIN_FWD_X3H, 2, 4, _cabi.TRAIN_BWD_W3, 4, 0, 2],
+                   (100, 1): [128, _cabi.TRAIN_FWD_PAIR, 2, 4, _cabi.TRAIN_BWD_PAIR, 2, 0, 4]}
+
+
 @pytest.mark.parametrize("B,tile", [(200, 0), (100, 16)])
 def test_train_pass_many_row_tiles(gv, dev, B, tile):
-    """One train-mode encoder pass at hu1024 with many row tiles per block: B=200 = seven 32-row tiles on two block rows (four per
-    block: h kept in four registers per thread) and, forced to the 16-row geometry, B=100 = seven 16-row tiles (the own h re-read from
-    the fp32 copy); reverse recurrence with seven / thirteen tiles per block row.  Sampled rows against the stock-torch checker run
-    on those rows alone (rows are independent), outputs and dx; parameter gradients against the same pass on the fp16-pair kernels."""
+    """One train-mode encoder pass at hu1024 with many row tiles, in the forms the plan gives (asserted with cvae_plan_train_pass):
+    B=200 at default options = fourteen 16-row tiles on the 16-unit forms -- forward k_train_fwd_steps_w3 on four block rows with 4/4/3/3
+    tiles (the own h re-read from the fp32 copy), reverse k_train_bwd_steps_w3 in launches of 8 + 6 tiles, at most two per block -- and
+    B=100 forced to x3_tile 16 = eight 16-row tiles: forward k_train_fwd_steps_x3h with four per block on two block rows, reverse
+    k_train_bwd_steps_w3 in one launch, two per block.  (The 32-row-tile forward k_train_fwd_steps_x3<16> and the 8-unit reverse over
+    several launches run in tests/test_train_forms_gpu.py.)  Sampled rows against the stock-torch checker run on those rows alone (rows
+    are independent), outputs and dx; parameter gradients against the same pass on the fp16-pair kernels (seven / four tiles per block
+    both ways)."""
     from oracle import torch_stock as ts
     T = 4
     P = synth.CycleVAEProblem(B=B, T=T, bias_scale=0.05, tag="manytrain%d" % B)
@@ -441,6 +453,9 @@ def test_train_pass_many_row_tiles(gv, dev, B, tile):
             lib.set_option("train_kernel", kern)
             lib.set_option("x3_tile", tile)
             enc = module(gv, P.enc, 54, 64, 1024, True, dev)
+            plan = lib.plan_train_pass(lib.desc(54, 64, 1024, 3, 2, True, False), B, T)
+            got = [plan[k] for k in ("Bp", "fwd", "fwd_rts", "fwd_tiles", "bwd", "bwd_rts", "bwd_per_launch", "bwd_tiles")]
+            assert got == MANY_TILE_PLANS[(B, kern)], (B, kern, plan)
             xt = t(P.x).requires_grad_(True)
             enc._debug_masks = (t(masks[0]), t(masks[1]))
             out, yl, hl = enc(xt, t(P.y_in_enc), do=True, clamp_vae=True, lat_dim=32)
@@ -526,9 +541,10 @@ def test_train_pass_full_size_hu2048(gv, dev):
 @pytest.mark.parametrize("kind,B", [("enc", 64), ("dec2", 128)], ids=["enc_64_rows", "rec_cv_stacked_128_rows"])
 def test_train_pass_full_size_hu1024(gv, dev, kind, B):
     """The geometry bench.py's train leg TIMES (BASELINE configs[2], reference gru_vae.py:376-382, train...:1326-1338): one train-mode
-    pass at hu1024 over 64 utterances x a full 80-frame window (k_train_fwd_steps_x3h: two 16-row tiles per block) and the stacked
-    rec || cv decoder pass of 128 rows (k_train_fwd_steps_x3: two 32-row tiles per block), reverse recurrence k_train_bwd_steps_x3,
-    default options.  Against the stock-torch checker on the WHOLE batch: outputs, carried state, dx and every parameter gradient
+    pass at hu1024 over 64 utterances x a full 80-frame window (forward k_train_fwd_steps_w3: four 16-row tiles, one per block row;
+    reverse k_train_bwd_steps_w3: two block rows with two tiles each) and the stacked rec || cv decoder pass of 128 rows (eight tiles:
+    two per block on four block rows, forward and reverse, one launch), default options; the plan is asserted with
+    cvae_plan_train_pass.  Against the stock-torch checker on the WHOLE batch: outputs, carried state, dx and every parameter gradient
     (sums over all 5,120 / 10,240 frames) -- first as a plain autograd backward, then as stage4.Stage4Step runs it: gradients
     accumulated into existing p.grad, weight-gradient GEMMs on the side stream, two backward passes in flight on alternating
     scratch buffers (the second pass re-uses the first one's scratch only after its side-stream work)."""
@@ -547,6 +563,11 @@ def test_train_pass_full_size_hu1024(gv, dev, kind, B):
     (out_r * torch.from_numpy(cot)).sum().backward()
     m = module(gv, sd, cin, cout, 1024, enc_like, dev)
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    lib = gv._lib()
+    plan = lib.plan_train_pass(lib.desc(cin, cout, 1024, 3, 2, enc_like, not enc_like), B, T)
+    assert [plan[k] for k in ("Bp", "fwd", "fwd_rts", "fwd_tiles", "bwd", "bwd_rts", "bwd_per_launch", "bwd_tiles")] == \
+        [B, _cabi.TRAIN_FWD_W3, 4, B // 64, _cabi.TRAIN_BWD_W3, B // 32, 0, 2], plan
+    assert plan["fwd_full_writes"] == 1 and plan["bwd_writes_gates"] == 1
 
     def one_pass():
         xt = t(x).requires_grad_(True)

@@ -13,8 +13,10 @@ status sink and are read back with cvae_workspace_status; train passes have no s
 host reads) that must stay zero.
 
 Forms.  The expected recurrence of every eval case is asserted with cvae_plan_pass / cvae_plan_pass_deep before the pass runs, so a
-case cannot silently move to another kernel.  Training has no form query: off H = 64 / 1024 (persist_ok, csrc/cvae_train.inc) every
-pass is the per-step forward (k_gru_step_train) and the per-step reverse (k_gru_step_bwd + k_bwd_step_gemm).
+case cannot silently move to another kernel.  The forms of a train case are asserted with cvae_plan_train_pass: off H = 64 / 1024
+(persist_ok, csrc/cvae_train.inc) every pass is the per-step forward (k_gru_step_train, FWD_STEPS) and the per-step reverse
+(k_gru_step_bwd + k_bwd_step_gemm, BWD_STEPS); the persistent forms of H = 64 / 1024 have a table of their own, tests/train_cases.py,
+which runs through the same TrainNet.
 
 What the widths reach, by kernel:
   k_gru_steps_ll      H % 64 == 0 up to 1024, <= 3 rows: 128 (waves 1-3 idle but voting), 192 (wave 0 with three words), 320 (wave 1
@@ -113,6 +115,9 @@ class TrainCase(collections.namedtuple("TrainCase", "H rows T kind carry opts"))
     def tag(self):
         return "width/t/" + self.id
 
+    wtag = tag          # the weights are drawn with the case's own tag
+    sub_of = 0          # (train_cases.FormCase: the case is the first rows of a larger problem)
+
 
 def _tcase(H, rows, T, kind="enc", carry=False, **opts):
     return TrainCase(H, rows, T, kind, carry, tuple(sorted(opts.items())))
@@ -133,6 +138,7 @@ TRAIN_CASES = [
     _tcase(80, 5, 1), _tcase(272, 5, 1),
     _tcase(48, 5, 4, train_old_gemm=1),
 ]
+assert all(c.H not in (64, 1024) for c in TRAIN_CASES), "this table is about the per-step training kernels"
 
 
 def emu_case(c):
@@ -413,8 +419,9 @@ class TrainNet(object):
         A.sync()
         assert A.guards_intact(), "cvae_net_prepare_train wrote outside the train image (H = %d)" % hidden
 
-    def run(self, x, y_in, h_in, cmask, gmask, cot, clamp_lat_dim, what=""):
-        """Forward + backward of sum(out * cot): dict(out, y_last [B,Co], h_last [B,H], dx, grads {state key: array})."""
+    def run(self, x, y_in, h_in, cmask, gmask, cot, clamp_lat_dim, what="", counters=False):
+        """Forward + backward of sum(out * cot): dict(out, y_last [B,Co], h_last [B,H], dx, grads {state key: array}).  counters: also
+        "counters", the eight words of cvae_train_debug_counters read from the pass's scratch (option train_prof)."""
         mem, lib, d = self.mem, self.mem.lib, self.d
         x = np.asarray(x, np.float32)
         B, T, Cin = x.shape
@@ -438,6 +445,7 @@ class TrainNet(object):
             lib.backward(d, self.A.address(self.image), adr(ocot), B, T, clamp_lat_dim, adr(otape), adr(oscr), sb, adr(odx),
                          {f: adr(o) for f, o in og.items()}, accumulate=False, stream=mem.stream)
             A.sync()
+            words = lib.train_debug_counters(d, B, T, adr(oscr), mem.stream) if counters else None
         finally:
             lib.set_status_sink(None)
         assert mem.sink_words() == [0, 0, 0, 0], "%s: status sink %s" % (what, mem.sink_words())
@@ -448,26 +456,38 @@ class TrainNet(object):
                "grads": {GRAD_KEYS[f]: A.read(o, int(np.prod(gshape[f]))).reshape(gshape[f]) for f, o in og.items()}}
         for name, a in list(res.items())[:4] + list(res["grads"].items()):
             assert np.all(np.isfinite(a)), "%s: %s not fully written / not finite" % (what, name)
+        if counters:
+            res["counters"] = words
         return res
 
 
 def train_problem(c):
     """(state dict, in_dim, out_dim, x, y_in, h_in, cmask, gmask, cot, clamp_lat_dim) of a train case: inputs of
-    synth.CycleVAEProblem, masks of train_util.make_masks (every form sees the same dropout)."""
-    ind = _in_dim(c.H)
-    P = synth.CycleVAEProblem(B=c.rows, T=c.T, in_dim=ind, out_dim=ind - 4, lat_dim=4, hidden=c.H, n_cyc=1, bias_scale=0.1, tag=c.tag)
+    synth.CycleVAEProblem, masks of train_util.make_masks (every form sees the same dropout).  Weights and feature statistics are
+    drawn with c.wtag, inputs and masks with c.tag (the same for a width case; train_cases.FormCase shares one set of weights per H
+    and one set of inputs per problem, however the pass is tiled).  c.sub_of > 0: the first c.rows rows of the c.sub_of-row problem."""
+    ind, rows = _in_dim(c.H), c.sub_of or c.rows
+    assert rows >= c.rows
+    P = synth.CycleVAEProblem(B=rows, T=c.T, in_dim=ind, out_dim=ind - 4, lat_dim=4, hidden=c.H, n_cyc=1, bias_scale=0.1, tag=c.wtag)
+    if c.wtag != c.tag:
+        P.x = synth.features(c.tag + "/x", rows, c.T, P.mu, P.sigma)
     masks = train_util.make_masks(P, 1, 1, tag=c.tag + "/masks")
     if c.kind == "enc":
         sd, i, o, x, y_in, clamp = P.enc, ind, 8, P.x, P.y_in_enc, 4
     else:
-        x = np.concatenate([P.code_src, synth.normal(c.tag + "/z", (c.rows, c.T, 4))], 2).astype(np.float32)
+        x = np.concatenate([P.code_src, synth.normal(c.tag + "/z", (rows, c.T, 4))], 2).astype(np.float32)
         sd, i, o, y_in, clamp = P.dec, 6, ind - 4, P.y_in_dec, -1
     h_in = None
     if c.carry:
-        h_in = (0.3 * synth.normal(c.tag + "/h_in", (1, c.rows, c.H))).astype(np.float32)
+        h_in = (0.3 * synth.normal(c.tag + "/h_in", (1, rows, c.H))).astype(np.float32)
         y_in = (y_in + 0.2 * synth.normal(c.tag + "/y_in", y_in.shape)).astype(np.float32)
     cm, gm = masks[c.kind][0]
-    cot = synth.normal(c.tag + "/cot", (c.rows, c.T, o))
+    cot = synth.normal(c.tag + "/cot", (rows, c.T, o))
+    if rows != c.rows:
+        n = c.rows
+        x, y_in, cm, gm, cot = x[:n], y_in[:n], cm[:n], gm[:, :n], cot[:n]
+        h_in = None if h_in is None else h_in[:, :n]
+        x, y_in, cm, gm, cot = (np.ascontiguousarray(a) for a in (x, y_in, cm, gm, cot))
     return sd, i, o, x, y_in, h_in, cm, gm, cot, clamp
 
 
@@ -482,21 +502,34 @@ def rel_err(a, ref):
     return float(np.max(np.abs(a.astype(np.float64) - ref))) / max(1.0, float(np.max(np.abs(ref))))
 
 
-def run_train_case(mem, c, ref, note, bound_out, bound_grad):
-    """One train case against `ref` (train_reference(c)); the caller has set c.opts on mem.lib.  Returns (worst output, worst gradient)."""
-    assert c.H not in (64, 1024), "the table is about the per-step training kernels"
-    sd, i, o, x, y_in, h_in, cm, gm, cot, clamp = train_problem(c)
-    net = TrainNet(mem, sd, i, o, c.H)
-    got = net.run(x, y_in, h_in, cm, gm, cot, clamp, what=c.id)
+def train_distances(got, ref):
+    """({output: distance}, {gradient: distance}) of TrainNet.run's result to a train_reference."""
     outs = {k: rel_err(got[k], ref[k]) for k in ("out", "y_last", "h_last")}
     grads = {"dx": rel_err(got["dx"], ref["dx"])}
     for k in GRAD_KEYS.values():
         grads["d" + k] = rel_err(got["grads"][k], ref["grads"][k])
+    return outs, grads
+
+
+def check_train_result(mem, c, got, ref, note, bound_out, bound_grad):
+    """Prints and records the distances of a train pass to its reference, then holds them to the bounds; (worst output, worst gradient)."""
+    outs, grads = train_distances(got, ref)
     wo, wg = max(outs.values()), max(grads.values())
     note("%-9s train %-36s outputs %.3e (%s)  gradients %.3e (%s)" % (mem.name, c.id, wo, max(outs, key=outs.get), wg, max(grads, key=grads.get)))
     assert wo <= bound_out, (c.id, outs, bound_out)
     assert wg <= bound_grad, (c.id, grads, bound_grad)
     return wo, wg
+
+
+def run_train_case(mem, c, ref, note, bound_out, bound_grad):
+    """One case of TRAIN_CASES against `ref` (train_reference(c)); the caller has set c.opts on mem.lib.  The plan must be the per-step
+    launches in both directions.  Returns (worst output, worst gradient)."""
+    sd, i, o, x, y_in, h_in, cm, gm, cot, clamp = train_problem(c)
+    net = TrainNet(mem, sd, i, o, c.H)
+    plan = mem.lib.plan_train_pass(net.d, c.rows, c.T)
+    assert (plan["fwd"], plan["bwd"]) == (_cabi.TRAIN_FWD_STEPS, _cabi.TRAIN_BWD_STEPS), "%s: planned %s, the table is about the per-step kernels" % (c.id, plan)
+    got = net.run(x, y_in, h_in, cm, gm, cot, clamp, what=c.id)
+    return check_train_result(mem, c, got, ref, note, bound_out, bound_grad)
 
 
 # ---------------------------------------------------------------------------------------------------------------
