@@ -138,10 +138,12 @@ def chain_forward(run_pass, x, cvx, code_src, code_trg, y_in_enc, y_in_dec, eps,
     return trajs, state
 
 
-def frame_weights(B, T, flen_acc=None, select_utt_idx=None):
+def frame_weights(B, T, flen_acc=None, select_utt_idx=None, list_quirk=True):
     """What the reference's per-utterance slicing amounts to (train...:1363-1410), as three host lists: w[j][t] = 1/n_j for the
     first n_j = min(flen_acc[j], T) frames of a selected utterance, else 0 (mean over frames, summed over utterances);
-    last[j] = 1 for the LAST selected utterance; n_sel.  Defaults = every utterance, whole window."""
+    last[j] = 1 for the LAST selected utterance; n_sel.  Defaults = every utterance, whole window.
+    list_quirk=False (the utterance branch, :1589-1590, which appends KL(latcv) to its own list): last[j] = 1 for EVERY selected
+    utterance."""
     sel = list(range(B)) if select_utt_idx is None else [int(j) for j in select_utt_idx]
     nfr = [T] * B if flen_acc is None else [min(int(n), T) for n in flen_acc]
     w = [[0.0] * T for _ in range(B)]
@@ -152,10 +154,13 @@ def frame_weights(B, T, flen_acc=None, select_utt_idx=None):
     last = [0.0] * B
     if sel:
         last[sel[-1]] = 1.0
+    if not list_quirk:
+        for j in sel:
+            last[j] = 1.0
     return w, last, len(sel)
 
 
-def loss_terms(trajs, x, stdim, lat_dim, flen_acc=None, select_utt_idx=None, half_cyc=False, posterior="gauss"):
+def loss_terms(trajs, x, stdim, lat_dim, flen_acc=None, select_utt_idx=None, half_cyc=False, posterior="gauss", list_quirk=True):
     """Batch loss of one frame window from the trajectories of chain_forward, as the reference computes it (:1363-1410).
 
     Utterance j of select_utt_idx contributes the first n = flen_acc[j] frames of the window (Python slice clipping: at most T); the
@@ -164,11 +169,13 @@ def loss_terms(trajs, x, stdim, lat_dim, flen_acc=None, select_utt_idx=None, hal
     utterances and cycles -- with the reference's quirk at :1393 kept: for more than one selected utterance the `lat_src_cv` list is
     rebuilt from the `lat_src` list, so its sum is (sum of KL(lat) over the utterances) + KL(latcv of the LAST utterance) (SURVEY
     App. C.2; harmless at the recipe's batch_size_utt = 1).  half_cyc (n_cyc < 1 in the reference, :283-287) drops the rec_cyc /
-    latcv terms.  posterior="laplace": the KL terms are loss_vae_laplace's (gru_vae.py:130-139), everything else as above."""
+    latcv terms.  posterior="laplace": the KL terms are loss_vae_laplace's (gru_vae.py:130-139), everything else as above.
+    list_quirk=False: the utterance branch of the script (:1567-1643), whose lists are built correctly (:1589-1590): the sum over the
+    utterances of KL(lat) and of KL(latcv), each once.  The two forms agree for one selected utterance."""
     L = lat_dim
     laplace = _check_posterior(posterior)
     B, T = x.shape[0], x.shape[1]
-    wl, lastl, n_sel = frame_weights(B, T, flen_acc, select_utt_idx)
+    wl, lastl, n_sel = frame_weights(B, T, flen_acc, select_utt_idx, list_quirk)
     w = torch.tensor(wl, dtype=torch.float32, device=x.device)
     last = torch.tensor(lastl, dtype=torch.float32, device=x.device)
     tgt = x[:, :, stdim:]
@@ -186,13 +193,13 @@ def loss_terms(trajs, x, stdim, lat_dim, flen_acc=None, select_utt_idx=None, hal
         loss = loss + mcd(tr["rec"]) + kl_lat.sum()
         if not half_cyc and n_sel:
             loss = loss + mcd(tr["reccyc"])
-            if n_sel > 1:          # :1393: [KL(lat) of every utterance ..., KL(latcv) of the LAST selected one]
+            if n_sel > 1 and list_quirk:          # :1393: [KL(lat) of every utterance ..., KL(latcv) of the LAST selected one]
                 loss = loss + kl_lat.sum()
             loss = loss + (kl_rows(tr["latcv"]) * last).sum()
     return loss
 
 
-def script_loss_loop(trajs, x, stdim, lat_dim, flen_acc=None, select_utt_idx=None, half_cyc=False, log=None):
+def script_loss_loop(trajs, x, stdim, lat_dim, flen_acc=None, select_utt_idx=None, half_cyc=False, log=None, list_quirk=True):
     """The same batch loss the way the UNCHANGED training script forms it (train...:1363-1410): a Python loop over the selected
     utterances that slices each one's frames, calls the module's TWFSEloss / loss_vae on them, reads five scalars back to the host
     for the log (`.item()`, a device synchronisation each) and concatenates the per-utterance terms.  loss_terms is the vectorised
@@ -218,7 +225,9 @@ def script_loss_loop(trajs, x, stdim, lat_dim, flen_acc=None, select_utt_idx=Non
                 log.append(scalars)
             terms["rec"].append(m_rec)
             terms["reccyc"].append(m_cyc)
-            if k > 0:                     # :1393: the list is rebuilt from the `lat` list
+            if not list_quirk:            # :1589-1597, the utterance branch: the list of its own
+                terms["latcv"].append(kl_cv)
+            elif k > 0:                   # :1393: the list is rebuilt from the `lat` list
                 terms["latcv"] = list(terms["lat"]) + [kl, kl_cv]
             else:
                 terms["latcv"] = [kl_cv]
@@ -233,17 +242,47 @@ def script_loss_loop(trajs, x, stdim, lat_dim, flen_acc=None, select_utt_idx=Non
 
 def chain_loss(run_pass, x, cvx, code_src, code_trg, y_in_enc, y_in_dec, eps, lat_dim, n_cyc=2, masks=None,
                flen_acc=None, select_utt_idx=None, half_cyc=False, carry=None, return_state=False, stack_rec_cv=False,
-               posterior="gauss"):
+               posterior="gauss", list_quirk=True):
     """chain_forward + loss_terms: the batch loss of one frame window (train...:1299-1338 forward, :1363-1410 loss).
     x is the WINDOW of the padded utterance batch (batch_src[:, s:e+1]); flen_acc / select_utt_idx: the generator's bookkeeping
     (windows.plan_windows, reference train...:45-149).  return_state=True additionally returns the state dict for the next window
     and the five trajectories per cycle."""
     trajs, state = chain_forward(run_pass, x, cvx, code_src, code_trg, y_in_enc, y_in_dec, eps, lat_dim, n_cyc, masks, carry,
                                  stack_rec_cv, posterior=posterior)
-    loss = loss_terms(trajs, x, cvx.shape[2], lat_dim, flen_acc, select_utt_idx, half_cyc, posterior)
+    loss = loss_terms(trajs, x, cvx.shape[2], lat_dim, flen_acc, select_utt_idx, half_cyc, posterior, list_quirk)
     if return_state:
         return loss, state, trajs
     return loss
+
+
+def utterance_step_args(items):
+    """The keyword arguments of chain_loss / Stage4Step.__call__ for ONE utterance-length mini-batch: a 16-field yield of
+    loader.train_generator(batch_size=0) (train...:706: batch_src, batch_src_src_code, batch_src_trg_code, batch_src_trg,
+    batch_cv_src, c_idx_src, utt_idx_src, spcidx_src, spcidx_src_trg, featfile_src, featfile_src_trg, flens_src, flens_src_trg,
+    flens_spc_src, flens_spc_src_trg, n_batch_utt).  The script's utterance branch (:1491-1643) runs the ten passes on the whole
+    padded utterances, selects every utterance and cuts each one's loss to flens_src[j]; there is no window, hence no carry:
+
+        loss = step(y_in_enc=y_in_pp, y_in_dec=y_in_src, eps=None, **stage4.utterance_step_args(items))
+
+    The branch builds its per-utterance lists correctly (:1589-1590; the window branch's :1393 does not), so the batch loss is the plain
+    sum of the four terms over utterances and cycles: list_quirk=False (loss_terms).  With one utterance both forms are the same.
+    Returns {"x", "cvx", "code_src", "code_trg", "flen_acc", "select_utt_idx", "carry", "list_quirk"}.  Refuses the sentinel (c_idx_src < 0) and
+    the 22-field yields of batch_size > 0, whose window bookkeeping is items[5:9] / items[19:21]."""
+    if len(items) == 22:
+        raise ValueError("utterance_step_args: a 22-field yield is a frame window (batch_size > 0): pass its fields to the step yourself "
+                         "(x[:, s:e+1], flen_acc=items[20], select_utt_idx=items[19], carry)")
+    if len(items) != 16:
+        raise ValueError("utterance_step_args: a yield of %d fields, expected 16" % len(items))
+    if items[5] < 0:
+        raise ValueError("utterance_step_args: the sentinel (c_idx_src < 0) ends an epoch; there is nothing to step on")
+    x, n_utt = items[0], int(items[15])
+    flens = [int(v) for v in (items[11].tolist() if hasattr(items[11], "tolist") else items[11])]
+    if x.shape[0] != n_utt or len(flens) != n_utt:
+        raise ValueError("utterance_step_args: n_batch_utt = %d, batch_src holds %d utterances and flens_src %d" % (n_utt, x.shape[0], len(flens)))
+    if not all(1 <= n <= x.shape[1] for n in flens):
+        raise ValueError("utterance_step_args: flens_src %s do not fit the %d padded frames" % (flens, x.shape[1]))
+    return dict(x=x, cvx=items[4], code_src=items[1], code_trg=items[2], flen_acc=flens, select_utt_idx=list(range(n_utt)), carry=None,
+                list_quirk=False)
 
 
 def freeze_scalers(*modules):
@@ -382,6 +421,7 @@ class Stage4Step(object):
         self._owns_status = False
         self._saved_bwd_per_step = 0
         self.last_trajs = None
+        self._list_quirk = True                           # (the loss form of the call in progress: __call__)
 
     MAX_IN_FLIGHT = 6          # sync=False: the host waits for the oldest step when this many are queued
 
@@ -427,11 +467,11 @@ class Stage4Step(object):
 
     def _weights(self, B, T, flen_acc, select_utt_idx, dev):
         key = (B, T, None if flen_acc is None else tuple(int(v) for v in flen_acc),
-               None if select_utt_idx is None else tuple(int(v) for v in select_utt_idx))
+               None if select_utt_idx is None else tuple(int(v) for v in select_utt_idx), self._list_quirk)
         if key not in self._wcache:
             if len(self._wcache) > 64:
                 self._wcache.clear()
-            w, last, n_sel = frame_weights(B, T, flen_acc, select_utt_idx)
+            w, last, n_sel = frame_weights(B, T, flen_acc, select_utt_idx, self._list_quirk)
             self._wcache[key] = (torch.tensor(w, dtype=torch.float32, device=dev), torch.tensor(last, dtype=torch.float32, device=dev), n_sel)
         return self._wcache[key]
 
@@ -444,7 +484,7 @@ class Stage4Step(object):
         dev = x.device
         w, last, n_sel = self._weights(B, T, flen_acc, select_utt_idx, dev)
         full = (not half_cyc) and n_sel > 0
-        kl_scale = 2.0 if (full and n_sel > 1) else 1.0
+        kl_scale = 2.0 if (full and n_sel > 1 and self._list_quirk) else 1.0
         loss = torch.zeros(1, dtype=torch.float32, device=dev)
         frame_loss = torch.empty(B * T, dtype=torch.float32, device=dev)
         xc = x.contiguous()
@@ -503,9 +543,9 @@ class Stage4Step(object):
         loss = None
         if not self.fused:
             if self.script_loss:
-                loss = script_loss_loop(trajs, x, cvx.shape[2], self.lat_dim, flen_acc, select_utt_idx, half_cyc)
+                loss = script_loss_loop(trajs, x, cvx.shape[2], self.lat_dim, flen_acc, select_utt_idx, half_cyc, list_quirk=self._list_quirk)
             else:
-                loss = loss_terms(trajs, x, cvx.shape[2], self.lat_dim, flen_acc, select_utt_idx, half_cyc, self.posterior)
+                loss = loss_terms(trajs, x, cvx.shape[2], self.lat_dim, flen_acc, select_utt_idx, half_cyc, self.posterior, self._list_quirk)
         if self.overlap_wgrad:
             for m in self.mods.values():
                 m._grad_sink = True
@@ -703,12 +743,14 @@ class Stage4Step(object):
             pass
 
     def __call__(self, x, cvx, code_src, code_trg, y_in_enc, y_in_dec, eps, masks=None, flen_acc=None, select_utt_idx=None,
-                 carry=None, return_state=False, half_cyc=False):
+                 carry=None, return_state=False, half_cyc=False, list_quirk=True):
         """One step on the frame window x [B,T,Cin].  flen_acc / select_utt_idx / carry as in chain_loss (windows after the first
-        of an utterance batch pass the previous call's state as `carry`, train...:1299-1311).  Returns the loss (0-dim tensor),
-        with return_state=True (loss, state)."""
+        of an utterance batch pass the previous call's state as `carry`, train...:1299-1311).  list_quirk=False: the loss of the
+        script's utterance branch (loss_terms; utterance_step_args sets it).  Returns the loss (0-dim tensor), with
+        return_state=True (loss, state)."""
         import gru_vae
         self._want_state = return_state
+        self._list_quirk = bool(list_quirk)
         lagged = self.fused and not self.sync and x.is_cuda
         if lagged:
             self._lagged_check()

@@ -1,5 +1,6 @@
 """What the stage-4 training loop does AROUND every step, on the device and without a host stall (reference
-train_gru_cyclevae_gauss_batch.py:660-739, :1312-1316, :1339-1353, :1364-1472; utterance-length mini-batches, :1476-1665, are not built).
+train_gru_cyclevae_gauss_batch.py:660-739, :1312-1316, :1339-1353, :1364-1472: TrainLog, frame windows, batch_size > 0; :705-706,
+:1476-1665: UttLog, utterance-length mini-batches, batch_size == 0).
 
 The script reads five scalars back per utterance and cycle (`.item()`), runs four dtw_c.calc_mcd per utterance and cycle on host
 copies, copies three trajectories per window to the host for its GV buffers, and at the end of an utterance batch runs one more
@@ -20,6 +21,19 @@ The GV rule of :1339-1348 appends the variances of the PREVIOUS utterance batch 
 reference's generator yields one dataloader batch per pass and the loop resets iter_count at the sentinel, so with it the rule never
 fires and the epoch line prints nan for the six GV figures -- exactly as the script does.  The rule is implemented as written: it
 fires when two utterance batches follow each other without a sentinel between them.
+
+Utterance-length mini-batches (UttLog): the script's branch runs the extra encoder pass BEFORE the step (:1489-1490), appends the GV
+variances of the three cycle-0 trajectories per utterance at every step (:1516-1524: no "previous batch" rule, the epoch line shows
+real GV figures), aligns per utterance on cycle 0 (:1526-1545) and logs the five loss figures and four calc_mcd means per utterance
+and cycle (:1567-1582, without the list quirk of :1393).  Here:
+
+  per step         before(): the no-grad encoder pass over batch_src_trg on the current stream, ahead of the step (pre-update weights);
+                   after(): ONE cvae_trainlog_window launch over the whole padded utterances (no accumulators) and ONE MetricPlan
+                   (3 B STAT_GV, 4 B STAT_GATHER64, 2 B alignments, B latent distances) reading the step's cycle-0 trajectories
+                   directly, one copy of [record | plan results | loss] to a pinned slot behind one event
+  per epoch        epoch_end(): shared with TrainLog
+
+TrainLog and UttLog share the lists, the resets, the pinned slots, poll / lines and epoch_end through _LogBase.
 """
 import os
 
@@ -68,35 +82,24 @@ def _std(v):
     return float(np.std(v)) if len(v) else float("nan")
 
 
-class TrainLog(object):
-    """TrainLog(model_encoder, model_decoder, lat_dim, stdim, gv_src_mean, gv_trg_mean, n_cyc=2, spk_src=None, half_cyc=False), used
-    around an unchanged stage4.Stage4Step:
-
-        tl.before(items, y_in_pp)      # items: one 22-field yield of loader.train_generator (batch_size > 0), or the sentinel
-        loss, state = step(...)
-        tl.after(items, step.last_trajs, loss)
-        for line in tl.lines(): logging.info(line)
-        ...
-        s = tl.epoch_end()             # after before(sentinel): the figures of :722-738 and s["line"], then the resets of :1202-1269
-
-    Neither before() on a window nor after() waits for the device.  Timing fields: after(..., sec=) takes the caller's seconds for
-    the "(%.3f sec)" of :1472 and the "(%.3f min., %.3f sec / batch)" of :739; without it both parentheses are omitted.
-    epoch_idx (0 on construction) numbers the epoch line; set it when resuming."""
+class _LogBase(object):
+    """What TrainLog and UttLog share: the script's lists and their resets (:1202-1269), pinned slots behind events, the host half's
+    queue (poll / lines) and the epoch report (:719-739).  A subclass queues (kind, event, slot, meta) in _pending and names the
+    method that takes a finished slot of each kind in _TAKE."""
 
     MAX_IN_FLIGHT = stage4.Stage4Step.MAX_IN_FLIGHT
+    _TAKE = {}
 
     def __init__(self, model_encoder, model_decoder, lat_dim, stdim, gv_src_mean, gv_trg_mean, n_cyc=2, spk_src=None, half_cyc=False):
         if not 1 <= int(n_cyc) <= _cabi.TRAINLOG_MAX_CYC:
-            raise ValueError("n_cyc = %d: TrainLog takes 1 .. %d cycles" % (n_cyc, _cabi.TRAINLOG_MAX_CYC))
+            raise ValueError("n_cyc = %d: %s takes 1 .. %d cycles" % (n_cyc, type(self).__name__, _cabi.TRAINLOG_MAX_CYC))
         self.enc, self.dec, self.lat_dim, self.stdim, self.n_cyc = model_encoder, model_decoder, int(lat_dim), int(stdim), int(n_cyc)
         self.spk_src, self.half_cyc = spk_src, bool(half_cyc)
         self.gv_src_mean, self.gv_trg_mean = np.asarray(gv_src_mean, np.float64), np.asarray(gv_trg_mean, np.float64)
         self.epoch_idx = self.iter_idx = 0
-        self._prev = self._prev_featfile = self._acc = None
         self._pending, self._lines, self._free = [], [], {}
-        self._fresh = True
-        self.last_lat_srctrg = None            # (kept: the encoder pass of the latest closed utterance batch)
-        self.last_record = None                # (kept: the device record [n_cyc, B, 9] of the latest window)
+        self.last_lat_srctrg = None            # (kept: the latest no-grad encoder pass over batch_src_trg)
+        self.last_record = None                # (kept: the device record [n_cyc, B, 9] of the latest launch)
         self.last_args = None
         self._reset()
 
@@ -127,10 +130,127 @@ class TrainLog(object):
         ev.record()
         return ev
 
+    def _throttle(self, kind):
+        """Wait for the oldest slot while MAX_IN_FLIGHT of `kind` are queued (as the step does)."""
+        while sum(1 for q in self._pending if q[0] == kind) >= self.MAX_IN_FLIGHT:
+            self._pending[0][1].synchronize()
+            self.poll()
+
+    def _traj_ptrs(self, a, trajs, B, T, D, who):
+        """The trajectories of a chain (Stage4Step.last_trajs) into an argument block's traj table; returns what it points to."""
+        if len(trajs) != self.n_cyc:
+            raise ValueError("%s: %d cycles of trajectories, n_cyc = %d" % (who, len(trajs), self.n_cyc))
+        keep = []
+        for i, tr in enumerate(trajs):
+            for k, name in enumerate(_cabi.TRAINLOG_SLOTS):
+                t = tr[name].detach()
+                want = (B, T, 2 * self.lat_dim if name in ("lat", "latcv") else D)
+                if tuple(t.shape) != want or t.dtype != torch.float32:
+                    raise ValueError("trajectory %s of cycle %d has shape %s, expected %s" % (name, i, tuple(t.shape), want))
+                t = t.contiguous()
+                keep.append(t)
+                a.traj[i][k] = t.data_ptr()
+        return keep
+
+    def _align_jobs(self, plan, where, j, cv, lat, feat_trg, lat_par, spc, spc_trg, n, n_trg):
+        """The jobs of one utterance's alignments (:679-688 / :1526-1542): its converted trajectory and own latents gathered at its
+        n speech frames, the parallel utterance's features and latents at their n_trg, two alignments of the conversion (all
+        coefficients; without the power coefficient) and the latent distance."""
+        L, sd, D = self.lat_dim, self.stdim, cv.shape[2]
+        ix = spc.data_ptr() + 8 * j * spc.shape[1]
+        ixp = spc_trg.data_ptr() + 8 * j * spc_trg.shape[1]
+        g = {}
+        for key, t, idx, col, c1, rows in (("trj", cv, ix, 0, D, n), ("feat", feat_trg, ixp, sd, D, n_trg),
+                                           ("par", lat_par, ixp, 0, 2 * L, n_trg), ("own", lat, ix, 0, 2 * L, n)):
+            a, lda = row(t, j, col)
+            g[key] = plan.mat(rows, c1)
+            plan.stat(1, _cabi.STAT_GATHER64, rows, 0, c1, a, lda, idx=idx, dst=g[key], src_rows=t.shape[1])
+        for name, c0 in (("mcdpow", 0), ("mcd", 1)):                                              # :679-680
+            where[(name, j)] = plan.vec()
+            plan.align(g["trj"], g["feat"], -1, None, where[(name, j)], c0=c0)
+        where[("ld", j)] = plan.latent_distance(g["own"], g["par"])                               # :683-688
+
+    # ---- the host half: whatever has arrived, oldest first -----------------------------------------------------------------------
+    def poll(self):
+        """Take the finished slots, oldest first, into the lists and the text lines; stops at the first one still in flight.
+        Returns the number of slots taken."""
+        n = 0
+        while self._pending and self._pending[0][1].query():
+            kind, _, slot, meta = self._pending.pop(0)
+            getattr(self, self._TAKE[kind])(slot.numpy().copy(), meta)
+            self._free.setdefault(slot.numel(), []).append(slot)
+            n += 1
+        return n
+
+    def lines(self):
+        """The text lines that have become available since the last call, in the script's order."""
+        self.poll()
+        out, self._lines = self._lines, []
+        return out
+
+    def _take_close_figures(self, host, W, j, featfile, featfile_trg):
+        """:689-704 / :1535-1560 -- the four figures of one utterance's alignments into the epoch lists, and their line."""
+        ld_a, ld_b, cd_a, cd_b = (float(host[r.off]) for r in W[("ld", j)])
+        vals = (float(host[W[("mcdpow", j)].off]), float(host[W[("mcd", j)].off]), (ld_a + ld_b) / 2, (cd_a + cd_b) / 2)
+        src = self._is_src(featfile)
+        for n, x in zip(CLOSE_SRC if src else CLOSE_TRG, vals):
+            self.lists[n][0].append(x)
+        return ("srctrg" if src else "trgsrc", featfile, featfile_trg) + vals
+
+    # ---- :719-739 ----------------------------------------------------------------------------------------------------------------
+    def epoch_end(self):
+        """Wait for everything in flight; the epoch's figures under the reference's names (n_ev_cyc = 1: the lists of cycle 1) --
+        "loss", the means of the ten loss lists, of the twelve dB lists and of the four latent distances, mcdpowstd_* / mcdstd_* of
+        the two conversions, eval_gv_* -- and "line", the "(EPOCH:%d) average optimization loss" text.  Then the resets of :1202-1269.
+        Lines not yet fetched stay available through lines()."""
+        while self._pending:
+            self._pending[0][1].synchronize()
+            self.poll()
+        l0 = lambda n: self.lists[n][0]
+        s = {"loss": _mean(self.loss)}
+        for n in WIN_SRC + WIN_TRG + DB_SRC + DB_TRG + CLOSE_SRC + CLOSE_TRG:
+            s[n] = _mean(l0(n))
+        for n in ("mcdpow_trg_src", "mcd_trg_src", "mcdpow_src_trg", "mcd_src_trg"):
+            s[n.replace("_", "std_", 1)] = _std(l0(n))
+        for g in GV_SRC + GV_TRG:                                   # a conversion INTO a speaker is held against that speaker's statistics
+            ref = self.gv_trg_mean if g in ("gv_trg_trg", "gv_src_trg", "gv_trg_src_trg") else self.gv_src_mean
+            s["eval_" + g] = float(np.mean(np.sqrt(np.square(np.log(np.mean(l0(g), axis=0)) - np.log(ref))))) if l0(g) else float("nan")
+        text = "%.3f ;; " % s["loss"] + EPOCH_FMT % ((1,) + tuple(s[n] for n in EPOCH_ORDER))
+        line = "(EPOCH:%d) average optimization loss = %s" % (self.epoch_idx + 1, text)
+        if self.total:
+            line += "  (%.3f min., %.3f sec / batch)" % (np.sum(self.total) / 60.0, np.mean(self.total))
+        s["line"] = line
+        self._reset()
+        self.epoch_idx += 1
+        return s
+
+
+class TrainLog(_LogBase):
+    """TrainLog(model_encoder, model_decoder, lat_dim, stdim, gv_src_mean, gv_trg_mean, n_cyc=2, spk_src=None, half_cyc=False), used
+    around an unchanged stage4.Stage4Step:
+
+        tl.before(items, y_in_pp)      # items: one 22-field yield of loader.train_generator (batch_size > 0), or the sentinel
+        loss, state = step(...)
+        tl.after(items, step.last_trajs, loss)
+        for line in tl.lines(): logging.info(line)
+        ...
+        s = tl.epoch_end()             # after before(sentinel): the figures of :722-738 and s["line"], then the resets of :1202-1269
+
+    Neither before() on a window nor after() waits for the device.  Timing fields: after(..., sec=) takes the caller's seconds for
+    the "(%.3f sec)" of :1472 and the "(%.3f min., %.3f sec / batch)" of :739; without it both parentheses are omitted.
+    epoch_idx (0 on construction) numbers the epoch line; set it when resuming."""
+
+    _TAKE = {"win": "_take_window", "close": "_take_close"}
+
+    def __init__(self, model_encoder, model_decoder, lat_dim, stdim, gv_src_mean, gv_trg_mean, n_cyc=2, spk_src=None, half_cyc=False):
+        self._prev = self._prev_featfile = self._acc = None
+        self._fresh = True
+        _LogBase.__init__(self, model_encoder, model_decoder, lat_dim, stdim, gv_src_mean, gv_trg_mean, n_cyc, spk_src, half_cyc)
+
     # ---- before: :660-704 and the GV rule of :1339-1348 --------------------------------------------------------------------------
     def before(self, items, y_in_pp):
         if len(items) == 16:
-            raise NotImplementedError("utterance-length mini-batches (batch_size == 0, train...:1476-1665) are not built: TrainLog takes the "
+            raise NotImplementedError("utterance-length mini-batches (batch_size == 0, train...:1476-1665) are UttLog's: TrainLog takes the "
                                       "22-field yields of loader.train_generator(batch_size > 0)")
         if len(items) != 22:
             raise ValueError("TrainLog.before: a yield of %d fields, expected 22" % len(items))
@@ -179,18 +299,7 @@ class TrainLog(object):
                 lat_par = self.enc(feat_trg, batch_rows(y_in_pp, B), clamp_vae=True, lat_dim=L)[0].contiguous()
             self.last_lat_srctrg = lat_par
         for j in range(n_close):
-            ix = spc.data_ptr() + 8 * j * spc.shape[1]
-            ixp = spc_trg.data_ptr() + 8 * j * spc_trg.shape[1]
-            g = {}
-            for key, t, idx, col, c1, n in (("trj", acc["cv"], ix, 0, D, ns[j]), ("feat", feat_trg, ixp, sd, D, nsp[j]),
-                                            ("par", lat_par, ixp, 0, 2 * L, nsp[j]), ("own", acc["lat"], ix, 0, 2 * L, ns[j])):
-                a, lda = row(t, j, col)
-                g[key] = plan.mat(n, c1)
-                plan.stat(1, _cabi.STAT_GATHER64, n, 0, c1, a, lda, idx=idx, dst=g[key], src_rows=t.shape[1])
-            for n, c0 in (("mcdpow", 0), ("mcd", 1)):                                                 # :679-680
-                where[(n, j)] = plan.vec()
-                plan.align(g["trj"], g["feat"], -1, None, where[(n, j)], c0=c0)
-            where[("ld", j)] = plan.latent_distance(g["own"], g["par"])                               # :683-688
+            self._align_jobs(plan, where, j, acc["cv"], acc["lat"], feat_trg, lat_par, spc, spc_trg, ns[j], nsp[j])
         plan.finalise()
         plan.begin(pinned=True)
         plan.stats(1)
@@ -212,9 +321,7 @@ class TrainLog(object):
         gru_vae._need_cuda(x, "TrainLog.after(batch_src)")
         if len(trajs) != self.n_cyc:
             raise ValueError("TrainLog.after: %d cycles of trajectories, n_cyc = %d" % (len(trajs), self.n_cyc))
-        while sum(1 for q in self._pending if q[0] == "win") >= self.MAX_IN_FLIGHT:                   # as the step does
-            self._pending[0][1].synchronize()
-            self.poll()
+        self._throttle("win")
         B, F, Cin = x.shape
         T, L, sd = e - s + 1, self.lat_dim, self.stdim
         D = Cin - sd
@@ -224,16 +331,7 @@ class TrainLog(object):
         if not 0 <= s <= e < F:
             raise ValueError("TrainLog.after: window %d .. %d outside the %d frames of batch_src" % (s, e, F))
         a = _cabi.TrainlogWindowArgs()
-        keep = []
-        for i, tr in enumerate(trajs):
-            for k, name in enumerate(_cabi.TRAINLOG_SLOTS):
-                t = tr[name].detach()
-                want = (B, T, 2 * L if name in ("lat", "latcv") else D)
-                if tuple(t.shape) != want or t.dtype != torch.float32:
-                    raise ValueError("trajectory %s of cycle %d has shape %s, expected %s" % (name, i, tuple(t.shape), want))
-                t = t.contiguous()
-                keep.append(t)
-                a.traj[i][k] = t.data_ptr()
+        keep = self._traj_ptrs(a, trajs, B, T, D, "TrainLog.after")
         if self._fresh or self._acc is None or self._acc["cv"].shape[:2] != (B, F):                   # :1349-1353
             self._acc = {"rec": torch.zeros(B, F, D, dtype=torch.float32, device=dev), "cv": torch.zeros(B, F, D, dtype=torch.float32, device=dev),
                          "reccyc": torch.zeros(B, F, D, dtype=torch.float32, device=dev), "lat": torch.zeros(B, F, 2 * L, dtype=torch.float32, device=dev)}
@@ -271,24 +369,7 @@ class TrainLog(object):
         self.iter_idx += 1
         self.iter_count += 1
 
-    # ---- the host half: whatever has arrived, oldest first -----------------------------------------------------------------------
-    def poll(self):
-        """Take the finished slots, oldest first, into the lists and the text lines; stops at the first one still in flight.
-        Returns the number of slots taken."""
-        n = 0
-        while self._pending and self._pending[0][1].query():
-            kind, _, slot, meta = self._pending.pop(0)
-            (self._take_window if kind == "win" else self._take_close)(slot.numpy().copy(), meta)
-            self._free.setdefault(slot.numel(), []).append(slot)
-            n += 1
-        return n
-
-    def lines(self):
-        """The text lines that have become available since the last call, in the script's order."""
-        self.poll()
-        out, self._lines = self._lines, []
-        return out
-
+    # ---- the host half -----------------------------------------------------------------------------------------------------------
     def _take_close(self, host, meta):
         W = meta["where"]
         for j in range(meta["gv_rows"]):                                                              # :1341-1348
@@ -296,13 +377,8 @@ class TrainLog(object):
             for n, k in zip(names, ("rec", "cv", "reccyc")):
                 self.lists[n][0].append(W[("gv", k, j)].of(host))
         for j in range(meta["n_close"]):                                                              # :689-704
-            ld_a, ld_b, cd_a, cd_b = (float(host[r.off]) for r in W[("ld", j)])
-            vals = (float(host[W[("mcdpow", j)].off]), float(host[W[("mcd", j)].off]), (ld_a + ld_b) / 2, (cd_a + cd_b) / 2)
-            src = self._is_src(meta["files"][j])
-            for n, x in zip(CLOSE_SRC if src else CLOSE_TRG, vals):
-                self.lists[n][0].append(x)
-            self._lines.append("batch %s loss %s %s = %.3f dB %.3f dB , %.3f %.3f" % (
-                ("srctrg" if src else "trgsrc", meta["files"][j], meta["files_trg"][j]) + vals))
+            self._lines.append("batch %s loss %s %s = %.3f dB %.3f dB , %.3f %.3f" % self._take_close_figures(
+                host, W, j, meta["files"][j], meta["files_trg"][j]))
 
     def _take_window(self, host, meta):
         B, sel, spoken = meta["B"], meta["sel"], meta["spoken"]
@@ -336,29 +412,156 @@ class TrainLog(object):
             self.total.append(float(meta["sec"]))
         self._lines.append(line)
 
-    # ---- :719-739 ----------------------------------------------------------------------------------------------------------------
-    def epoch_end(self):
-        """Wait for everything in flight; the epoch's figures under the reference's names (n_ev_cyc = 1: the lists of cycle 1) --
-        "loss", the means of the ten loss lists, of the twelve dB lists and of the four latent distances, mcdpowstd_* / mcdstd_* of
-        the two conversions, eval_gv_* -- and "line", the "(EPOCH:%d) average optimization loss" text.  Then the resets of :1202-1269.
-        Lines not yet fetched stay available through lines()."""
-        while self._pending:
-            self._pending[0][1].synchronize()
-            self.poll()
-        l0 = lambda n: self.lists[n][0]
-        s = {"loss": _mean(self.loss)}
-        for n in WIN_SRC + WIN_TRG + DB_SRC + DB_TRG + CLOSE_SRC + CLOSE_TRG:
-            s[n] = _mean(l0(n))
-        for n in ("mcdpow_trg_src", "mcd_trg_src", "mcdpow_src_trg", "mcd_src_trg"):
-            s[n.replace("_", "std_", 1)] = _std(l0(n))
-        for g in GV_SRC + GV_TRG:                                   # a conversion INTO a speaker is held against that speaker's statistics
-            ref = self.gv_trg_mean if g in ("gv_trg_trg", "gv_src_trg", "gv_trg_src_trg") else self.gv_src_mean
-            s["eval_" + g] = float(np.mean(np.sqrt(np.square(np.log(np.mean(l0(g), axis=0)) - np.log(ref))))) if l0(g) else float("nan")
-        text = "%.3f ;; " % s["loss"] + EPOCH_FMT % ((1,) + tuple(s[n] for n in EPOCH_ORDER))
-        line = "(EPOCH:%d) average optimization loss = %s" % (self.epoch_idx + 1, text)
-        if self.total:
-            line += "  (%.3f min., %.3f sec / batch)" % (np.sum(self.total) / 60.0, np.mean(self.total))
-        s["line"] = line
-        self._reset()
-        self.epoch_idx += 1
-        return s
+
+
+class UttLog(_LogBase):
+    """UttLog(model_encoder, model_decoder, lat_dim, stdim, gv_src_mean, gv_trg_mean, n_cyc=2, spk_src=None, half_cyc=False): TrainLog's
+    sibling for utterance-length mini-batches (train...:705-706, :1476-1665), around an unchanged stage4.Stage4Step:
+
+        ul.before(items, y_in_pp)      # items: one 16-field yield of loader.train_generator(batch_size=0), or the sentinel
+        loss = step(**stage4.utterance_step_args(items), y_in_enc=..., y_in_dec=..., eps=None)
+        ul.after(items, step.last_trajs, loss)
+        for line in ul.lines(): logging.info(line)
+        ...
+        s = ul.epoch_end()             # after before(sentinel)
+
+    before() runs the no-grad encoder pass of :1489-1490 over batch_src_trg on the current stream, AHEAD of the step, so it reads
+    the weights the script reads; after() launches the step's figures.  Neither waits for the device; after() stalls only with
+    MAX_IN_FLIGHT slots queued.  sec= and epoch_idx as in TrainLog.  The Gaussian posterior only."""
+
+    _TAKE = {"utt": "_take_utt"}
+
+    def __init__(self, model_encoder, model_decoder, lat_dim, stdim, gv_src_mean, gv_trg_mean, n_cyc=2, spk_src=None, half_cyc=False):
+        self._lat_of = None                    # the yield the kept encoder pass belongs to
+        _LogBase.__init__(self, model_encoder, model_decoder, lat_dim, stdim, gv_src_mean, gv_trg_mean, n_cyc, spk_src, half_cyc)
+
+    @staticmethod
+    def _fields(items, who):
+        if len(items) == 22:
+            raise NotImplementedError("%s: a 22-field yield is a frame window (batch_size > 0, train...:1298-1472): that is TrainLog's; "
+                                      "UttLog takes the 16-field yields of loader.train_generator(batch_size=0)" % who)
+        if len(items) != 16:
+            raise ValueError("%s: a yield of %d fields, expected 16" % (who, len(items)))
+
+    # ---- before: :1489-1490 ------------------------------------------------------------------------------------------------------
+    def before(self, items, y_in_pp):
+        self._fields(items, "UttLog.before")
+        if items[5] < 0:                       # the sentinel: nothing but the epoch's end (epoch_end() is the caller's next call)
+            self._lat_of = None
+            return
+        feat_trg = items[3]
+        gru_vae._need_cuda(items[0], "UttLog.before(batch_src)")
+        gru_vae._need_cuda(feat_trg, "UttLog.before(batch_src_trg)")
+        B = feat_trg.shape[0]
+        with torch.no_grad():                  # (on the current stream, ahead of the step: the pre-update weights)
+            self.last_lat_srctrg = self.enc(feat_trg.to(torch.float32).contiguous(), batch_rows(y_in_pp, B), clamp_vae=True,
+                                            lat_dim=self.lat_dim)[0].contiguous()
+        self._lat_of = items
+
+    # ---- after: one window launch, one plan, one copy ----------------------------------------------------------------------------
+    def after(self, items, trajs, loss, sec=None):
+        """The figures of the step on `items` from the trajectories of its chain (Stage4Step.last_trajs) and its 0-dim loss tensor:
+        cvae_trainlog_window over the whole padded utterances, a MetricPlan on the cycle-0 trajectories and before()'s encoder
+        pass, and the copy of [record | plan results | loss] behind an event.  sec: the caller's seconds for this step."""
+        self._fields(items, "UttLog.after")
+        if items[5] < 0:
+            raise ValueError("UttLog.after: not an utterance batch's yield")
+        x, feat_trg, spc, spc_trg = items[0], items[3], items[7], items[8]
+        gru_vae._need_cuda(x, "UttLog.after(batch_src)")
+        if self._lat_of is not items:
+            raise ValueError("UttLog.after: before() has not been given this yield")
+        self._throttle("utt")
+        B, T, Cin = x.shape
+        L, sd = self.lat_dim, self.stdim
+        D = Cin - sd
+        dev = x.device
+        if x.dtype != torch.float32 or not x.is_contiguous():
+            raise ValueError("UttLog.after: batch_src must be a contiguous float32 tensor")
+        if int(items[15]) != B:
+            raise ValueError("UttLog.after: n_batch_utt = %d, batch_src holds %d utterances" % (int(items[15]), B))
+        a = _cabi.TrainlogWindowArgs()
+        keep = self._traj_ptrs(a, trajs, B, T, D, "UttLog.after")
+        if spc.dtype != torch.int64 or not spc.is_contiguous() or spc.shape[0] != B:
+            raise ValueError("UttLog.after: spcidx_src must be a contiguous int64 tensor of %d rows" % B)
+        flens, ns, nsp = ints(items[11]), ints(items[13]), ints(items[14])
+        if not (len(flens) == len(ns) == len(nsp) == len(items[9]) == len(items[10]) == B):
+            raise ValueError("UttLog.after: the generator's bookkeeping does not hold %d utterances" % B)
+        lat_par = self.last_lat_srctrg
+        feat_trg = feat_trg.to(torch.float32).contiguous()
+        spc_trg = spc_trg.to(device=dev, dtype=torch.int64).contiguous()
+        if feat_trg.shape[0] != B or spc_trg.shape[0] != B or feat_trg.shape[2] != Cin or tuple(lat_par.shape[:2]) != tuple(feat_trg.shape[:2]):
+            raise ValueError("UttLog.after: batch_src_trg / spcidx_src_trg do not hold %d utterances of %d features" % (B, Cin))
+        for j in range(B):
+            if not 1 <= flens[j] <= T:
+                raise ValueError("flens_src[%d] = %d does not fit the %d padded frames" % (j, flens[j], T))
+            if not (1 <= ns[j] <= spc.shape[1] and 1 <= nsp[j] <= spc_trg.shape[1]):
+                raise ValueError("flens_spc of utterance %d (%d, %d) do not fit the speech-frame index rows" % (j, ns[j], nsp[j]))
+        # the window launch: the whole utterance is the window (:1567-1582)
+        host = [np.ascontiguousarray(flens, np.int32), np.zeros(B, np.int32), np.ascontiguousarray(ns, np.int32) - 1, np.ones(B, np.uint8)]
+        # the plan on cycle 0: :1516-1524 (GV), :1526-1545 (alignments)
+        plan = MetricPlan(dev)
+        plan.hold((keep, feat_trg, spc, spc_trg, lat_par))
+        tr0 = {name: keep[k] for k, name in enumerate(_cabi.TRAINLOG_SLOTS)}
+        where = {}
+        for j in range(B):
+            for k in ("rec", "cv", "reccyc"):
+                at, lda = row(tr0[k], j)
+                where[("gv", k, j)] = plan.vec(D - 1)
+                plan.stat(1, _cabi.STAT_GV, flens[j], 1, D, at, lda, out=where[("gv", k, j)])
+        for j in range(B):
+            self._align_jobs(plan, where, j, tr0["cv"], tr0["lat"], feat_trg, lat_par, spc, spc_trg, ns[j], nsp[j])
+        plan.finalise()
+        n, n_out = self.n_cyc * B * _cabi.TRAINLOG_REC, max(1, plan.n_out)
+        out = torch.empty(n + n_out + 1, dtype=torch.float64, device=dev)        # [record | plan results | loss]: ONE copy to the host
+        a.x_win, a.x_row_stride, a.x_utt_stride = x.data_ptr(), Cin, T * Cin
+        a.spcidx, a.spc_ld = spc.data_ptr(), spc.shape[1]
+        a.flen_acc, a.s_idx, a.e_idx, a.selected = (h.ctypes.data for h in host)
+        a.n_cyc, a.B, a.T, a.D, a.L, a.stdim, a.src_idx_s, a.acc_rows = self.n_cyc, B, T, D, L, sd, 0, 0
+        a.rec_out = out.data_ptr()
+        gru_vae._lib().trainlog_window(a, gru_vae._stream())
+        self.last_args = (a, keep, host)
+        self.last_record = out[:n].view(self.n_cyc, B, _cabi.TRAINLOG_REC)
+        plan.begin(pinned=True)
+        plan.stats(1)
+        plan.dtw()
+        plan.stats(2)
+        out[n:n + n_out].copy_(plan.results())
+        out[n + n_out:].copy_(loss.detach().reshape(1))
+        slot = self._pinned(out.numel())
+        ev = self._behind(out, slot)
+        meta = dict(B=B, n=n, where=where, files=list(items[9]), files_trg=list(items[10]), flens=flens, flens_trg=ints(items[12]), ns=ns, nsp=nsp,
+                    c_idx=int(items[5]), sec=sec, keep=(plan, out))
+        self._pending.append(("utt", ev, slot, meta))
+        self._lat_of = None
+        self.iter_idx += 1
+        self.iter_count += 1
+
+    # ---- the host half -----------------------------------------------------------------------------------------------------------
+    def _take_utt(self, host, meta):
+        B, n, W, files, files_trg = meta["B"], meta["n"], meta["where"], meta["files"], meta["files_trg"]
+        R = host[:n].reshape(self.n_cyc, B, _cabi.TRAINLOG_REC)
+        res, loss = host[n:-1], float(host[-1])
+        for j in range(B):                                                                            # :1478
+            self._lines.append("%s %s %d %d %d %d" % (files[j], files_trg[j], meta["flens"][j], meta["flens_trg"][j], meta["ns"][j], meta["nsp"][j]))
+        for j in range(B):
+            for name, k in zip(GV_SRC if self._is_src(files[j]) else GV_TRG, ("rec", "cv", "reccyc")):  # :1517-1524
+                self.lists[name][0].append(W[("gv", k, j)].of(res))
+            self._lines.append("batch %s loss %s %s = %.3f dB %.3f dB , %.3f %.3f " % self._take_close_figures(      # :1547-1560
+                res, W, j, files[j], files_trg[j]))
+        for i in range(self.n_cyc):                                                                   # :1599-1622
+            for j in range(B):
+                src = self._is_src(files[j])
+                for name, q in zip(WIN_SRC if src else WIN_TRG, range(5)):
+                    self.lists[name][i].append(float(R[i, j, q]))
+                for name, q in zip(DB_SRC if src else DB_TRG, (5, 6, 7, 8)):
+                    self.lists[name][i].append(float(R[i, j, q]))
+        self.loss.append(loss)                                                                        # :1655
+        text = "%.3f ;; " % loss                                                                      # :1657-1662: means over every utterance
+        for i in range(self.n_cyc):
+            text += "[%d] %.3f %.3f %.3f ; %.3f %.3f ; %.3f dB %.3f dB , %.3f dB %.3f dB;; " % (
+                (i + 1,) + tuple(float(np.mean(R[i, :, q])) for q in range(9)))
+        line = "batch loss [%d] = %s" % (meta["c_idx"] + 1, text)                                     # :1663
+        if meta["sec"] is not None:
+            line += "  (%.3f sec)" % meta["sec"]
+            self.total.append(float(meta["sec"]))
+        self._lines.append(line)
