@@ -18,7 +18,7 @@ FLAG_EXACT3 = 512
 STATUS_RANGE = 7        # CVAE_STATUS_RANGE: an operand of a limb-operand eval kernel was outside the window of its fp16 limbs (ABI 8)
 STATUS_RANGE_WORD = 3   # the status word that carries it (word 0: time-outs, status 5)
 CLAMP_LAPLACE = 1 << 30     # OR into a clamp_lat_dim argument: clamp_vae_laplace's floor (gru_vae.py:417) instead of ln(1e-6)
-DRAW_LAPLACE = 1 << 30      # OR into a lat_dim argument (pass_input, cycle_forward*, latent_mean, sample_cat*, stage4_loss): the Laplace
+DRAW_LAPLACE = 1 << 30      # OR into a lat_dim argument (pass_input, cycle_forward*, latent_mean, sample_cat*, stage4_loss, trainlog_window's L): the Laplace
                             # posterior -- z = mu + exp(s) * u(eps), loss_vae_laplace's KL (gru_vae.py:101-112, :130-139)
 POSTERIORS = ("gauss", "laplace")
 
@@ -103,6 +103,7 @@ class DtwProblem(C.Structure):
 
 STAT_GV, STAT_MCD_SPC, STAT_MCD_L1, STAT_KL, STAT_GATHER64, STAT_LATDIST = range(6)      # cvae_stat_job.kind
 STAT_MEANSTD64, STAT_MCD64 = 6, 7       # stage 5: (np.mean, np.std) of an f64 vector / of the frame-wise mel-cd of two f64 matrices
+STAT_KL_LAPLACE = 8                     # STAT_KL's operands, loss_vae_laplace's KL (the Laplace posterior's loss_lat_* figures)
 
 
 class StatJob(C.Structure):

@@ -17,6 +17,7 @@ struct TlwParams {
     float* acc[4];                   // rows of utterance j0 on; NULL: no copy
     double* out;                     // rec[0][j0][0]
     int B, nb, T, D, L, stdim, s0, acc_rows;      // B: utterances of the trajectories' row stride; nb: of this launch
+    int laplace;                     // non-zero: entries [3], [4] are loss_vae_laplace's KL (the caller's L | CVAE_DRAW_LAPLACE)
     int flen_acc[CVAE_TRAINLOG_MAX_UTT], s_idx[CVAE_TRAINLOG_MAX_UTT], e_idx[CVAE_TRAINLOG_MAX_UTT];
     unsigned char sel[CVAE_TRAINLOG_MAX_UTT];
 };
@@ -91,21 +92,32 @@ __global__ __launch_bounds__(TLW_THREADS) void k_trainlog_window(const TlwParams
             v[1] += fabs((double)cyc[e] - y);
             v[2] += fabs((double)cv[e] - y);
         }
-        for (long e = tid; e < (long)n * L; e += TLW_THREADS) {
-            const long t = e / L, at = t * 2 * L + (e - t * L);
-            const double mu = (double)lat[at], sg = (double)lat[at + L];
-            const double mu2 = (double)latcv[at], sg2 = (double)latcv[at + L];
-            v[3] += exp(sg) + mu * mu - sg - 1.0;
-            v[4] += exp(sg2) + mu2 * mu2 - sg2 - 1.0;
+        if (p.laplace) {      // loss_vae_laplace (gru_vae.py:130-139): sum_l (-s + b exp(-|mu|/b) + |mu| - 1), b = exp(s)
+            for (long e = tid; e < (long)n * L; e += TLW_THREADS) {
+                const long t = e / L, at = t * 2 * L + (e - t * L);
+                const double ma = fabs((double)lat[at]), sg = (double)lat[at + L];
+                const double ma2 = fabs((double)latcv[at]), sg2 = (double)latcv[at + L];
+                const double b = exp(sg), b2 = exp(sg2);
+                v[3] += -sg + b * exp(-ma / b) + ma - 1.0;
+                v[4] += -sg2 + b2 * exp(-ma2 / b2) + ma2 - 1.0;
+            }
+        } else {
+            for (long e = tid; e < (long)n * L; e += TLW_THREADS) {
+                const long t = e / L, at = t * 2 * L + (e - t * L);
+                const double mu = (double)lat[at], sg = (double)lat[at + L];
+                const double mu2 = (double)latcv[at], sg2 = (double)latcv[at + L];
+                v[3] += exp(sg) + mu * mu - sg - 1.0;
+                v[4] += exp(sg2) + mu2 * mu2 - sg2 - 1.0;
+            }
         }
         block_sums256<5>(v, red);
         if (tid == 0) {
-            const double km = K * 1.4142135623730950488016887242097 / (double)n;
+            const double km = K * 1.4142135623730950488016887242097 / (double)n, kk = p.laplace ? 1.0 : 0.5;
             o[0] = km * v[0];
             o[1] = km * v[1];
             o[2] = km * v[2];
-            o[3] = 0.5 * v[3] / (double)n;
-            o[4] = 0.5 * v[4] / (double)n;
+            o[3] = kk * v[3] / (double)n;
+            o[4] = kk * v[4] / (double)n;
         }
     } else if (tid == 0) {
         o[0] = o[1] = o[2] = o[3] = o[4] = NaN;
@@ -182,9 +194,12 @@ int cvae_trainlog_window(cvae_ctx* ctx, const cvae_trainlog_window_args* a, void
     CVAE_ENTER(ctx);
     if (!a || !a->x_win || !a->spcidx || !a->flen_acc || !a->s_idx || !a->e_idx || !a->selected || !a->rec_out)
         return fail(-1, "cvae_trainlog_window: bad argument");
-    if (a->n_cyc < 1 || a->n_cyc > CVAE_TRAINLOG_MAX_CYC || a->B < 1 || a->T < 1 || a->D < 1 || a->L < 1 || a->stdim < 0 || a->spc_ld < 1 ||
+    // L, or L | CVAE_DRAW_LAPLACE: the flag is taken off before anything is checked or addressed with it
+    const int L = draw_dim(a->L);
+    const bool laplace = draw_laplace(a->L);
+    if (a->n_cyc < 1 || a->n_cyc > CVAE_TRAINLOG_MAX_CYC || a->B < 1 || a->T < 1 || a->D < 1 || L < 1 || a->stdim < 0 || a->spc_ld < 1 ||
         a->x_row_stride < (int64_t)a->stdim + a->D)
-        return fail(-1, "cvae_trainlog_window: bad shape (n_cyc=%d B=%d T=%d D=%d L=%d stdim=%d)", a->n_cyc, a->B, a->T, a->D, a->L, a->stdim);
+        return fail(-1, "cvae_trainlog_window: bad shape (n_cyc=%d B=%d T=%d D=%d L=%d stdim=%d)", a->n_cyc, a->B, a->T, a->D, L, a->stdim);
     for (int i = 0; i < a->n_cyc; ++i)
         for (int k = 0; k < 5; ++k)
             if (!a->traj[i][k]) return fail(-1, "cvae_trainlog_window: trajectory %d of cycle %d is NULL", k, i);
@@ -198,19 +213,20 @@ int cvae_trainlog_window(cvae_ctx* ctx, const cvae_trainlog_window_args* a, void
         const int nb = a->B - j0 < CVAE_TRAINLOG_MAX_UTT ? a->B - j0 : CVAE_TRAINLOG_MAX_UTT;
         memset(&p, 0, sizeof(p));
         for (int i = 0; i < a->n_cyc; ++i)
-            for (int k = 0; k < 5; ++k) p.traj[i][k] = a->traj[i][k] + (size_t)j0 * a->T * (k == 0 || k == 3 ? 2 * a->L : a->D);
+            for (int k = 0; k < 5; ++k) p.traj[i][k] = a->traj[i][k] + (size_t)j0 * a->T * (k == 0 || k == 3 ? 2 * L : a->D);
         p.x = a->x_win + (size_t)j0 * a->x_utt_stride;
         p.ldx = a->x_row_stride;
         p.sx = a->x_utt_stride;
         p.spc = (const long long*)a->spcidx + (size_t)j0 * a->spc_ld;
         p.spc_ld = a->spc_ld;
-        for (int q = 0; q < 4; ++q) p.acc[q] = copy ? a->acc[q] + (size_t)j0 * a->acc_rows * (q == 3 ? 2 * a->L : a->D) : nullptr;
+        for (int q = 0; q < 4; ++q) p.acc[q] = copy ? a->acc[q] + (size_t)j0 * a->acc_rows * (q == 3 ? 2 * L : a->D) : nullptr;
         p.out = a->rec_out + (size_t)j0 * 9;
         p.B = a->B;
         p.nb = nb;
         p.T = a->T;
         p.D = a->D;
-        p.L = a->L;
+        p.L = L;
+        p.laplace = laplace ? 1 : 0;
         p.stdim = a->stdim;
         p.s0 = a->src_idx_s;
         p.acc_rows = a->acc_rows;

@@ -239,6 +239,21 @@ __global__ __launch_bounds__(256) void k_eval_stats(const cvae_stat_job* jobs, d
         }
         const double tot = block_sum256(acc, red);
         if (tid == 0) o[0] = tot / (double)rows;
+    } else if (kind == CVAE_STAT_KL_LAPLACE) {
+        // loss_vae_laplace (gru_vae.py:130-139) in CVAE_STAT_KL's summation order: a[t] = [mu | log-scale], b = exp(s)
+        const float* a = (const float*)jb.a;
+        double acc = 0.0;
+        for (int t = tid; t < rows; t += 256) {
+            double s = 0.0;
+            for (int l = 0; l < c1; ++l) {
+                const double ma = fabs((double)a[(long)t * lda + l]), sg = (double)a[(long)t * lda + c1 + l];
+                const double b = exp(sg);
+                s += -sg + b * exp(-ma / b) + ma - 1.0;
+            }
+            acc += s;
+        }
+        const double tot = block_sum256(acc, red);
+        if (tid == 0) o[0] = tot / (double)rows;
     } else if (kind == CVAE_STAT_GATHER64) {
         const float* a = (const float*)jb.a;
         const int w = c1 - c0;

@@ -48,13 +48,16 @@ PROFILE_PARTS = ("stats", "dtw", "mc2e_1", "mc2e_2", "modpow")
 
 class DecodePass(object):
     """DecodePass(model_encoder, model_decoder, lat_dim, gv_mean_src, gv_mean_trg, cvgv_mean, cvgvsrc_mean, cvgvtrg_mean,
-    n_smpl_dec=300, mcep_alpha=0.455, irlen=1024): call pairs() on the evaluation pairs, ten at a time at most, then summary() /
-    log_lines().  gv_mean_*: "/gv_range_mean"[1:] of the two speakers (:186-187); cvgv*_mean: the three vectors of :205-210, which
-    stage5.CvgvPass.write produces."""
+    n_smpl_dec=300, mcep_alpha=0.455, irlen=1024, posterior="gauss"): call pairs() on the evaluation pairs, ten at a time at most,
+    then summary() / log_lines().  gv_mean_*: "/gv_range_mean"[1:] of the two speakers (:186-187); cvgv*_mean: the three vectors of
+    :205-210, which stage5.CvgvPass.write produces.  posterior: handed to the stage5.CvgvPass that runs the network half ("laplace":
+    the Laplace clamp and draws); it has to be the posterior the model was trained with, which cannot be detected here."""
 
     def __init__(self, model_encoder, model_decoder, lat_dim, gv_mean_src, gv_mean_trg, cvgv_mean, cvgvsrc_mean, cvgvtrg_mean,
-                 n_smpl_dec=300, mcep_alpha=0.455, irlen=1024):
-        self.net = stage5.CvgvPass(model_encoder, model_decoder, lat_dim, gv_mean_src, gv_mean_trg, n_smpl_dec=n_smpl_dec)
+                 n_smpl_dec=300, mcep_alpha=0.455, irlen=1024, posterior="gauss"):
+        self.net = stage5.CvgvPass(model_encoder, model_decoder, lat_dim, gv_mean_src, gv_mean_trg, n_smpl_dec=n_smpl_dec,
+                                   posterior=posterior)
+        self.posterior = posterior
         self.enc, self.dec, self.lat_dim, self.n_smpl_dec = model_encoder, model_decoder, int(lat_dim), int(n_smpl_dec)
         self.D = int(model_decoder.out_dim)
         self.mcep_alpha, self.irlen = float(mcep_alpha), int(irlen)

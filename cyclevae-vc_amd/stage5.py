@@ -96,10 +96,16 @@ def pair_figures(host, o, mcd_terms, calc_mcd):
 
 
 class CvgvPass(object):
-    """CvgvPass(model_encoder, model_decoder, lat_dim, gv_mean_src, gv_mean_trg, n_smpl_dec=300): call pairs() on the training
-    pairs, ten at a time at most, then summary() / log_lines() / write()."""
+    """CvgvPass(model_encoder, model_decoder, lat_dim, gv_mean_src, gv_mean_trg, n_smpl_dec=300, posterior="gauss"): call pairs() on
+    the training pairs, ten at a time at most, then summary() / log_lines() / write().
+    posterior="laplace": the Laplace posterior of the sibling recipes, as stage6.convert_pairs(posterior="laplace") runs it -- the
+    encoder passes clamp as clamp_vae_laplace does and lat_feat is the mean over n_smpl_dec draws of sampling_vae_laplace(lat)
+    (cvae_latent_mean with lat_dim | CVAE_DRAW_LAPLACE; supplied eps are its uniforms in (-0.4999, 0.5)).  It has to be the posterior
+    the model was trained with: a disagreement cannot be detected here and is the caller's mistake."""
 
-    def __init__(self, model_encoder, model_decoder, lat_dim, gv_mean_src, gv_mean_trg, n_smpl_dec=300):
+    def __init__(self, model_encoder, model_decoder, lat_dim, gv_mean_src, gv_mean_trg, n_smpl_dec=300, posterior="gauss"):
+        _cabi.posterior_flags(posterior, 0)      # (ValueError for anything but "gauss" / "laplace")
+        self.posterior = posterior
         self.enc, self.dec, self.lat_dim, self.n_smpl_dec = model_encoder, model_decoder, int(lat_dim), int(n_smpl_dec)
         if self.lat_dim < 1 or self.n_smpl_dec < 1:
             raise ValueError("lat_dim and n_smpl_dec must be >= 1, got %d and %d" % (self.lat_dim, self.n_smpl_dec))
@@ -138,7 +144,7 @@ class CvgvPass(object):
         mark = (lambda k: ev[k].record()) if ev else (lambda k: None)
         mark(0)
         with torch.no_grad():
-            enc = stage6._encode_pairs(self.enc, feats + feats[:pad_enc], y_in_pp, L)
+            enc = stage6._encode_pairs(self.enc, feats + feats[:pad_enc], y_in_pp, L, self.posterior)
         lens, T, lat, dev = enc["lens"][:N], enc["T"], enc["lat"], enc["dev"]
         mark(1)
         # :180-184 -- all 2N means in one launch; rows behind a cell's frames stay zero and are never read
@@ -155,7 +161,7 @@ class CvgvPass(object):
                 r = 2 * q + side
                 jobs.append(_cabi.LatMeanJob(lat[r].data_ptr(), None if e is None else e.data_ptr(), 2 * n * (first + q) + side * n, frames, 0,
                                              latfeat[r].data_ptr()))
-        lib.latent_mean(jobs, L, n, 0 if seed is None else int(seed), st)
+        lib.latent_mean(jobs, _cabi.posterior_flags(self.posterior, L)[0], n, 0 if seed is None else int(seed), st)
         mark(2)
         # :185-199 -- [code ; lat_feat] through the decoder: cvmcep and cvmcep_src share lat_feat, cvmcep_trg reads lat_feat_trg
         Co = dec.out_dim

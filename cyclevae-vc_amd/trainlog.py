@@ -90,7 +90,13 @@ class _LogBase(object):
     MAX_IN_FLIGHT = stage4.Stage4Step.MAX_IN_FLIGHT
     _TAKE = {}
 
-    def __init__(self, model_encoder, model_decoder, lat_dim, stdim, gv_src_mean, gv_trg_mean, n_cyc=2, spk_src=None, half_cyc=False):
+    def __init__(self, model_encoder, model_decoder, lat_dim, stdim, gv_src_mean, gv_trg_mean, n_cyc=2, spk_src=None, half_cyc=False,
+                 posterior="gauss"):
+        self._laplace = stage4._check_posterior(posterior)      # (ValueError for anything but "gauss" / "laplace")
+        self.posterior = posterior
+        # the window launch's L (the flag makes record entries [3], [4] loss_vae_laplace's KL) and the log's own encoder passes' clamp
+        self._win_L = _cabi.posterior_flags(posterior, int(lat_dim))[0]
+        self._clamp_kw = {"clamp_vae_laplace": True} if self._laplace else {"clamp_vae": True}
         if not 1 <= int(n_cyc) <= _cabi.TRAINLOG_MAX_CYC:
             raise ValueError("n_cyc = %d: %s takes 1 .. %d cycles" % (n_cyc, type(self).__name__, _cabi.TRAINLOG_MAX_CYC))
         self.enc, self.dec, self.lat_dim, self.stdim, self.n_cyc = model_encoder, model_decoder, int(lat_dim), int(stdim), int(n_cyc)
@@ -226,8 +232,8 @@ class _LogBase(object):
 
 
 class TrainLog(_LogBase):
-    """TrainLog(model_encoder, model_decoder, lat_dim, stdim, gv_src_mean, gv_trg_mean, n_cyc=2, spk_src=None, half_cyc=False), used
-    around an unchanged stage4.Stage4Step:
+    """TrainLog(model_encoder, model_decoder, lat_dim, stdim, gv_src_mean, gv_trg_mean, n_cyc=2, spk_src=None, half_cyc=False,
+    posterior="gauss"), used around an unchanged stage4.Stage4Step:
 
         tl.before(items, y_in_pp)      # items: one 22-field yield of loader.train_generator (batch_size > 0), or the sentinel
         loss, state = step(...)
@@ -238,14 +244,19 @@ class TrainLog(_LogBase):
 
     Neither before() on a window nor after() waits for the device.  Timing fields: after(..., sec=) takes the caller's seconds for
     the "(%.3f sec)" of :1472 and the "(%.3f min., %.3f sec / batch)" of :739; without it both parentheses are omitted.
-    epoch_idx (0 on construction) numbers the epoch line; set it when resuming."""
+    epoch_idx (0 on construction) numbers the epoch line; set it when resuming.
+    posterior="laplace", around a Stage4Step(posterior="laplace"): the window launch carries _cabi.DRAW_LAPLACE, so the two KL
+    figures of a record are loss_vae_laplace's and the logged terms sum to that step's loss, and the log's own encoder pass
+    (_close) clamps as clamp_vae_laplace does; the texts are unchanged.  A posterior that disagrees with the step's cannot be
+    detected here and is the caller's mistake."""
 
     _TAKE = {"win": "_take_window", "close": "_take_close"}
 
-    def __init__(self, model_encoder, model_decoder, lat_dim, stdim, gv_src_mean, gv_trg_mean, n_cyc=2, spk_src=None, half_cyc=False):
+    def __init__(self, model_encoder, model_decoder, lat_dim, stdim, gv_src_mean, gv_trg_mean, n_cyc=2, spk_src=None, half_cyc=False,
+                 posterior="gauss"):
         self._prev = self._prev_featfile = self._acc = None
         self._fresh = True
-        _LogBase.__init__(self, model_encoder, model_decoder, lat_dim, stdim, gv_src_mean, gv_trg_mean, n_cyc, spk_src, half_cyc)
+        _LogBase.__init__(self, model_encoder, model_decoder, lat_dim, stdim, gv_src_mean, gv_trg_mean, n_cyc, spk_src, half_cyc, posterior)
 
     # ---- before: :660-704 and the GV rule of :1339-1348 --------------------------------------------------------------------------
     def before(self, items, y_in_pp):
@@ -296,7 +307,7 @@ class TrainLog(_LogBase):
                 if not (1 <= ns[j] <= spc.shape[1] and 1 <= nsp[j] <= spc_trg.shape[1]):
                     raise ValueError("flens_spc of utterance %d (%d, %d) do not fit the speech-frame index rows" % (j, ns[j], nsp[j]))
             with torch.no_grad():                                                                     # :673-677
-                lat_par = self.enc(feat_trg, batch_rows(y_in_pp, B), clamp_vae=True, lat_dim=L)[0].contiguous()
+                lat_par = self.enc(feat_trg, batch_rows(y_in_pp, B), lat_dim=L, **self._clamp_kw)[0].contiguous()
             self.last_lat_srctrg = lat_par
         for j in range(n_close):
             self._align_jobs(plan, where, j, acc["cv"], acc["lat"], feat_trg, lat_par, spc, spc_trg, ns[j], nsp[j])
@@ -350,7 +361,7 @@ class TrainLog(_LogBase):
         a.x_win, a.x_row_stride, a.x_utt_stride = x.data_ptr() + 4 * s * Cin, Cin, F * Cin
         a.spcidx, a.spc_ld = spc.data_ptr(), spc.shape[1]
         a.flen_acc, a.s_idx, a.e_idx, a.selected = (h.ctypes.data for h in host)
-        a.n_cyc, a.B, a.T, a.D, a.L, a.stdim, a.src_idx_s, a.acc_rows = self.n_cyc, B, T, D, L, sd, s, F
+        a.n_cyc, a.B, a.T, a.D, a.L, a.stdim, a.src_idx_s, a.acc_rows = self.n_cyc, B, T, D, self._win_L, sd, s, F
         for q, k in enumerate(("rec", "cv", "reccyc", "lat")):
             a.acc[q] = self._acc[k].data_ptr()
         a.rec_out = rec.data_ptr()
@@ -415,8 +426,9 @@ class TrainLog(_LogBase):
 
 
 class UttLog(_LogBase):
-    """UttLog(model_encoder, model_decoder, lat_dim, stdim, gv_src_mean, gv_trg_mean, n_cyc=2, spk_src=None, half_cyc=False): TrainLog's
-    sibling for utterance-length mini-batches (train...:705-706, :1476-1665), around an unchanged stage4.Stage4Step:
+    """UttLog(model_encoder, model_decoder, lat_dim, stdim, gv_src_mean, gv_trg_mean, n_cyc=2, spk_src=None, half_cyc=False,
+    posterior="gauss"): TrainLog's sibling for utterance-length mini-batches (train...:705-706, :1476-1665), around an unchanged
+    stage4.Stage4Step:
 
         ul.before(items, y_in_pp)      # items: one 16-field yield of loader.train_generator(batch_size=0), or the sentinel
         loss = step(**stage4.utterance_step_args(items), y_in_enc=..., y_in_dec=..., eps=None)
@@ -427,13 +439,15 @@ class UttLog(_LogBase):
 
     before() runs the no-grad encoder pass of :1489-1490 over batch_src_trg on the current stream, AHEAD of the step, so it reads
     the weights the script reads; after() launches the step's figures.  Neither waits for the device; after() stalls only with
-    MAX_IN_FLIGHT slots queued.  sec= and epoch_idx as in TrainLog.  The Gaussian posterior only."""
+    MAX_IN_FLIGHT slots queued.  sec= and epoch_idx as in TrainLog.  posterior as in TrainLog: "laplace" puts the flag on the
+    window launch and the Laplace clamp on before()'s encoder pass; it must be the step's posterior, which cannot be detected here."""
 
     _TAKE = {"utt": "_take_utt"}
 
-    def __init__(self, model_encoder, model_decoder, lat_dim, stdim, gv_src_mean, gv_trg_mean, n_cyc=2, spk_src=None, half_cyc=False):
+    def __init__(self, model_encoder, model_decoder, lat_dim, stdim, gv_src_mean, gv_trg_mean, n_cyc=2, spk_src=None, half_cyc=False,
+                 posterior="gauss"):
         self._lat_of = None                    # the yield the kept encoder pass belongs to
-        _LogBase.__init__(self, model_encoder, model_decoder, lat_dim, stdim, gv_src_mean, gv_trg_mean, n_cyc, spk_src, half_cyc)
+        _LogBase.__init__(self, model_encoder, model_decoder, lat_dim, stdim, gv_src_mean, gv_trg_mean, n_cyc, spk_src, half_cyc, posterior)
 
     @staticmethod
     def _fields(items, who):
@@ -454,8 +468,8 @@ class UttLog(_LogBase):
         gru_vae._need_cuda(feat_trg, "UttLog.before(batch_src_trg)")
         B = feat_trg.shape[0]
         with torch.no_grad():                  # (on the current stream, ahead of the step: the pre-update weights)
-            self.last_lat_srctrg = self.enc(feat_trg.to(torch.float32).contiguous(), batch_rows(y_in_pp, B), clamp_vae=True,
-                                            lat_dim=self.lat_dim)[0].contiguous()
+            self.last_lat_srctrg = self.enc(feat_trg.to(torch.float32).contiguous(), batch_rows(y_in_pp, B), lat_dim=self.lat_dim,
+                                            **self._clamp_kw)[0].contiguous()
         self._lat_of = items
 
     # ---- after: one window launch, one plan, one copy ----------------------------------------------------------------------------
@@ -516,7 +530,7 @@ class UttLog(_LogBase):
         a.x_win, a.x_row_stride, a.x_utt_stride = x.data_ptr(), Cin, T * Cin
         a.spcidx, a.spc_ld = spc.data_ptr(), spc.shape[1]
         a.flen_acc, a.s_idx, a.e_idx, a.selected = (h.ctypes.data for h in host)
-        a.n_cyc, a.B, a.T, a.D, a.L, a.stdim, a.src_idx_s, a.acc_rows = self.n_cyc, B, T, D, L, sd, 0, 0
+        a.n_cyc, a.B, a.T, a.D, a.L, a.stdim, a.src_idx_s, a.acc_rows = self.n_cyc, B, T, D, self._win_L, sd, 0, 0
         a.rec_out = out.data_ptr()
         gru_vae._lib().trainlog_window(a, gru_vae._stream())
         self.last_args = (a, keep, host)

@@ -16,6 +16,7 @@ import torch
 
 import _cabi
 import gru_vae
+import stage4
 from metricplan import MetricPlan, batch_rows, ints, row
 
 N_EV_CYC = 1      # train...:604
@@ -45,10 +46,16 @@ def _side(items):
 
 
 class ValidationPass(object):
-    """ValidationPass(model_encoder, model_decoder, lat_dim, stdim, gv_src_mean, gv_trg_mean, half_cyc=False): call batch() on
-    every pair of yields of the two evaluation generators, then summary(); better() is the checkpoint decision."""
+    """ValidationPass(model_encoder, model_decoder, lat_dim, stdim, gv_src_mean, gv_trg_mean, half_cyc=False, posterior="gauss"):
+    call batch() on every pair of yields of the two evaluation generators, then summary(); better() is the checkpoint decision.
+    posterior="laplace": the Laplace posterior of the sibling recipes (reference gru_vae.py:101-112, :130-139, :415-417) -- the six
+    encoder passes clamp as clamp_vae_laplace does, the draws are sampling_vae_laplace's (injected eps are then its uniforms in
+    (-0.4999, 0.5)) and the four loss_lat_* figures are loss_vae_laplace's KL (CVAE_STAT_KL_LAPLACE).  It has to be the posterior the
+    model was trained with (stage4.Stage4Step(posterior=)): a disagreement cannot be detected here and is the caller's mistake."""
 
-    def __init__(self, model_encoder, model_decoder, lat_dim, stdim, gv_src_mean, gv_trg_mean, half_cyc=False):
+    def __init__(self, model_encoder, model_decoder, lat_dim, stdim, gv_src_mean, gv_trg_mean, half_cyc=False, posterior="gauss"):
+        self._laplace = stage4._check_posterior(posterior)      # (ValueError for anything but "gauss" / "laplace")
+        self.posterior = posterior
         self.enc, self.dec, self.lat_dim, self.stdim, self.half_cyc = model_encoder, model_decoder, int(lat_dim), int(stdim), bool(half_cyc)
         self.gv_src_mean = np.asarray(gv_src_mean, np.float64)
         self.gv_trg_mean = np.asarray(gv_trg_mean, np.float64)
@@ -82,21 +89,26 @@ class ValidationPass(object):
     def _passes(self, src, trg, y_pp, y_src, y_trg, eps):
         enc, dec, L, sd = self.enc, self.dec, self.lat_dim, self.stdim
         f = lambda t: t.to(torch.float32)
+        laplace = self._laplace
 
         def run(mod, xs, ys, clamp):
             """mod over a list of [B, T, C] inputs: inputs of one length go as rows of one call (rows are independent recurrences)."""
             outs = [None] * len(xs)
+            kw = {"clamp_vae_laplace": clamp} if laplace else {"clamp_vae": clamp}
             for T in sorted({x.shape[1] for x in xs}):
                 ids = [i for i, x in enumerate(xs) if x.shape[1] == T]
                 if len(ids) == 1:
-                    outs[ids[0]] = mod(xs[ids[0]], ys[ids[0]], clamp_vae=clamp, lat_dim=L)[0]
+                    outs[ids[0]] = mod(xs[ids[0]], ys[ids[0]], lat_dim=L, **kw)[0]
                     continue
-                out = mod(torch.cat([xs[i] for i in ids], 0), torch.cat([ys[i] for i in ids], 0), clamp_vae=clamp, lat_dim=L)[0]
+                out = mod(torch.cat([xs[i] for i in ids], 0), torch.cat([ys[i] for i in ids], 0), lat_dim=L, **kw)[0]
                 for i, part in zip(ids, torch.split(out, [xs[i].shape[0] for i in ids], 0)):
                     outs[i] = part
             return outs
 
         def draw(lat, name):
+            if laplace:      # rows flattened to [B T, 2L]; eps: the reference's uniforms, through its eps= argument
+                e = None if eps is None else f(eps[name]).reshape(-1, L)
+                return gru_vae.sampling_vae_laplace(lat.reshape(-1, 2 * L), lat_dim=L, eps=e).reshape(lat.shape[0], lat.shape[1], L)
             if eps is None:
                 return gru_vae.sampling_vae_batch(lat, lat_dim=L)
             return gru_vae.sampling_with_eps(lat, f(eps[name]), lat_dim=L)
@@ -185,7 +197,7 @@ class ValidationPass(object):
                               ("loss_lat_src_cv", "lat_src_trg", fs)):
                 a, lda = row(P[t], j)
                 o[n] = plan.vec()
-                stat(1, _cabi.STAT_KL, nfr, 0, L, a, lda, out=o[n])
+                stat(1, _cabi.STAT_KL_LAPLACE if self._laplace else _cabi.STAT_KL, nfr, 0, L, a, lda, out=o[n])
             # :895-896, :912-913, :938-939, :950-951: the f64 DTW operands
             for key, t, side, col, c1 in (("lat_srctrg", P["lat_srctrg"], "src_par", 0, 2 * L), ("lat_src", P["lat_src"], "src", 0, 2 * L),
                                           ("lat_trgsrc", P["lat_trgsrc"], "trg_par", 0, 2 * L), ("lat_trg", P["lat_trg"], "trg", 0, 2 * L),

@@ -465,7 +465,8 @@ int cvae_sample_laplace_backward(cvae_ctx* ctx, const float* dz, const float* la
  * It is honoured by cvae_pass_input.lat_dim (the draw inside a pass prologue, single or the mean of n_draws), by the lat_dim of
  * cvae_cycle_forward / cvae_cycle_forward_carry (the three draws of every cycle are Laplace draws and the encoder passes clamp at
  * the Laplace floor), of cvae_latent_mean, of cvae_sample_cat / cvae_sample_cat_backward (d mu = dz, d s = dz * exp(s) * u(eps)) and
- * of cvae_stage4_loss (KL = sum_d(-s + b exp(-|mu|/b) + |mu| - 1), b = exp(s): loss_vae_laplace, gru_vae.py:130-139).  Every entry
+ * of cvae_stage4_loss (KL = sum_d(-s + b exp(-|mu|/b) + |mu| - 1), b = exp(s): loss_vae_laplace, gru_vae.py:130-139), and by
+ * cvae_trainlog_window_args.L (record entries [3], [4] are that KL).  Every entry
  * strips the flag before it validates or uses the dimension; without it nothing changes.
  */
 #define CVAE_DRAW_LAPLACE (1 << 30)
@@ -755,6 +756,8 @@ int cvae_dtw_batch(cvae_ctx* ctx, const cvae_dtw_problem* probs, int P, void* wo
  *                       GV=False)'s mean, :1006-1013; cvae_mcd_l1's second output, here in f64)
  *   CVAE_STAT_KL        out[0] = mean over t < rows of 0.5 sum_{l < c1} (exp(s) + mu^2 - s - 1), a[t] = [mu (c1) | s (c1)]
  *                       (loss_vae, :1015-1019; cvae_kl_gauss in f64)
+ *   CVAE_STAT_KL_LAPLACE  out[0] = mean over t < rows of sum_{l < c1} (-s + b exp(-|mu|/b) + |mu| - 1), b = exp(s), the operands of
+ *                       CVAE_STAT_KL in its summation order (loss_vae_laplace, gru_vae.py:130-139: the Laplace posterior's loss_lat_*)
  *   CVAE_STAT_GATHER64  dst[k][c - c0] = (double)a[idx[k]][c], k < rows, c0 <= c < c1: the packed f64 DTW operands of :895-951
  *   CVAE_STAT_LATDIST   out[0] = mean_c sqrt(mean_t (a[t][c] - b[t][c])^2), a and b F64 [rows][lda / ldb], c < c1      (:898)
  */
@@ -780,6 +783,7 @@ int cvae_eval_stats(cvae_ctx* ctx, const cvae_stat_job* jobs, int n, double* out
  *                       given at column 0: dtw_c.calc_mcd's frame array as oracle.mcd_aligned defines it (PARITY UNPINNED)   (:224-229)
  */
 enum { CVAE_STAT_MEANSTD64 = 6, CVAE_STAT_MCD64 = 7 };
+enum { CVAE_STAT_KL_LAPLACE = 8 };       /* (listed with CVAE_STAT_KL above) */
 
 /*
  * The n_draws-draw latent mean of stage 5 / 6 as an array of its own (calc_cvgv_gru-cyclevae_gauss.py:180-184: lat_feat, which the
@@ -871,7 +875,9 @@ int cvae_decode_jobs(cvae_ctx* ctx, const cvae_decode_job* jobs, int n_jobs, voi
  * rec_out [n_cyc][B][9] f64 device:
  *   [0..4]  utterance selected and n = min(flen_acc[j], T) > 0: the means over the window's frames 0 .. n-1 of
  *           (10/ln10) sqrt2 sum_d |y[t][d] - x[t][stdim + d]| for y = rec, reccyc, cv   (criterion_mcd(L2=False, GV=False), :1366-1368)
- *           and of 0.5 sum_l (exp(s) + mu^2 - s - 1) for lat, latcv                        (loss_vae, :1370-1371); else NaN
+ *           and of 0.5 sum_l (exp(s) + mu^2 - s - 1) for lat, latcv                        (loss_vae, :1370-1371); else NaN.
+ *           L given as L | CVAE_DRAW_LAPLACE: the last two are the means of sum_l (-s + b exp(-|mu|/b) + |mu| - 1), b = exp(s)
+ *           (loss_vae_laplace, gru_vae.py:130-139); nothing else of the call changes
  *   [5..8]  utterance selected, s_idx[j] >= 0: with f_k = spcidx[j][s_idx[j] + k], k <= e_idx[j] - s_idx[j], r_k = f_k - src_idx_s,
  *           the means over k of (10/ln10) sqrt(2 sum_{d >= d0} (x[r_k][stdim + d] - y[r_k][d])^2) for (y, d0) = (rec, 0), (rec, 1),
  *           (reccyc, 0), (reccyc, 1): dtw_c.calc_mcd as oracle.mcd_aligned defines it (PARITY UNPINNED), :1435-1439.  An r_k outside
