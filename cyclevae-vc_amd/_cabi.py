@@ -151,6 +151,11 @@ TRAINLOG_SLOTS = ("lat", "rec", "cv", "latcv", "reccyc")      # cvae_trainlog_wi
 TRAINLOG_REC = 9                                    # doubles per (cycle, utterance) record
 
 
+class MoveJob(C.Structure):
+    """cvae_move_job: one strided row copy of cvae_stream_move (device addresses, strides in floats)."""
+    _fields_ = [("dst", _fp), ("src", _fp), ("rows", C.c_int32), ("width", C.c_int32), ("dst_stride", C.c_int64), ("src_stride", C.c_int64)]
+
+
 class TrainlogWindowArgs(C.Structure):
     """cvae_trainlog_window_args (device addresses; flen_acc, s_idx, e_idx, selected: HOST arrays the call reads before it returns)."""
     _fields_ = [("traj", (_fp * 5) * TRAINLOG_MAX_CYC), ("x_win", _fp), ("x_row_stride", C.c_int64), ("x_utt_stride", C.c_int64),
@@ -197,7 +202,7 @@ class _Bound(object):
 # Test queries added WITHOUT an ABI bump: a library of the same ABI version built before one of them still loads (every kernel entry
 # point is there), and calling the missing query raises CvaeError.  The shipped library must export them (__graft_entry__.build and
 # tests/test_cabi_exports.py check all of EXPORTS).
-ADDITIVE = ("cvae_plan_pass_deep_tiles", "cvae_plan_train_pass")
+ADDITIVE = ("cvae_plan_pass_deep_tiles", "cvae_plan_train_pass", "cvae_stream_move")
 NO_CONTEXT = ("cvae_last_error_string", "cvae_abi_version", "cvae_ctx_create", "cvae_ctx_destroy")
 _CDLLS = {}     # path -> (CDLL with argtypes declared): one load per process, any number of contexts
 
@@ -357,6 +362,9 @@ class CvaeLib(object):
         L.cvae_decode_jobs.argtypes = [C.POINTER(DecodeJob), C.c_int, _fp, C.c_size_t, _fp]
         L.cvae_trainlog_window.restype = C.c_int
         L.cvae_trainlog_window.argtypes = [C.POINTER(TrainlogWindowArgs), _fp]
+        if hasattr(L, "cvae_stream_move"):               # (ADDITIVE, below)
+            L.cvae_stream_move.restype = C.c_int
+            L.cvae_stream_move.argtypes = [C.POINTER(MoveJob), C.c_int, _fp]
         L.cvae_step_timing.restype = C.c_int
         L.cvae_step_timing.argtypes = [C.POINTER(NetDesc), C.c_int, C.c_int, _fp, C.POINTER(C.c_double * 8), _fp]
         L.cvae_profile_collect.restype = C.c_int
@@ -712,6 +720,13 @@ class CvaeLib(object):
         """args: a TrainlogWindowArgs; its host arrays are read before the call returns, nothing is waited for."""
         self._check(self.lib.cvae_trainlog_window(C.byref(args), stream or None), "cvae_trainlog_window")
 
+    def stream_move(self, jobs, stream=0):
+        """jobs: list of MoveJob (a host list; the table travels in the kernel arguments): every copy in one launch per 96 jobs."""
+        if not hasattr(self.lib, "cvae_stream_move"):
+            raise CvaeError("%s was built before cvae_stream_move was added: rebuild it" % self.path)
+        arr = (MoveJob * max(1, len(jobs)))(*jobs)
+        self._check(self.lib.cvae_stream_move(arr, len(jobs), stream or None), "cvae_stream_move")
+
     def step_timing(self, d, B, T, ws, stream=0):
         out = (C.c_double * 8)()
         self._check(self.lib.cvae_step_timing(C.byref(d), B, T, ws, C.byref(out), stream or None), "cvae_step_timing")
@@ -799,6 +814,6 @@ EXPORTS = ("cvae_last_error_string", "cvae_abi_version", "cvae_ctx_create", "cva
            "cvae_kl_gauss_backward",
            "cvae_gv_postfilter", "cvae_mcd_aligned", "cvae_mc2e", "cvae_dtw_work_bytes", "cvae_dtw_org_to_trg",
            "cvae_dtw_batch_work_bytes", "cvae_dtw_batch", "cvae_eval_stats", "cvae_latent_mean",
-           "cvae_mc2e_batch_work_bytes", "cvae_mc2e_batch", "cvae_decode_jobs", "cvae_trainlog_window",
+           "cvae_mc2e_batch_work_bytes", "cvae_mc2e_batch", "cvae_decode_jobs", "cvae_trainlog_window", "cvae_stream_move",
            "cvae_net_prepared_bytes_deep", "cvae_net_prepare_scratch_bytes_deep", "cvae_net_prepare_deep", "cvae_pass_workspace_bytes_deep",
            "cvae_plan_pass", "cvae_plan_pass_deep", "cvae_plan_pass_deep_tiles", "cvae_gru_rnn_forward_deep", "cvae_net_prepared_in_range")

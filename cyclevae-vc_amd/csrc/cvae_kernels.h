@@ -284,7 +284,8 @@ struct ProParams {
     int zero_status_n;   // how many: 8 in a workspace (status + spare words), the 4 words of a status sink (cvae_set_status_sink: int32[4])
     unsigned* ll_counter;   // null, or the workspace's launch counter of k_gru_steps_ll: incremented here, read there as the tag nonce
     int nA, nH, nD;      // block ranges: [0,nA) assemble rows, [nA,nA+nH) slot-0 init, then dy, then gx0, last block zeroing
-    int nG;              // 0, or blocks of the frame-0 feedback correction gx0 (only when no cell carries a state in: dy = y_in - out_1.b)
+    int nG;              // 0, or blocks of the frame-0 feedback correction gx0 (fresh cells: dy = y_in - out_1.b; cells without y_in continue
+                         //   a recurrence: dy = 0, zeros; never with a cell that has both h_in and y_in)
     float* gx0;          // [ncell*B][3H]: W_ih[:, R*C:] . dy -- what the recurrent kernel adds to the gates of frame 0 (else it forms
     const float* wyT;    //   the sums itself, cvae_t0_fix: 4 loads per channel and thread in front of its first step); wyT [Co][3H]
     // Range guard of the limb operands (CVAE_STATUS_RANGE).  range_word: null (the pass builds no limb operand: nothing is checked),
@@ -489,9 +490,10 @@ __global__ void k_prologue(ProParams p) {
         const long q4 = ((long)(blk - p.nA - p.nH - p.nD) * blockDim.x + tid) * 4, H3 = 3L * p.H;
         if (q4 < (long)p.ncell * p.B * H3) {
             const int bb = (int)(q4 / H3), col = (int)(q4 - (long)bb * H3);
-            const float* yi = p.cell[bb / p.B].y_in + (long)(bb % p.B) * p.Co;
+            const float* yi = p.cell[bb / p.B].y_in;
             float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-            int c = 0;
+            int c = yi ? 0 : p.Co;      // (no y_in: the cell continues a recurrence, its correction is zero)
+            if (yi) yi += (long)(bb % p.B) * p.Co;
             for (; c + 8 <= p.Co; c += 8) {          // eight channels' loads in flight before the first use (see cvae_t0_fix)
                 float d[8], w[8][4];
 #pragma unroll

@@ -395,6 +395,9 @@ inline int row_tiles_per_block(int cus, int per_tile, int ntiles) {
 // V5 -> V4 -> V2 -> GENERIC -> PER_STEP (run_pass; LL, V6 and V6H return the error).
 struct PassFacts {      // what a call's pointers decide
     bool h_in, y_last, h_last, many_draws;      // any cell with a carried-in state / a raw last projection / a state out / n_draws > 1
+    bool fresh;                                 // any cell without a carried-in state
+    bool h_in_y;                                // any cell with a carried-in state AND a y_in of its own: its frame-0 feedback correction
+                                                //   W_ih[:, R*C:] . (y_in - out_1(h_in)) needs the dy role's H-long products
 };
 enum { PRO_ROWS = 0, PRO_DRAWS = 1, PRO_TILES = 2 };      // prologue launch: 64 threads per (row, frame); 256 (draws summed in slices); 256 per (32-row tile, frame)
 enum { PROJ_GEMM = 0, PROJ_FUSED = 1, PROJ_V6 = 2 };      // projection: GEMM + k_epilogue; k_outproj<1|4|8>; k_outproj_v6
@@ -475,7 +478,12 @@ EvalPlan plan_eval_pass(const Dims& m, int Brows, int T, int flags, int cus, boo
     // the pair copies are written whenever SPLIT_F16 is set off V6, but only k_gru_steps_v5 reads them: a pass that ends up on
     // k_gru_steps_ll or on an fp32-operand kernel has nothing to report (limbs)
     pn.pairs = !v6 && (flags & CVAE_FLAG_SPLIT_F16);
-    pn.gx0_ready = v6 && !f.h_in;
+    // A pass that MIXES fresh cells (no h_in: dy = y_in - out_1.b) with cells that continue a recurrence (h_in, no y_in: dy = 0) keeps
+    // the prologue's gx0 role: the fresh cells then compute the bits they compute in a pass of fresh cells only (a live stream opens
+    // sessions next to running ones: stream.py), and the role writes zeros for the continuing cells, which changes no bit of them.
+    // Every other pass with a carried state -- all cells continuing (the windowed stage 6), or a cell with both h_in and y_in (the
+    // chain's carry form, GRU_RNN.forward(h_in=...)) -- forms the correction in the recurrent kernel (cvae_t0_fix), as before.
+    pn.gx0_ready = v6 && (!f.h_in || (f.fresh && !f.h_in_y));
     // no cell carries a state in <=> k_prologue zero-fills slot 0 (its !any_h branch reads the same pointers PassFacts was built from)
     pn.h0_zero = v6 && !f.h_in && opt(OPT_V6_SKIP_T0) != 0;
     // the fp32 state copy of a V6 pass is only read by the raw projection (y_last), k_hlast and the projections off the limb triples
@@ -651,7 +659,7 @@ struct ProTargets {
     float* hs;                // fp16-pair copies of slot 0 and of the input (SPLIT_F16 off V6)
     float* xs;
     long xs_plane;
-    float* gx0;               // frame-0 feedback correction (V6 without a carried-in state)
+    float* gx0;               // frame-0 feedback correction (V6: no carried-in state, or fresh cells beside continuing ones)
     unsigned* ll_counter;     // launch counter of k_gru_steps_ll
 };
 struct RangeSlot { int* word; int val; float at; };      // where and how a kernel behind the prologue reports on the same guard
@@ -788,6 +796,8 @@ int run_pass(const Dims& m, const cvae_net_desc* d, const float* P, const Cell* 
     PassFacts facts = {};
     for (int c = 0; c < ncell; ++c) {
         facts.h_in = facts.h_in || cells[c].h_in != nullptr;
+        facts.fresh = facts.fresh || cells[c].h_in == nullptr;
+        facts.h_in_y = facts.h_in_y || (cells[c].h_in != nullptr && cells[c].y_in != nullptr);
         facts.y_last = facts.y_last || cells[c].y_last != nullptr;
         facts.h_last = facts.h_last || cells[c].h_last != nullptr;
         facts.many_draws = facts.many_draws || (cells[c].in->lat && cells[c].in->n_draws > 1);
@@ -1509,3 +1519,4 @@ int cvae_net_prepared_in_range(cvae_ctx* ctx, const cvae_net_desc* d, int n_laye
 #include "cvae_decode.inc"
 #include "cvae_trainlog.inc"
 #include "cvae_deep.inc"
+#include "cvae_stream.inc"

@@ -903,6 +903,24 @@ typedef struct cvae_trainlog_window_args {
 } cvae_trainlog_window_args;
 int cvae_trainlog_window(cvae_ctx* ctx, const cvae_trainlog_window_args* a, void* stream);
 
+/*
+ * Live streams (stream.py: StreamConverter) -- a list of strided row copies as ONE launch: element (r, c) of a job, r < rows,
+ * c < width, goes from src[r * src_stride + c] to dst[r * dst_stride + c] (fp32 device arrays, strides in floats).  A stream step
+ * appends the frames pushed since the last step to its sessions' input buffers, compacts their buffers and packs their converted
+ * frames with one call each, whatever the number of sessions (as single copies: 3 x sessions launches per step).  `jobs` is a HOST
+ * array read before the call returns; the table travels in the kernel arguments, 96 jobs per launch (more: several launches).
+ * rows == 0 jobs are legal and do nothing.  Refused (-1, nothing enqueued): a null pointer with rows > 0, a negative field, width
+ * larger than a stride, a job whose source and destination ranges overlap (blocks run in no order).  16-byte accesses where both
+ * pointers and both strides of a job are 16-byte aligned, single floats for the rest of a row and for every other job.
+ */
+typedef struct cvae_move_job {
+    float* dst;
+    const float* src;
+    int32_t rows, width;
+    int64_t dst_stride, src_stride;
+} cvae_move_job;
+int cvae_stream_move(cvae_ctx* ctx, const cvae_move_job* jobs, int njobs, void* stream);
+
 /* Copy status words (int32[4]) of a workspace to the host; synchronises `stream`.  status[0]!=0 = barrier timeout;
  * status[3] == CVAE_STATUS_RANGE: the latest call on this workspace met an operand outside the limb window (no sink set). */
 int cvae_workspace_status(cvae_ctx* ctx, const void* workspace, int32_t status_out[4], void* stream);
