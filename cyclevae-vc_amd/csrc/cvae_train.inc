@@ -2,6 +2,9 @@
 // Adam.  The recurrences are persistent cooperative launches where the size allows (H = 1024, 64: exact-operand kernels of
 // cvae_train_w3.h / cvae_train_x3.h by default, fp16-pair kernels with train_kernel = 1) and per-step launches otherwise, in the
 // forms plan_train_pass chooses; everything batched is an MFMA GEMM over time-major buffers (cvae_train_kernels.h).
+// A pass is a TrainPass (dimensions, layouts, plan, pointers) run through named stages.  Forward: draw_train_masks, run_train_prologue,
+// run_train_front_end, run_fwd_recurrence, run_train_projection.  Backward: wait_for_side_scratch, run_bwd_dy, run_bwd_recurrence or
+// run_bwd_steps, launch_wgrad / launch_wgrad_side, run_input_chain, run_conv_wgrad (DESIGN.md 4.2).
 namespace {
 
 struct TDims {
@@ -508,22 +511,408 @@ void gemm_ks(hipStream_t st, const float* A, long lda, const float* Bm, long ldb
                        accumulate);
 }
 
+// What the forward and the backward of one training pass share: dimensions, layouts, the plan, base pointers.  Both entry points
+// open one (after their own argument checks) and hand it to the stages below, in order; DESIGN.md 4.2 has the stages as a table.
+struct TrainPass {
+    Dims m; TDims t;
+    TPrep pl; TrainPlan pn; TTape tl; TScratch sl;       // the image's layout, the plan, the layouts of tape and scratch
+    const cvae_net_desc* d;
+    const float* P;      // the train image
+    float* TP;           // the tape: written by the forward, only read by the backward (which casts its const away to open the pass)
+    float* S;            // the scratch
+    int B, T, Bp, M;     // M = T * Bp rows of the time-major buffers
+    long mtot;           // (T + 1) * Bp: with the slot of the incoming state
+    hipStream_t st;
+    SplitWs fws, bws;    // gpart with the forward's arrival counters (cleared by the prologue) / the backward's (by its memset)
+};
+
+// p.m is filled (make_train_dims): the layouts and the plan, which must be the same in both directions (the backward never checked B, T)
+void open_train_pass(TrainPass& p, const cvae_net_desc* d, const void* image, int B, int T, void* tape, void* scratch, void* stream) {
+    p.d = d; p.B = B; p.T = T; p.st = (hipStream_t)stream;
+    p.t = make_tdims(p.m, T);
+    p.pl = tprep_layout(p.m, d->has_scale_in != 0, d->has_scale_out != 0);
+    p.pn = plan_train_pass(p.m, B, T);
+    p.tl = ttape_layout(p.m, B, T, p.pn.Bp); p.sl = tscratch_layout(p.m, T, p.pn.Bp);
+    p.P = (const float*)image; p.TP = (float*)tape; p.S = (float*)scratch;
+    p.Bp = p.tl.Bp; p.M = T * p.Bp; p.mtot = (long)(T + 1) * p.Bp;
+    p.fws = SplitWs{p.S + p.sl.gpart, (unsigned*)(p.S + p.sl.fcnt)};
+    p.bws = SplitWs{p.S + p.sl.gpart, (unsigned*)(p.S + p.sl.bcnt)};
+}
+
+// Dropout masks into the tape, which keeps them for the backward: supplied (parity tests inject the reference's) or drawn with Philox.
+// With a side stream set, the mask of the recurrence's feedback operand (gmask, two thirds of the draws; first read by the mask-bit
+// kernel behind the three front-end GEMMs) is drawn THERE, beside the prologue and those GEMMs: 25-40 us less on the critical path of
+// every pass of 64 rows (the masks depend on nothing but the seed).  Returns 1 where the recurrence has to wait for mask_join, < 0: error.
+int draw_train_masks(const TrainPass& p, const float* cmask, const float* gmask, uint64_t seed, float p_drop) {
+    const int B = p.B, T = p.T;
+    const long nc = (long)B * T * p.t.C9, ng = (long)T * B * p.m.H;      // values of conv_drop's mask / of the feedback operand's
+    float *const cm = p.TP + p.tl.cmask, *const gm = p.TP + p.tl.gmask;
+    const long mparts = cx().draw_parts > 1 && B % cx().draw_parts == 0 ? cx().draw_parts : 1;
+    const long rows = cx().draw_rows > 0 ? cx().draw_rows : (long)B / mparts;
+    // one k_mask_gen launch: n values of Philox stream `id`, `inner` of them per batch row
+    auto draw = [&](hipStream_t s, float* dst, long n, uint64_t id, long inner) {
+        hipLaunchKernelGGL((k_mask_gen), dim3(nblk(n, 256)), dim3(256), 0, s, dst, n, seed, id, p_drop, (long)B, inner, rows, cx().draw_row0, mparts);
+    };
+    if (!cmask && !gmask && cx().side && opt(OPT_MASKS_ON_SIDE) && ng >= (1L << 20)) {
+        if (!cx().mask_fork) CVAE_HIP_OK(hipEventCreateWithFlags(&cx().mask_fork, hipEventDisableTiming));
+        if (!cx().mask_join) CVAE_HIP_OK(hipEventCreateWithFlags(&cx().mask_join, hipEventDisableTiming));
+        CVAE_HIP_OK(hipEventRecord(cx().mask_fork, p.st));                 // (behind the tape's memset)
+        CVAE_HIP_OK(hipStreamWaitEvent(cx().side, cx().mask_fork, 0));
+        draw(cx().side, gm, ng, 2, p.m.H);
+        CVAE_HIP_OK(hipEventRecord(cx().mask_join, cx().side));
+        draw(p.st, cm, nc, 1, (long)T * p.t.C9);
+        return 1;
+    }
+    if (!cmask && !gmask) {
+        hipLaunchKernelGGL((k_mask_gen2), dim3(nblk(nc + ng, 256)), dim3(256), 0, p.st, cm, nc, (long)T * p.t.C9, gm, ng, (long)p.m.H, seed, p_drop,
+                           (long)B, rows, cx().draw_row0, mparts);
+        return 0;
+    }
+    if (cmask) CVAE_HIP_OK(hipMemcpyAsync(cm, cmask, (size_t)nc * sizeof(float), hipMemcpyDeviceToDevice, p.st));
+    else draw(p.st, cm, nc, 1, (long)T * p.t.C9);
+    if (gmask) CVAE_HIP_OK(hipMemcpyAsync(gm, gmask, (size_t)ng * sizeof(float), hipMemcpyDeviceToDevice, p.st));
+    else draw(p.st, gm, ng, 2, p.m.H);
+    return 0;
+}
+
+// scale_in, the time-major padded input, slot 0 of the state buffers, y_in; it also clears the flags / status words of the
+// recurrence and the arrival counters of this pass's split GEMMs
+void run_train_prologue(const TrainPass& p, const float* x, const float* y_in, const float* h_in) {
+    const Dims& m = p.m; const TTape& tl = p.tl; const TScratch& sl = p.sl;
+    TrainProParams pp;
+    pp.x = x; pp.y_in = y_in; pp.h_in = h_in; pp.bo = p.P + p.pl.bo;
+    pp.sin_w = p.d->has_scale_in ? p.P + p.pl.sin_w : nullptr;
+    pp.sin_b = p.d->has_scale_in ? p.P + p.pl.sin_b : nullptr;
+    pp.B = p.B; pp.Bp = p.Bp; pp.T = p.T; pp.C = m.C; pp.Cq = p.t.Cq; pp.pad = m.pad; pp.Co = m.Co; pp.Cop = m.Cop; pp.H = m.H;
+    pp.xnp = p.TP + tl.xnp; pp.hbuf = p.S + sl.hbuf; pp.obuf = p.S + sl.obuf; pp.hrow = p.TP + tl.hrow; pp.orow = p.TP + tl.orow;
+    pp.ybuf = p.TP + tl.ybuf; pp.dy = p.S + sl.dy; pp.mtot = p.mtot;
+    pp.nA = p.B * p.T; pp.nH = (int)nblk((long)p.Bp * m.H, 1024); pp.nY = (int)nblk((long)p.Bp * m.Cop, 64);
+    pp.zero_ptr = p.S + sl.tflags; pp.zero_n = sl.fcnt + GEMM_CNT - sl.tflags;
+    hipLaunchKernelGGL((k_train_prologue), dim3(pp.nA + pp.nH + pp.nY + nblk(pp.zero_n, 64)), dim3(64), m.C * sizeof(float), p.st, pp);
+}
+
+// conv0, conv1 with conv_drop in its epilogue (the K padding columns of xcm stay zero from the tape's memset), input-gate GEMM:
+// time-major segmented-row GEMMs
+void run_train_front_end(const TrainPass& p) {
+    const Dims& m = p.m; const TDims& t = p.t; const TTape& tl = p.tl; const int Bp = p.Bp, T = p.T;
+    gemm_nt(p.st, p.TP + tl.xnp, t.Cq, t.Cq, (long)Bp * t.Cq, p.P + p.pl.w0r, t.K0, p.P + p.pl.b0, p.TP + tl.c0, t.C3p, t.F0 * Bp, t.C3, t.K0, 0, p.fws);
+    gemm_nt(p.st, p.TP + tl.c0, t.C3p, t.C3p, (long)m.ks * Bp * t.C3p, p.P + p.pl.w1r, t.K1, p.P + p.pl.b1, p.TP + tl.xcm, t.C9p, T * Bp, t.C9, t.K1, 0,
+            p.fws, EpiMask{p.TP + tl.cmask, p.B, Bp, T});
+    gemm_nt(p.st, p.TP + tl.xcm, t.C9p, t.C9p, 0, p.P + p.pl.wix, t.C9p, p.P + p.pl.cfold_t, p.S + p.sl.gi, m.H3, T * Bp, m.H3, t.C9p, 0, p.fws);
+}
+
+// flag words of the forward recurrences; their status word behind the flags (FWD_LL: the first word), or the sink; the phase
+// counters of block 0 with the option train_prof
+inline unsigned* fwd_flags(const TrainPass& p) { return (unsigned*)(p.S + p.sl.tflags); }
+inline int* fwd_status(const TrainPass& p, bool ll = false) {
+    return cx().status_sink ? cx().status_sink : (int*)(fwd_flags(p) + (ll ? 0 : (size_t)(p.Bp / 16) * (p.m.H / 8)));
+}
+inline long long* prof_words(const TrainPass& p) { return opt(OPT_TRAIN_PROF) ? (long long*)(p.S + p.sl.tprof) : nullptr; }
+
+// at most three rows: fp32 FMAs, one word per unit and row exchanged (cvae_train_ll.h).  KERNEL ORDER: clang emits the instances in the
+// order it resolves their names; <1>, <2> inside the inner conditional, the pointer assigned first below, keep the code object's order
+hipError_t fwd_ll(const TrainPass& p) {
+    const Dims& m = p.m;
+    TrainFwdLLParams q;
+    q.xbuf = p.S + p.sl.llx; q.nonce = (cx().ll_train_launch.fetch_add(1u) & 0xffffu) << 16; q.backoff = p.pn.fwd_backoff;
+    q.wrec_t = p.P + p.pl.wrec_t; q.gi = p.S + p.sl.gi; q.bhn = p.P + p.pl.bhn; q.gmask = p.TP + p.tl.gmask; q.tape = p.TP + p.tl.gates;
+    q.hrow = p.TP + p.tl.hrow; q.orow = p.TP + p.tl.orow; q.wyT = p.P + p.pl.wyT; q.dy = p.S + p.sl.dy; q.Co = m.Co; q.B = p.B; q.Bp = p.Bp;
+    q.H = m.H; q.T = p.T; q.status = fwd_status(p, true); const size_t lds = (size_t)(2 * 64 * 49 + 4 * 48) * sizeof(float);
+    return cvae_launch_coop(p.B <= 2 ? (p.B == 1 ? k_train_fwd_steps_ll<1> : k_train_fwd_steps_ll<2>) : k_train_fwd_steps_ll<3>, dim3(m.H / 4),
+                            dim3(256), lds, p.st, q);
+}
+
+// the 16-row-tile exact forms (16- and 8-unit blocks): exchanged h in limb triples, the feedback mask as bits
+TrainFwd3hParams fwd3h(const TrainPass& p, const float* w3) {
+    const Dims& m = p.m; const int Bp = p.Bp, T = p.T;
+    hipLaunchKernelGGL((k_train_x3h_slot0), dim3(nblk((long)Bp * m.H, 256)), dim3(256), 0, p.st, (const float*)(p.TP + p.tl.hrow),
+                       p.S + p.sl.hx3, Bp, m.H);
+    hipLaunchKernelGGL((k_train_x3h_maskbits), dim3(nblk((long)T * (Bp / 16) * 2048, 256)), dim3(256), 0, p.st,
+                       (const float*)(p.TP + p.tl.gmask), (unsigned char*)(p.S + p.sl.ox3), T, p.B, Bp, m.H, m.H == 1024 ? 8 : 1);
+    TrainFwd3hParams q;
+    q.hx = p.S + p.sl.hx3; q.mbits = (const unsigned char*)(p.S + p.sl.ox3); q.w3 = w3; q.gi = p.S + p.sl.gi; q.bhn = p.P + p.pl.bhn;
+    q.gmask = p.TP + p.tl.gmask; q.tape = p.TP + p.tl.gates; q.hrow = p.TP + p.tl.hrow; q.orow = p.TP + p.tl.orow; q.wyT = p.P + p.pl.wyT;
+    q.dy = p.S + p.sl.dy; q.Co = m.Co; q.B = p.B; q.Bp = Bp; q.H = m.H; q.T = T; q.rts = p.pn.fwd_rts; q.flags = fwd_flags(p);
+    q.status = fwd_status(p); q.backoff = p.pn.fwd_backoff; q.xmap = (int)(opt(OPT_TRAIN_XMAP) & 1); q.prof = prof_words(p);
+    return q;
+}
+
+// exact operands, 16-unit blocks with the zero column tiles of [W_hh | F] dropped (cvae_train_w3.h)
+hipError_t fwd_w3(const TrainPass& p) {
+    const Dims& m = p.m; const TrainFwd3hParams q = fwd3h(p, p.P + p.pl.wfw3);
+    const int nl1 = m.H == 1024 ? CVAE_FWDW_NL1 : (opt(OPT_BWD_W3_L1_H64) ? 2 : 0);
+    const size_t lds = (size_t)(4 * 16 * 68) * sizeof(float) + 1280 + (size_t)4 * 6 * w3_gpw(m) * 512 + (size_t)4 * nl1 * 1024;
+    void (*k)(TrainFwd3hParams) = k_train_fwd_steps_w3<8, 4, CVAE_FWDW_NL1>;      // (named first: KERNEL ORDER, see fwd_ll)
+    if (m.H != 1024) k = nl1 == 2 ? k_train_fwd_steps_w3<1, 2, 2> : k_train_fwd_steps_w3<1, 2, 0>;
+    return cvae_launch_coop(k, dim3((m.H / 16) * p.pn.fwd_rts), dim3(256), lds, p.st, q);
+}
+
+// exact operands as fp16 triples, 8-unit x 32-row-tile blocks (cvae_train_x3.h)
+hipError_t fwd_x3(const TrainPass& p) {
+    const Dims& m = p.m; const int Bp = p.Bp, T = p.T, kpw = x3_kpw(m);
+    hipLaunchKernelGGL((k_train_x3_slot0), dim3(nblk((long)Bp * m.H, 256)), dim3(256), 0, p.st, (const float*)(p.TP + p.tl.hrow),
+                       p.S + p.sl.hx3, p.mtot, Bp, m.H);
+    hipLaunchKernelGGL((k_train_x3_maskbits), dim3(nblk((long)T * (Bp / 32) * 4096, 256)), dim3(256), 0, p.st,
+                       (const float*)(p.TP + p.tl.gmask), (unsigned char*)(p.S + p.sl.ox3), T, p.B, Bp, m.H, kpw);
+    TrainFwd3Params q;
+    q.hx = p.S + p.sl.hx3; q.mbits = (const unsigned char*)(p.S + p.sl.ox3); q.mtot = p.mtot; q.w3 = p.P + p.pl.w3f; q.gi = p.S + p.sl.gi;
+    q.bhn = p.P + p.pl.bhn; q.gmask = p.TP + p.tl.gmask; q.tape = p.TP + p.tl.gates; q.hrow = p.TP + p.tl.hrow; q.orow = p.TP + p.tl.orow;
+    q.wyT = p.P + p.pl.wyT; q.dy = p.S + p.sl.dy; q.Co = m.Co; q.B = p.B; q.Bp = Bp; q.H = m.H; q.T = T; q.rts = p.pn.fwd_rts;
+    q.flags = fwd_flags(p); q.status = fwd_status(p); q.xmap = (int)(opt(OPT_TRAIN_XMAP) & 1); q.prof = prof_words(p);
+    const size_t lds = (size_t)(4 * 32 * 40 + 6 * 256) * sizeof(float) + 1280 + (size_t)4 * 2 * kpw * 1024;
+    return cvae_launch_coop(m.H == 1024 ? k_train_fwd_steps_x3<16> : k_train_fwd_steps_x3<1>, dim3((m.H / 8) * p.pn.fwd_rts), dim3(256), lds,
+                            p.st, q);
+}
+
+// the same with 16-row tiles
+hipError_t fwd_x3h(const TrainPass& p) {
+    const Dims& m = p.m; const TrainFwd3hParams q = fwd3h(p, p.P + p.pl.w3h);
+    const size_t lds = (size_t)(4 * 16 * 36) * sizeof(float) + 640 + (size_t)(m.H == 1024 ? 4 : 2) * 4 * (m.H == 1024 ? 8 : 1) * 1024;
+    return cvae_launch_coop(m.H == 1024 ? k_train_fwd_steps_x3h<8, 4> : k_train_fwd_steps_x3h<1, 2>, dim3((m.H / 8) * p.pn.fwd_rts), dim3(256),
+                            lds, p.st, q);
+}
+
+// the matrix product on fp16 pairs (same form as the eval kernel) or on the fp32-input MFMA
+hipError_t fwd_pair(const TrainPass& p, bool pair) {
+    const Dims& m = p.m;
+    TrainFwdParams q;
+    q.hbuf = p.S + p.sl.hbuf; q.obuf = p.S + p.sl.obuf; q.mtot = p.mtot; q.hrow = p.TP + p.tl.hrow; q.orow = p.TP + p.tl.orow;
+    q.wrec_t8 = pair ? p.P + p.pl.wrec_t8h : p.P + p.pl.wrec_t8; q.gi = p.S + p.sl.gi; q.bhn = p.P + p.pl.bhn; q.gmask = p.TP + p.tl.gmask;
+    q.tape = p.TP + p.tl.gates; q.wyT = p.P + p.pl.wyT; q.dy = p.S + p.sl.dy; q.Co = m.Co; q.B = p.B; q.Bp = p.Bp; q.H = m.H; q.T = p.T;
+    q.rts = p.pn.fwd_rts; q.flags = fwd_flags(p); q.status = fwd_status(p); q.prof = prof_words(p); q.backoff = p.pn.fwd_backoff;
+    const size_t lds = (4 * 16 * 36 + 2 * 128) * sizeof(float);
+    return cvae_launch_coop(pair ? (m.H == 1024 ? k_train_fwd_steps_h<16> : k_train_fwd_steps_h<1>)
+                                 : (m.H == 1024 ? k_train_fwd_steps<32> : k_train_fwd_steps<2>),
+                            dim3((m.H / 8) * p.pn.fwd_rts), dim3(256), lds, p.st, q);
+}
+
+// T per-step launches
+void fwd_steps(const TrainPass& p) {
+    const Dims& m = p.m;
+    TrainStepParams sp;
+    sp.hbuf = p.S + p.sl.hbuf; sp.obuf = p.S + p.sl.obuf; sp.mtot = p.mtot; sp.hrow = p.TP + p.tl.hrow; sp.orow = p.TP + p.tl.orow;
+    sp.wrec_t = p.P + p.pl.wrec_t; sp.gi = p.S + p.sl.gi; sp.bhn = p.P + p.pl.bhn; sp.gmask = p.TP + p.tl.gmask; sp.tape = p.TP + p.tl.gates;
+    sp.wyT = p.P + p.pl.wyT; sp.dy = p.S + p.sl.dy; sp.Co = m.Co; sp.B = p.B; sp.Bp = p.Bp; sp.H = m.H;
+    for (int tt = 0; tt < p.T; ++tt) {
+        sp.t = tt;
+        if (p.pn.fwd_col_tiles == 1)
+            hipLaunchKernelGGL((k_gru_step_train<1>), dim3(m.H / 4), dim3(256), 4 * 64 * 20 * sizeof(float), p.st, sp);
+        else if (p.Bp >= 128)
+            hipLaunchKernelGGL((k_gru_step_train<2, 8>), dim3(m.H / 8), dim3(256), 2 * 4 * 128 * 20 * sizeof(float), p.st, sp);
+        else
+            hipLaunchKernelGGL((k_gru_step_train<2>), dim3(m.H / 8), dim3(256), 2 * 4 * 64 * 20 * sizeof(float), p.st, sp);
+    }
+}
+
+// The T dependent steps, in the form the plan chose (bracketed by HIP events with the option train_profile).  join: gmask was drawn
+// on the side stream; the wait sits behind the front-end GEMMs and in front of the first launch that reads the mask.
+int run_fwd_recurrence(const TrainPass& p, bool join) {
+    if (join) CVAE_HIP_OK(hipStreamWaitEvent(p.st, cx().mask_join, 0));
+    TrainProf tprof(p.st, TPROF_FWD, 0.0);
+    const int iv = image_variants(p.P);
+    if (p.pn.fwd_need & ~iv)
+        return fail(-4, "the train image was prepared without the exact-operand kernels' weight images (cvae_net_prepare_train_v "
+                        "variants %d) and this pass (B=%d, T=%d) needs them", iv, p.B, p.T);
+    FwdForm form = p.pn.fwd;
+    if ((form == FWD_PAIR && !(iv & TV_PAIR)) || (form == FWD_FP32 && !(iv & TV_FP32))) form = FWD_STEPS;   // (image without them)
+    hipError_t e = hipSuccess;
+    const char* what = nullptr;      // (the forms that return -3 when their launch is refused name themselves)
+    switch (form) {
+    case FWD_LL: e = fwd_ll(p); what = "small-batch forward training recurrence"; break;
+    case FWD_W3: e = fwd_w3(p); what = "exact-operand forward training recurrence (16-unit blocks)"; break;
+    case FWD_X3: e = fwd_x3(p); what = "exact-operand forward training recurrence"; break;
+    case FWD_X3H: e = fwd_x3h(p); what = "exact-operand forward training recurrence (16-row tiles)"; break;
+    case FWD_PAIR: case FWD_FP32:
+        if (fwd_pair(p, form == FWD_PAIR) == hipSuccess) break;
+        (void)hipGetLastError();     // (a grid that does not fit: the per-step launches)
+        [[fallthrough]];
+    case FWD_STEPS: fwd_steps(p); break;
+    }
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(-3, "%s failed to launch: %s", what, hipGetErrorString(e));
+    }
+    return 0;
+}
+
+// raw projection of the dropped states, then scale_out / clamp into [B][T][Co], the last projection and the last state
+void run_train_projection(const TrainPass& p, int clamp_lat_dim, float* trj_out, float* y_last, float* h_last) {
+    const Dims& m = p.m;
+    gemm_nt(p.st, p.TP + p.tl.orow + (long)p.Bp * m.H, m.H, m.H, 0, p.P + p.pl.wo, m.H, p.P + p.pl.bo, p.TP + p.tl.ybuf + (long)p.Bp * m.Cop, m.Cop,
+            p.T * p.Bp, m.Co, m.H, 0, p.fws);
+    TrainEpiParams ep;
+    ep.ybuf = p.TP + p.tl.ybuf; ep.hrow = p.TP + p.tl.hrow;
+    ep.sout_w = p.d->has_scale_out ? p.P + p.pl.sout_w : nullptr;
+    ep.sout_b = p.d->has_scale_out ? p.P + p.pl.sout_b : nullptr;
+    ep.clamp_from = p.d->has_scale_out ? -1 : clamp_dim(clamp_lat_dim); ep.clamp_min = clamp_floor(clamp_lat_dim);
+    ep.B = p.B; ep.Bp = p.Bp; ep.T = p.T; ep.Co = m.Co; ep.Cop = m.Cop; ep.H = m.H;
+    ep.trj_out = trj_out; ep.y_last = y_last; ep.h_last = h_last;
+    hipLaunchKernelGGL((k_train_epilogue), dim3(p.B * p.T), dim3(64), m.Co * sizeof(float), p.st, ep);
+}
+
+// side-stream GEMMs of an earlier backward may still read this scratch (dgi / dgh / gpart2): wait for the event recorded behind
+// them; a scratch the table no longer knows (evicted) waits for everything the side stream has been given
+int wait_for_side_scratch(const TrainPass& p) {
+    if (!cx().side) return 0;
+    bool known = false;
+    for (int i = 0; i < 8; ++i)
+        if (cx().side_done[i].scratch == p.S && cx().side_done[i].ev) {
+            CVAE_HIP_OK(hipStreamWaitEvent(p.st, cx().side_done[i].ev, 0));
+            known = true;
+        }
+    if (!known && cx().side_last) CVAE_HIP_OK(hipStreamWaitEvent(p.st, cx().side_last, 0));
+    return 0;
+}
+
+// Everything from dyl on is backward scratch: zero it (padding frames of dc1p / dc0p, dh, dyfb, dead rows); the gate gradients dgi / dgh
+// right in front of dyl as well, unless the reverse recurrence writes every row of them.  Then dyl from dout (scale_out^T or the clamp).
+int run_bwd_dy(const TrainPass& p, const float* dout, int clamp_lat_dim) {
+    const Dims& m = p.m;
+    const long zero_from = p.pn.bwd_writes_gates ? p.sl.dyl : p.sl.dgi;
+    CVAE_HIP_OK(hipMemsetAsync(p.S + zero_from, 0, (size_t)(p.sl.total - zero_from) * sizeof(float), p.st));
+    // (the LDS form holds scale_out^T whole: beyond ~120 outputs it no longer fits 64 KB and the plain kernel takes over)
+    if (p.d->has_scale_out && (size_t)(m.Co * m.Co + CVAE_BWD_DY_ROWS * m.Co) * sizeof(float) <= 64 * 1024)
+        hipLaunchKernelGGL((k_bwd_dy_sout), dim3(nblk(p.M, CVAE_BWD_DY_ROWS)), dim3(256),
+                           (size_t)(m.Co * m.Co + CVAE_BWD_DY_ROWS * m.Co) * sizeof(float), p.st, dout, (const float*)(p.P + p.pl.sout_w),
+                           p.S + p.sl.dyl, p.B, p.Bp, p.T, m.Co, m.Cop);
+    else
+        hipLaunchKernelGGL((k_bwd_dy), dim3(nblk((long)p.M * m.Cop, 256)), dim3(256), 0, p.st, dout, (const float*)(p.TP + p.tl.ybuf),
+                           p.d->has_scale_out ? (const float*)(p.P + p.pl.sout_w) : (const float*)nullptr,
+                           p.d->has_scale_out ? -1 : clamp_dim(clamp_lat_dim), clamp_floor(clamp_lat_dim), p.S + p.sl.dyl, p.B, p.Bp, p.T, m.Co, m.Cop);
+    return 0;
+}
+
+// at most three rows (cvae_train_ll.h): it writes the live rows of dgi / dgh only (instances named as in fwd_ll: KERNEL ORDER)
+hipError_t bwd_ll(const TrainPass& p, int* status) {
+    TrainBwdLLParams q;
+    q.xbuf = p.S + p.sl.llx; q.nonce = (cx().ll_train_launch.fetch_add(1u) & 0xffffu) << 16; q.backoff = p.pn.bwd_backoff;
+    q.wrec_t = p.P + p.pl.wrec_t; q.dovl = p.S + p.sl.dovl; q.tape = p.TP + p.tl.gates; q.hrow = p.TP + p.tl.hrow; q.gmask = p.TP + p.tl.gmask;
+    q.dgi = p.S + p.sl.dgi; q.dgh = p.S + p.sl.dgh; q.B = p.B; q.Bp = p.Bp; q.H = p.m.H; q.T = p.T; q.status = status;
+    const size_t lds = (size_t)(256 * 25 + 8 * 24) * sizeof(float);
+    return cvae_launch_coop(p.B <= 2 ? (p.B == 1 ? k_train_bwd_steps_ll<1> : k_train_bwd_steps_ll<2>) : k_train_bwd_steps_ll<3>, dim3(p.m.H / 4),
+                            dim3(256), lds, p.st, q);
+}
+
+// the row tiles of the pass in launches of pn.bwd_per_launch tiles (0: all in one)
+hipError_t bwd_by_launch(const TrainPass& p, TrainBwdParams q, void (*k)(TrainBwdParams), dim3 g, size_t lds) {
+    const int per = p.pn.bwd_per_launch, nt16 = p.Bp / 16;
+    hipError_t e = hipSuccess;
+    for (int lo = 0; lo < nt16 && e == hipSuccess; lo += per ? per : nt16) {
+        q.tile_lo = lo;
+        q.tile_n = per ? (nt16 - lo < per ? nt16 - lo : per) : 0;
+        e = cvae_launch_coop(k, g, dim3(256), lds, p.st, q);
+    }
+    return e;
+}
+
+// exact operands, 16 units x 16-row tiles per block, zero rows dropped (cvae_train_w3.h)
+hipError_t bwd_w3(const TrainPass& p, TrainBwdParams q) {
+    const Dims& m = p.m; q.wbk = p.P + p.pl.wbw3;
+    const int nl1 = m.H == 1024 ? CVAE_BWDW_NL1 : (opt(OPT_BWD_W3_L1_H64) ? 2 : 0);
+    const size_t lds = (size_t)(4 * 16 * 36) * sizeof(float) + 5120 + (size_t)4 * 6 * w3_gpw(m) * 512 + (size_t)4 * nl1 * 1024;
+    void (*k)(TrainBwdParams) = k_train_bwd_steps_w3<8, 4, CVAE_BWDW_NL1>;        // (named first: KERNEL ORDER, see fwd_ll)
+    if (m.H != 1024) k = nl1 == 2 ? k_train_bwd_steps_w3<1, 2, 2> : k_train_bwd_steps_w3<1, 2, 0>;
+    return bwd_by_launch(p, q, k, dim3((m.H / 16) * p.pn.bwd_rts), lds);
+}
+
+// exact operands as limb triples, 8-unit blocks (cvae_train_x3.h)
+hipError_t bwd_x3(const TrainPass& p, TrainBwdParams q) {
+    const Dims& m = p.m; q.wbk = p.P + p.pl.wbk3;
+    const size_t lds = (size_t)(4 * 16 * 20) * sizeof(float) + 2560 + (size_t)4 * (m.H / 32) * 512;
+    return bwd_by_launch(p, q, m.H == 1024 ? k_train_bwd_steps_x3<32> : k_train_bwd_steps_x3<2>, dim3((m.H / 8) * p.pn.bwd_rts), lds);
+}
+
+// fp16 pairs (cvae_train_bwd.h): the whole pass in one launch
+hipError_t bwd_pair(const TrainPass& p, TrainBwdParams q) {
+    q.wbk = p.P + p.pl.wbk;
+    const size_t lds = (size_t)(4 * 16 * 20) * sizeof(float) + 2048;
+    return cvae_launch_coop(p.m.H == 1024 ? k_train_bwd_steps<32> : k_train_bwd_steps<2>, dim3((p.m.H / 8) * p.pn.bwd_rts), dim3(256), lds, p.st, q);
+}
+
+// The persistent reverse recurrence.  dovl[t*Bp + b][k] = sum_c dyl[.][c] * out_1.w[c][k]: one GEMM for all steps; then the
+// recurrence (one launch, or one per two tiles per block); d loss / d y_t = dyl_t + W_ih[:, C9:]^T dgi_{t+1} is formed with the
+// weight gradients (WgradWork)
+int run_bwd_recurrence(const TrainPass& p) {
+    const Dims& m = p.m; const TScratch& sl = p.sl;
+    gemm_nt(p.st, p.S + sl.dyl, m.Cop, m.Cop, 0, p.P + p.pl.woT, m.Cop, nullptr, p.S + sl.dovl, m.H, p.M, m.H, m.Cop, 0, p.bws);
+    TrainBwdParams q;
+    q.gx = p.S + sl.gx; q.flags = (unsigned*)(p.S + sl.bflags); q.tile_lo = 0; q.tile_n = 0;
+    q.status = cx().status_sink ? cx().status_sink : (int*)(p.S + sl.bflags) + (p.Bp / 16) * (m.H / 8);
+    q.dovl = p.S + sl.dovl; q.tape = p.TP + p.tl.gates; q.hrow = p.TP + p.tl.hrow; q.gmask = p.TP + p.tl.gmask; q.dgi = p.S + sl.dgi;
+    q.dgh = p.S + sl.dgh; q.dhz = p.S + sl.dh; q.B = p.B; q.Bp = p.Bp; q.H = m.H; q.T = p.T; q.ovf = (float)opt(OPT_BWD_OVERFLOW_AT);
+    q.prof = prof_words(p); q.rts = p.pn.bwd_rts; q.xmap = (int)((opt(OPT_TRAIN_XMAP) >> 1) & 1); q.backoff = p.pn.bwd_backoff;
+    if (p.pn.bwd != BWD_LL) {
+        const int need = p.pn.bwd == BWD_PAIR ? TV_PAIR : TV_EXACT, ivb = image_variants(p.P);
+        if (!(ivb & need))
+            return fail(-4, "the train image was prepared without the weight images of the persistent reverse recurrence "
+                            "(cvae_net_prepare_train_v variants %d, needed %d; B=%d, T=%d)", ivb, need, p.B, p.T);
+    }
+    TrainProf tprof(p.st, TPROF_BWD, 0.0);
+    hipError_t e = hipSuccess;
+    switch (p.pn.bwd) {
+    case BWD_LL: e = bwd_ll(p, q.status); break;
+    case BWD_W3: e = bwd_w3(p, q); break;
+    case BWD_X3: e = bwd_x3(p, q); break;
+    default: e = bwd_pair(p, q); break;
+    }
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(-3, "persistent reverse recurrence failed to launch: %s", hipGetErrorString(e));
+    }
+    tprof.end();
+    return 0;
+}
+
+// The reverse recurrence as 2T per-step launches on fp32 products
+int run_bwd_steps(const TrainPass& p) {
+    const Dims& m = p.m; const TScratch& sl = p.sl;
+    const int Bp = p.Bp, nt16 = Bp / 16; const bool old_gemm = opt(OPT_TRAIN_OLD_GEMM) != 0;
+    BwdStepParams bp;
+    bp.dyl = p.S + sl.dyl; bp.dytot = p.S + sl.dytot; bp.dyfb = p.S + sl.dyfb; bp.wo = p.P + p.pl.wo; bp.dh = p.S + sl.dh;
+    bp.tape = p.TP + p.tl.gates; bp.hrow = p.TP + p.tl.hrow; bp.gmask = p.TP + p.tl.gmask; bp.dgi = p.S + sl.dgi; bp.dgh = p.S + sl.dgh;
+    bp.dgic = old_gemm ? nullptr : p.S + sl.dgic; bp.dghc = old_gemm ? nullptr : p.S + sl.dghc;
+    bp.B = p.B; bp.Bp = Bp; bp.H = m.H; bp.Co = m.Co; bp.Cop = m.Cop; bp.part = nullptr; bp.nparts = 0;
+    BwdGemmParams gq;
+    gq.wbp = p.P + p.pl.wbp; gq.part = p.S + sl.bpart; gq.Bp = Bp; gq.H = m.H; gq.Co = m.Co; gq.Cop = m.Cop;
+    const int NRTB = nt16 >= 4 ? 4 : (nt16 >= 2 ? 2 : 1);
+    TrainProf tprof(p.st, TPROF_BWD, 0.0);
+    for (int tt = p.T - 1; tt >= 0; --tt) {
+        bp.t = tt;
+        hipLaunchKernelGGL((k_gru_step_bwd), dim3(nblk(m.H, 256), Bp), dim3(256), m.Cop * sizeof(float), p.st, bp);
+        if (tt > 0 && old_gemm) {
+            // d loss / d h_{t-1} += W_hh^T dgh_t ;  d loss / d y_{t-1} = W_ih[:, C9:]^T dgi_t
+            gemm_ks(p.st, p.S + sl.dgh + (long)tt * Bp * m.H3, m.H3, p.P + p.pl.whhT, m.H3, p.S + sl.dh, m.H, Bp, m.H, m.H3, 1);
+            gemm_ks(p.st, p.S + sl.dgi + (long)tt * Bp * m.H3, m.H3, p.P + p.pl.wyT, m.H3, p.S + sl.dyfb, m.Cop, Bp, m.Co, m.H3, 0);
+        } else if (tt > 0) {
+            // both products as K-split partial sums in one launch; step tt-1 adds them up
+            gq.dgh = p.S + sl.dghc;      // (the chunk-major copy k_gru_step_bwd just wrote)
+            gq.dgi = p.S + sl.dgic;
+            const int KSr = opt(OPT_BWD_KS) >= 1 && opt(OPT_BWD_KS) <= BWD_KS_MAX ? (int)opt(OPT_BWD_KS) : BWD_KS;
+            // a block's BWD_NTN column tiles must lie on one side of the H boundary (it reads dgh OR dgi): any H / 16 with one tile
+            if (m.nch % BWD_NTN)
+                return fail(-1, "k_bwd_step_gemm with %d column tiles per block needs hidden / 16 to be a multiple of it, got hidden %d",
+                            BWD_NTN, m.H);
+            const dim3 g(nblk((m.H + m.Cop) / 16, BWD_NTN), KSr, nblk(nt16, NRTB));
+            const size_t lds = (size_t)4 * BWD_NTN * NRTB * 16 * 20 * sizeof(float);
+            if (NRTB == 4) hipLaunchKernelGGL((k_bwd_step_gemm<4, BWD_NTN>), g, dim3(256), lds, p.st, gq);
+            else if (NRTB == 2) hipLaunchKernelGGL((k_bwd_step_gemm<2, BWD_NTN>), g, dim3(256), lds, p.st, gq);
+            else hipLaunchKernelGGL((k_bwd_step_gemm<1, BWD_NTN>), g, dim3(256), lds, p.st, gq);
+            bp.part = p.S + sl.bpart; bp.nparts = KSr;
+        }
+    }
+    return 0;
+}
+
 // The weight-gradient work of one backward pass that nothing in the same backward reads (see cvae_set_side_stream): launched on
 // the caller's stream, or on the side stream behind an event.
 struct WgradWork {
-    Dims m;
-    TDims t;
-    TTape tl;
-    TScratch sl;
-    const float* TP = nullptr;
-    float* S = nullptr;
-    const void* scratch = nullptr;
+    const TrainPass& p;
     cvae_net_grads g;
-    int M = 0, Bp = 0, acc = 0, T = 0;
+    int acc;
     // persistent reverse recurrence: d loss / d y_t = dyl_t + W_ih[:, C9:]^T dgi_{t+1} is formed here (one GEMM over all steps); only
     // the out_1 weight / bias gradients read it, so it belongs to the work that may run on the side stream
-    const float* wyT = nullptr;
-    int cap = 0;          // tile cap of the GEMMs when they run on the side stream (0: none)
+    const float* wyT;
+    int cap;              // tile cap of the GEMMs when they run on the side stream (0: none)
 };
 
 // out[n] (+)= sum_m A[m*lda + n].  Operand contract: the two-stage kernel reads rows as float4 guarded on their first element, so
@@ -550,30 +939,23 @@ static void colsum_launch(hipStream_t cs, SplitWs ws, const float* A, long lda, 
 // parts: bit 0 = the light work (the dytot GEMM, dW_ih's feedback columns, dW_out, the three bias column sums), bit 1 = the two big
 // contractions (dW_hh, dW_ih's input columns)
 static void launch_wgrad(hipStream_t ws, SplitWs part, const WgradWork& w, int parts = 3) {
-    const Dims& m = w.m;
-    const TDims& t = w.t;
-    const TTape& tl = w.tl;
-    const TScratch& sl = w.sl;
-    const float* TP = w.TP;
-    float* S = w.S;
-    const cvae_net_grads* g = &w.g;
-    const int M = w.M, Bp = w.Bp, acc = w.acc;
+    const TrainPass& p = w.p; const Dims& m = p.m; const TScratch& sl = p.sl;
     if (parts & 2) {
-        gemm_tn(ws, S + sl.dgh, m.H3, TP + tl.hrow, m.H, m.H, 0, g->w_hh, m.H, M, m.H3, m.H, acc, part);
-        gemm_tn(ws, S + sl.dgi, m.H3, TP + tl.xcm, t.C9p, t.C9p, 0, g->w_ih, m.tot, M, m.H3, t.C9, acc, part);
+        gemm_tn(ws, p.S + sl.dgh, m.H3, p.TP + p.tl.hrow, m.H, m.H, 0, w.g.w_hh, m.H, p.M, m.H3, m.H, w.acc, part);
+        gemm_tn(ws, p.S + sl.dgi, m.H3, p.TP + p.tl.xcm, p.t.C9p, p.t.C9p, 0, w.g.w_ih, m.tot, p.M, m.H3, p.t.C9, w.acc, part);
     }
     if (!(parts & 1)) return;
     if (w.wyT) {
-        (void)hipMemcpyAsync(S + sl.dytot, S + sl.dyl, (size_t)M * m.Cop * sizeof(float), hipMemcpyDeviceToDevice, ws);
-        if (w.T > 1)
-            gemm_nt(ws, S + sl.dgi + (long)Bp * m.H3, m.H3, m.H3, 0, w.wyT, m.H3, nullptr, S + sl.dytot, m.Cop, (w.T - 1) * Bp, m.Co, m.H3, 1,
-                    part);
+        (void)hipMemcpyAsync(p.S + sl.dytot, p.S + sl.dyl, (size_t)p.M * m.Cop * sizeof(float), hipMemcpyDeviceToDevice, ws);
+        if (p.T > 1)
+            gemm_nt(ws, p.S + sl.dgi + (long)p.Bp * m.H3, m.H3, m.H3, 0, w.wyT, m.H3, nullptr, p.S + sl.dytot, m.Cop, (p.T - 1) * p.Bp, m.Co, m.H3,
+                    1, part);
     }
-    gemm_tn(ws, S + sl.dgi, m.H3, TP + tl.ybuf, m.Cop, m.Cop, 0, g->w_ih + t.C9, m.tot, M, m.H3, m.Co, acc, part);
-    gemm_tn(ws, S + sl.dytot, m.Cop, TP + tl.orow + (long)Bp * m.H, m.H, m.H, 0, g->out_w, m.H, M, m.Co, m.H, acc, part);
-    colsum_launch(ws, part, S + sl.dgi, m.H3, g->b_ih, M, m.H3, acc);
-    colsum_launch(ws, part, S + sl.dgh, m.H3, g->b_hh, M, m.H3, acc);
-    colsum_launch(ws, part, S + sl.dytot, m.Cop, g->out_b, M, m.Co, acc);
+    gemm_tn(ws, p.S + sl.dgi, m.H3, p.TP + p.tl.ybuf, m.Cop, m.Cop, 0, w.g.w_ih + p.t.C9, m.tot, p.M, m.H3, m.Co, w.acc, part);
+    gemm_tn(ws, p.S + sl.dytot, m.Cop, p.TP + p.tl.orow + (long)p.Bp * m.H, m.H, m.H, 0, w.g.out_w, m.H, p.M, m.Co, m.H, w.acc, part);
+    colsum_launch(ws, part, p.S + sl.dgi, m.H3, w.g.b_ih, p.M, m.H3, w.acc);
+    colsum_launch(ws, part, p.S + sl.dgh, m.H3, w.g.b_hh, p.M, m.H3, w.acc);
+    colsum_launch(ws, part, p.S + sl.dytot, m.Cop, w.g.out_b, p.M, m.Co, w.acc);
 }
 
 // enqueue the work on the side stream, ordered after everything `st` has been given so far
@@ -582,10 +964,56 @@ static int launch_wgrad_side(hipStream_t st, const WgradWork& w, int parts = 3) 
     CVAE_HIP_OK(hipEventRecord(cx().side_ready, st));
     CVAE_HIP_OK(hipStreamWaitEvent(cx().side, cx().side_ready, 0));
     cx().side_cap = w.cap;
-    launch_wgrad(cx().side, SplitWs{w.S + w.sl.gpart2, (unsigned*)(w.S + w.sl.bcnt2)}, w, parts);
-    CVAE_HIP_OK(hipEventRecord(side_event_for(w.scratch), cx().side));
+    launch_wgrad(cx().side, SplitWs{w.p.S + w.p.sl.gpart2, (unsigned*)(w.p.S + w.p.sl.bcnt2)}, w, parts);
+    CVAE_HIP_OK(hipEventRecord(side_event_for(w.p.S), cx().side));
     if (!cx().side_last) CVAE_HIP_OK(hipEventCreateWithFlags(&cx().side_last, hipEventDisableTiming));
     CVAE_HIP_OK(hipEventRecord(cx().side_last, cx().side));
+    return 0;
+}
+
+// Input side: W_ih[:, :C9]^T, conv_drop, conv1^T, conv0^T, scale_in^T: the chain that produces dx (the next backward pass of the
+// caller's graph waits for it).  conv_drop's gradient in the epilogue; dc1's padding frames / columns stay zero from the scratch
+// memset.  dc1 / dc0: the gradients at the outputs of conv1 / conv0, behind the padding frames of dc1p / dc0p.
+inline float* bwd_dc1(const TrainPass& p) { return p.S + p.sl.dc1p + (long)(p.m.R - p.m.ks) * p.Bp * p.t.C9p; }
+inline float* bwd_dc0(const TrainPass& p) { return p.S + p.sl.dc0p + (long)(p.m.ks - 1) * p.Bp * p.t.C3p; }
+void run_input_chain(const TrainPass& p, float* dx) {
+    const Dims& m = p.m; const TDims& t = p.t; const TScratch& sl = p.sl; const int Bp = p.Bp;
+    gemm_nt(p.st, p.S + sl.dgi, m.H3, m.H3, 0, p.P + p.pl.wixT, m.H3, nullptr, bwd_dc1(p), t.C9p, p.M, t.C9, m.H3, 0, p.bws,
+            EpiMask{p.TP + p.tl.cmask, p.B, Bp, p.T});
+    gemm_nt(p.st, p.S + sl.dc1p + (long)m.ks * (m.ks - 1) * Bp * t.C9p, t.C9p, t.C9p, -(long)m.ks * Bp * t.C9p, p.P + p.pl.w1t,
+            (long)m.ks * t.C9p, nullptr, bwd_dc0(p), t.C3p, t.F0 * Bp, t.C3, m.ks * t.C9p, 0, p.bws);
+    if (!dx) return;
+    gemm_nt(p.st, p.S + sl.dc0p + (long)(m.ks - 1) * Bp * t.C3p, t.C3p, t.C3p, -(long)Bp * t.C3p, p.P + p.pl.w0t, (long)m.ks * t.C3p,
+            nullptr, p.S + sl.dxn, t.Cq, t.Tp * Bp, t.Cq, m.ks * t.C3p, 0, p.bws);
+    // (scale_in^T is folded into w0t at prepare time: this launch only gathers time-major -> [B][T][C])
+    hipLaunchKernelGGL((k_scale_in_bwd), dim3(nblk((long)p.B * p.T * m.C, 256)), dim3(256), 0, p.st, (const float*)(p.S + sl.dxn),
+                       (const float*)nullptr, dx, p.B, Bp, p.T, m.C, t.Cq, m.pad);
+}
+
+// The two convolution weight gradients and their bias sums feed nothing in this backward: with a side stream (overlap) they run
+// there, behind an event recorded after the input chain
+int run_conv_wgrad(const TrainPass& p, const cvae_net_grads* g, int acc, bool overlap) {
+    const Dims& m = p.m; const TDims& t = p.t;
+    float *const dc1 = bwd_dc1(p), *const dc0 = bwd_dc0(p), *const tmpw = p.S + p.sl.tmpw;
+    hipStream_t cs = p.st; SplitWs part = p.bws;
+    if (overlap) {
+        CVAE_HIP_OK(hipEventRecord(cx().side_ready, p.st));
+        CVAE_HIP_OK(hipStreamWaitEvent(cx().side, cx().side_ready, 0));
+        cs = cx().side;
+        part = SplitWs{p.S + p.sl.gpart2, (unsigned*)(p.S + p.sl.bcnt2)};
+    }
+    gemm_tn(cs, dc1, t.C9p, p.TP + p.tl.c0, t.C3p, t.C3p, (long)m.ks * p.Bp * t.C3p, tmpw, t.K1, p.M, t.C9, t.K1, 0, part);
+    hipLaunchKernelGGL((k_unpack_dw), dim3(nblk((long)t.C9 * t.C3 * m.ks, 256)), dim3(256), 0, cs, (const float*)tmpw, (long)t.K1, t.C3p,
+                       g->conv1_w, t.C9, t.C3, m.ks, acc);
+    colsum_launch(cs, part, dc1, t.C9p, g->conv1_b, p.M, t.C9, acc);
+    gemm_tn(cs, dc0, t.C3p, p.TP + p.tl.xnp, t.Cq, t.Cq, (long)p.Bp * t.Cq, tmpw, t.K0, t.F0 * p.Bp, t.C3, t.K0, 0, part);
+    hipLaunchKernelGGL((k_unpack_dw), dim3(nblk((long)t.C3 * m.C * m.ks, 256)), dim3(256), 0, cs, (const float*)tmpw, (long)t.K0, t.Cq,
+                       g->conv0_w, t.C3, m.C, m.ks, acc);
+    colsum_launch(cs, part, dc0, t.C3p, g->conv0_b, t.F0 * p.Bp, t.C3, acc);
+    if (overlap) {
+        CVAE_HIP_OK(hipEventRecord(side_event_for(p.S), cx().side));     // (re-recorded: now also behind this work)
+        CVAE_HIP_OK(hipEventRecord(cx().side_last, cx().side));
+    }
     return 0;
 }
 
@@ -733,220 +1161,23 @@ int cvae_gru_rnn_forward_train(cvae_ctx* ctx, const cvae_net_desc* d, const void
                                float p_drop, float* trj_out, float* y_last, float* h_last, void* tape, size_t tape_bytes,
                                void* scratch, size_t scratch_bytes, void* stream) {
     CVAE_ENTER(ctx);
-    Dims m;
-    if (int rc = make_train_dims(d, &m)) return rc;
+    TrainPass p;
+    if (int rc = make_train_dims(d, &p.m)) return rc;
     if (B < 1 || T < 1) return fail(-1, "empty batch: B=%d T=%d", B, T);
     if (!image || !x || !y_in || !trj_out || !tape || !scratch) return fail(-1, "null argument");
     if (!(p_drop >= 0.0f && p_drop < 1.0f)) return fail(-1, "dropout probability %f outside [0,1)", (double)p_drop);
-    if (tape_bytes < cvae_train_tape_bytes(ctx, d, B, T)) return fail(-2, "tape too small");
-    if (scratch_bytes < cvae_train_scratch_bytes(ctx, d, B, T)) return fail(-2, "scratch too small");
-    hipStream_t st = (hipStream_t)stream;
-    const TDims t = make_tdims(m, T);
-    const TPrep pl = tprep_layout(m, d->has_scale_in != 0, d->has_scale_out != 0);
-    const TrainPlan pn = plan_train_pass(m, B, T);
-    const TTape tl = ttape_layout(m, B, T, pn.Bp);
-    const TScratch sl = tscratch_layout(m, T, pn.Bp);
-    const float* P = (const float*)image;
-    float* TP = (float*)tape;
-    float* S = (float*)scratch;
-    const int Bp = tl.Bp;
-    const long mtot = (long)(T + 1) * Bp;
+    open_train_pass(p, d, image, B, T, tape, scratch, stream);
+    if (tape_bytes < (size_t)p.tl.total * sizeof(float)) return fail(-2, "tape too small");
+    if (scratch_bytes < (size_t)p.sl.total * sizeof(float)) return fail(-2, "scratch too small");
     // zero: input padding frames / batch padding rows / K padding columns all rely on it.  The state copies and the gate tape (90 %
     // of the tape's 170 MB at B = 64) are written in full by the persistent recurrences and need no memset then.
-    CVAE_HIP_OK(hipMemsetAsync(TP, 0, (size_t)(pn.fwd_full_writes ? tl.zero_end : tl.total) * sizeof(float), st));
-    // (the flags / status words of the recurrence and the arrival counters of this pass's split GEMMs are cleared by the prologue)
-    const SplitWs fws{S + sl.gpart, (unsigned*)(S + sl.fcnt)};
-    // dropout masks: supplied (parity tests inject the reference's) or drawn with Philox; the tape keeps them for backward
-    const long mparts = cx().draw_parts > 1 && B % cx().draw_parts == 0 ? cx().draw_parts : 1;
-    // With a side stream set, the mask of the recurrence's feedback operand (gmask, two thirds of the draws; first read by the
-    // mask-bit kernel behind the three front-end GEMMs) is drawn THERE, beside the prologue and those GEMMs: 25-40 us less on the
-    // critical path of every pass of 64 rows (the masks depend on nothing but the seed)
-    bool gmask_on_side = false;
-    if (!cmask && !gmask && cx().side && opt(OPT_MASKS_ON_SIDE) && (long)T * B * m.H >= (1L << 20)) {
-        if (!cx().mask_fork) CVAE_HIP_OK(hipEventCreateWithFlags(&cx().mask_fork, hipEventDisableTiming));
-        if (!cx().mask_join) CVAE_HIP_OK(hipEventCreateWithFlags(&cx().mask_join, hipEventDisableTiming));
-        CVAE_HIP_OK(hipEventRecord(cx().mask_fork, st));                 // (behind the tape's memset)
-        CVAE_HIP_OK(hipStreamWaitEvent(cx().side, cx().mask_fork, 0));
-        hipLaunchKernelGGL((k_mask_gen), dim3(nblk((long)T * B * m.H, 256)), dim3(256), 0, cx().side, TP + tl.gmask, (long)T * B * m.H, seed,
-                           (uint64_t)2, p_drop, (long)B, (long)m.H, cx().draw_rows > 0 ? cx().draw_rows : (long)B / mparts, cx().draw_row0, mparts);
-        CVAE_HIP_OK(hipEventRecord(cx().mask_join, cx().side));
-        hipLaunchKernelGGL((k_mask_gen), dim3(nblk((long)B * T * t.C9, 256)), dim3(256), 0, st, TP + tl.cmask, (long)B * T * t.C9, seed, (uint64_t)1, p_drop,
-                           (long)B, (long)T * t.C9, cx().draw_rows > 0 ? cx().draw_rows : (long)B / mparts, cx().draw_row0, mparts);
-        gmask_on_side = true;
-    } else if (!cmask && !gmask)
-        hipLaunchKernelGGL((k_mask_gen2), dim3(nblk((long)B * T * t.C9 + (long)T * B * m.H, 256)), dim3(256), 0, st, TP + tl.cmask,
-                           (long)B * T * t.C9, (long)T * t.C9, TP + tl.gmask, (long)T * B * m.H, (long)m.H, seed, p_drop, (long)B,
-                           cx().draw_rows > 0 ? cx().draw_rows : (long)B / mparts, cx().draw_row0, mparts);
-    else {
-    if (cmask) CVAE_HIP_OK(hipMemcpyAsync(TP + tl.cmask, cmask, (size_t)B * T * t.C9 * sizeof(float), hipMemcpyDeviceToDevice, st));
-    else hipLaunchKernelGGL((k_mask_gen), dim3(nblk((long)B * T * t.C9, 256)), dim3(256), 0, st, TP + tl.cmask, (long)B * T * t.C9, seed, (uint64_t)1, p_drop,
-                            (long)B, (long)T * t.C9, cx().draw_rows > 0 ? cx().draw_rows : (long)B / mparts, cx().draw_row0, mparts);
-    if (gmask) CVAE_HIP_OK(hipMemcpyAsync(TP + tl.gmask, gmask, (size_t)T * B * m.H * sizeof(float), hipMemcpyDeviceToDevice, st));
-    else hipLaunchKernelGGL((k_mask_gen), dim3(nblk((long)T * B * m.H, 256)), dim3(256), 0, st, TP + tl.gmask, (long)T * B * m.H, seed, (uint64_t)2, p_drop,
-                            (long)B, (long)m.H, cx().draw_rows > 0 ? cx().draw_rows : (long)B / mparts, cx().draw_row0, mparts);
-    }
-
-    TrainProParams pp;
-    pp.x = x; pp.y_in = y_in; pp.h_in = h_in;
-    pp.sin_w = d->has_scale_in ? P + pl.sin_w : nullptr;
-    pp.sin_b = d->has_scale_in ? P + pl.sin_b : nullptr;
-    pp.bo = P + pl.bo;
-    pp.B = B; pp.Bp = Bp; pp.T = T; pp.C = m.C; pp.Cq = t.Cq; pp.pad = m.pad; pp.Co = m.Co; pp.Cop = m.Cop; pp.H = m.H;
-    pp.mtot = mtot;
-    pp.xnp = TP + tl.xnp; pp.hbuf = S + sl.hbuf; pp.obuf = S + sl.obuf; pp.hrow = TP + tl.hrow; pp.orow = TP + tl.orow;
-    pp.ybuf = TP + tl.ybuf; pp.dy = S + sl.dy;
-    pp.nA = B * T;
-    pp.nH = (int)nblk((long)Bp * m.H, 1024);
-    pp.nY = (int)nblk((long)Bp * m.Cop, 64);
-    pp.zero_ptr = S + sl.tflags;
-    pp.zero_n = sl.fcnt + GEMM_CNT - sl.tflags;
-    hipLaunchKernelGGL((k_train_prologue), dim3(pp.nA + pp.nH + pp.nY + nblk(pp.zero_n, 64)), dim3(64), m.C * sizeof(float), st, pp);
-
-    // conv0, conv1 (+ conv_drop), input-gate GEMM: time-major segmented-row GEMMs
-    gemm_nt(st, TP + tl.xnp, t.Cq, t.Cq, (long)Bp * t.Cq, P + pl.w0r, t.K0, P + pl.b0, TP + tl.c0, t.C3p, t.F0 * Bp, t.C3, t.K0, 0, fws);
-    // conv1 with conv_drop in its epilogue (the K padding columns of xcm stay zero from the tape's memset)
-    gemm_nt(st, TP + tl.c0, t.C3p, t.C3p, (long)m.ks * Bp * t.C3p, P + pl.w1r, t.K1, P + pl.b1, TP + tl.xcm, t.C9p, T * Bp, t.C9, t.K1, 0,
-            fws, EpiMask{TP + tl.cmask, B, Bp, T});
-    gemm_nt(st, TP + tl.xcm, t.C9p, t.C9p, 0, P + pl.wix, t.C9p, P + pl.cfold_t, S + sl.gi, m.H3, T * Bp, m.H3, t.C9p, 0, fws);
-
-    if (gmask_on_side) CVAE_HIP_OK(hipStreamWaitEvent(st, cx().mask_join, 0));
-    {   // ---- the T dependent steps, in the form the plan chose (bracketed by HIP events with the option train_profile)
-    TrainProf tprof(st, TPROF_FWD, 0.0);
-    const int iv = image_variants(image);
-    if (pn.fwd_need & ~iv)
-        return fail(-4, "the train image was prepared without the exact-operand kernels' weight images (cvae_net_prepare_train_v "
-                        "variants %d) and this pass (B=%d, T=%d) needs them", iv, B, T);
-    unsigned* tfl = (unsigned*)(S + sl.tflags);
-    int* stat = cx().status_sink ? cx().status_sink : (int*)(tfl + (size_t)(Bp / 16) * (m.H / 8));
-    long long* prof = opt(OPT_TRAIN_PROF) ? (long long*)(S + sl.tprof) : nullptr;
-    const int xmap = (int)(opt(OPT_TRAIN_XMAP) & 1), c32w = m.H == 1024 ? 8 : 1;
-    hipError_t e = hipSuccess;
-    const char* what = nullptr;
-    // the 16-row-tile exact forms (16- and 8-unit blocks): exchanged h in limb triples, the feedback mask as bits
-    auto fwd3h = [&](const float* w3) {
-        hipLaunchKernelGGL((k_train_x3h_slot0), dim3(nblk((long)Bp * m.H, 256)), dim3(256), 0, st, (const float*)(TP + tl.hrow),
-                           S + sl.hx3, Bp, m.H);
-        hipLaunchKernelGGL((k_train_x3h_maskbits), dim3(nblk((long)T * (Bp / 16) * 2048, 256)), dim3(256), 0, st,
-                           (const float*)(TP + tl.gmask), (unsigned char*)(S + sl.ox3), T, B, Bp, m.H, c32w);
-        TrainFwd3hParams q;
-        q.hx = S + sl.hx3; q.mbits = (const unsigned char*)(S + sl.ox3); q.w3 = w3; q.gi = S + sl.gi; q.bhn = P + pl.bhn;
-        q.gmask = TP + tl.gmask; q.tape = TP + tl.gates; q.hrow = TP + tl.hrow; q.orow = TP + tl.orow; q.wyT = P + pl.wyT;
-        q.dy = S + sl.dy; q.Co = m.Co; q.B = B; q.Bp = Bp; q.H = m.H; q.T = T; q.rts = pn.fwd_rts; q.flags = tfl; q.status = stat;
-        q.backoff = pn.fwd_backoff; q.xmap = xmap; q.prof = prof;
-        return q;
-    };
-    FwdForm form = pn.fwd;
-    if ((form == FWD_PAIR && !(iv & TV_PAIR)) || (form == FWD_FP32 && !(iv & TV_FP32))) form = FWD_STEPS;   // (image without them)
-    switch (form) {
-    case FWD_LL: {           // at most three rows: fp32 FMAs, one word per unit and row exchanged (cvae_train_ll.h)
-        TrainFwdLLParams q;
-        q.xbuf = S + sl.llx;
-        q.nonce = (cx().ll_train_launch.fetch_add(1u) & 0xffffu) << 16;
-        q.backoff = pn.fwd_backoff;
-        q.wrec_t = P + pl.wrec_t; q.gi = S + sl.gi; q.bhn = P + pl.bhn; q.gmask = TP + tl.gmask; q.tape = TP + tl.gates;
-        q.hrow = TP + tl.hrow; q.orow = TP + tl.orow; q.wyT = P + pl.wyT; q.dy = S + sl.dy; q.Co = m.Co; q.B = B; q.Bp = Bp;
-        q.H = m.H; q.T = T;
-        q.status = cx().status_sink ? cx().status_sink : (int*)tfl;
-        const dim3 gl(m.H / 4);
-        const size_t ldsl = (size_t)(2 * 64 * 49 + 4 * 48) * sizeof(float);
-        e = B == 1 ? cvae_launch_coop(k_train_fwd_steps_ll<1>, gl, dim3(256), ldsl, st, q)
-          : B == 2 ? cvae_launch_coop(k_train_fwd_steps_ll<2>, gl, dim3(256), ldsl, st, q)
-                   : cvae_launch_coop(k_train_fwd_steps_ll<3>, gl, dim3(256), ldsl, st, q);
-        what = "small-batch forward training recurrence";
-        break;
-    }
-    case FWD_W3: {           // exact operands, 16-unit blocks with the zero column tiles of [W_hh | F] dropped (cvae_train_w3.h)
-        const TrainFwd3hParams q = fwd3h(P + pl.wfw3);
-        const int nl1 = m.H == 1024 ? CVAE_FWDW_NL1 : (opt(OPT_BWD_W3_L1_H64) ? 2 : 0);
-        const size_t lds = (size_t)(4 * 16 * 68) * sizeof(float) + 1280 + (size_t)4 * 6 * w3_gpw(m) * 512 + (size_t)4 * nl1 * 1024;
-        const dim3 g((m.H / 16) * pn.fwd_rts);
-        e = m.H == 1024 ? cvae_launch_coop(k_train_fwd_steps_w3<8, 4, CVAE_FWDW_NL1>, g, dim3(256), lds, st, q)
-          : nl1 == 2    ? cvae_launch_coop(k_train_fwd_steps_w3<1, 2, 2>, g, dim3(256), lds, st, q)
-                        : cvae_launch_coop(k_train_fwd_steps_w3<1, 2, 0>, g, dim3(256), lds, st, q);
-        what = "exact-operand forward training recurrence (16-unit blocks)";
-        break;
-    }
-    case FWD_X3: {           // exact operands as fp16 triples, 8-unit x 32-row-tile blocks (cvae_train_x3.h)
-        const int kpw = x3_kpw(m);
-        hipLaunchKernelGGL((k_train_x3_slot0), dim3(nblk((long)Bp * m.H, 256)), dim3(256), 0, st, (const float*)(TP + tl.hrow),
-                           S + sl.hx3, mtot, Bp, m.H);
-        hipLaunchKernelGGL((k_train_x3_maskbits), dim3(nblk((long)T * (Bp / 32) * 4096, 256)), dim3(256), 0, st,
-                           (const float*)(TP + tl.gmask), (unsigned char*)(S + sl.ox3), T, B, Bp, m.H, kpw);
-        TrainFwd3Params q;
-        q.hx = S + sl.hx3; q.mbits = (const unsigned char*)(S + sl.ox3); q.mtot = mtot; q.w3 = P + pl.w3f; q.gi = S + sl.gi; q.bhn = P + pl.bhn;
-        q.gmask = TP + tl.gmask; q.tape = TP + tl.gates; q.hrow = TP + tl.hrow; q.orow = TP + tl.orow; q.wyT = P + pl.wyT;
-        q.dy = S + sl.dy; q.Co = m.Co; q.B = B; q.Bp = Bp; q.H = m.H; q.T = T; q.rts = pn.fwd_rts; q.flags = tfl; q.status = stat;
-        q.xmap = xmap; q.prof = prof;
-        const size_t lds = (size_t)(4 * 32 * 40 + 6 * 256) * sizeof(float) + 1280 + (size_t)4 * 2 * kpw * 1024;
-        const dim3 g((m.H / 8) * pn.fwd_rts);
-        e = m.H == 1024 ? cvae_launch_coop(k_train_fwd_steps_x3<16>, g, dim3(256), lds, st, q)
-                        : cvae_launch_coop(k_train_fwd_steps_x3<1>, g, dim3(256), lds, st, q);
-        what = "exact-operand forward training recurrence";
-        break;
-    }
-    case FWD_X3H: {          // the same with 16-row tiles
-        const TrainFwd3hParams q = fwd3h(P + pl.w3h);
-        const size_t lds = (size_t)(4 * 16 * 36) * sizeof(float) + 640 + (size_t)(m.H == 1024 ? 4 : 2) * 4 * c32w * 1024;
-        const dim3 g((m.H / 8) * pn.fwd_rts);
-        e = m.H == 1024 ? cvae_launch_coop(k_train_fwd_steps_x3h<8, 4>, g, dim3(256), lds, st, q)
-                        : cvae_launch_coop(k_train_fwd_steps_x3h<1, 2>, g, dim3(256), lds, st, q);
-        what = "exact-operand forward training recurrence (16-row tiles)";
-        break;
-    }
-    case FWD_PAIR:
-    case FWD_FP32: {         // the matrix product on fp16 pairs (same form as the eval kernel) or on the fp32-input MFMA
-        TrainFwdParams q;
-        q.hbuf = S + sl.hbuf; q.obuf = S + sl.obuf; q.mtot = mtot; q.hrow = TP + tl.hrow; q.orow = TP + tl.orow;
-        q.wrec_t8 = form == FWD_PAIR ? P + pl.wrec_t8h : P + pl.wrec_t8; q.gi = S + sl.gi; q.bhn = P + pl.bhn; q.gmask = TP + tl.gmask;
-        q.tape = TP + tl.gates; q.wyT = P + pl.wyT; q.dy = S + sl.dy; q.Co = m.Co; q.B = B; q.Bp = Bp; q.H = m.H; q.T = T;
-        q.rts = pn.fwd_rts; q.flags = tfl; q.status = stat; q.prof = prof; q.backoff = pn.fwd_backoff;
-        const size_t lds = (4 * 16 * 36 + 2 * 128) * sizeof(float);
-        const dim3 g((m.H / 8) * pn.fwd_rts);
-        if (form == FWD_PAIR)
-            e = m.H == 1024 ? cvae_launch_coop(k_train_fwd_steps_h<16>, g, dim3(256), lds, st, q)
-                            : cvae_launch_coop(k_train_fwd_steps_h<1>, g, dim3(256), lds, st, q);
-        else
-            e = m.H == 1024 ? cvae_launch_coop(k_train_fwd_steps<32>, g, dim3(256), lds, st, q)
-                            : cvae_launch_coop(k_train_fwd_steps<2>, g, dim3(256), lds, st, q);
-        if (e == hipSuccess) break;
-        (void)hipGetLastError();     // (a grid that does not fit: the per-step launches)
-        e = hipSuccess;
-    }
-    [[fallthrough]];
-    case FWD_STEPS: {
-        TrainStepParams sp;
-        sp.hbuf = S + sl.hbuf; sp.obuf = S + sl.obuf; sp.mtot = mtot; sp.hrow = TP + tl.hrow; sp.orow = TP + tl.orow;
-        sp.wrec_t = P + pl.wrec_t; sp.gi = S + sl.gi; sp.bhn = P + pl.bhn; sp.gmask = TP + tl.gmask; sp.tape = TP + tl.gates;
-        sp.wyT = P + pl.wyT; sp.dy = S + sl.dy; sp.Co = m.Co; sp.B = B; sp.Bp = Bp; sp.H = m.H;
-        for (int tt = 0; tt < T; ++tt) {
-            sp.t = tt;
-            if (pn.fwd_col_tiles == 1)
-                hipLaunchKernelGGL((k_gru_step_train<1>), dim3(m.H / 4), dim3(256), 4 * 64 * 20 * sizeof(float), st, sp);
-            else if (Bp >= 128)
-                hipLaunchKernelGGL((k_gru_step_train<2, 8>), dim3(m.H / 8), dim3(256), 2 * 4 * 128 * 20 * sizeof(float), st, sp);
-            else
-                hipLaunchKernelGGL((k_gru_step_train<2>), dim3(m.H / 8), dim3(256), 2 * 4 * 64 * 20 * sizeof(float), st, sp);
-        }
-        break;
-    }
-    }
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(-3, "%s failed to launch: %s", what, hipGetErrorString(e));
-    }
-    }
-    // raw projection of the dropped states, then scale_out / clamp
-    gemm_nt(st, TP + tl.orow + (long)Bp * m.H, m.H, m.H, 0, P + pl.wo, m.H, P + pl.bo, TP + tl.ybuf + (long)Bp * m.Cop, m.Cop,
-            T * Bp, m.Co, m.H, 0, fws);
-    TrainEpiParams ep;
-    ep.ybuf = TP + tl.ybuf; ep.hrow = TP + tl.hrow;
-    ep.sout_w = d->has_scale_out ? P + pl.sout_w : nullptr;
-    ep.sout_b = d->has_scale_out ? P + pl.sout_b : nullptr;
-    ep.clamp_from = d->has_scale_out ? -1 : clamp_dim(clamp_lat_dim);
-    ep.clamp_min = clamp_floor(clamp_lat_dim);
-    ep.B = B; ep.Bp = Bp; ep.T = T; ep.Co = m.Co; ep.Cop = m.Cop; ep.H = m.H;
-    ep.trj_out = trj_out; ep.y_last = y_last; ep.h_last = h_last;
-    hipLaunchKernelGGL((k_train_epilogue), dim3(B * T), dim3(64), m.Co * sizeof(float), st, ep);
+    CVAE_HIP_OK(hipMemsetAsync(p.TP, 0, (size_t)(p.pn.fwd_full_writes ? p.tl.zero_end : p.tl.total) * sizeof(float), p.st));
+    const int join = draw_train_masks(p, cmask, gmask, seed, p_drop);
+    if (join < 0) return join;
+    run_train_prologue(p, x, y_in, h_in);
+    run_train_front_end(p);
+    if (int rc = run_fwd_recurrence(p, join != 0)) return rc;
+    run_train_projection(p, clamp_lat_dim, trj_out, y_last, h_last);
     CVAE_HIP_OK(hipGetLastError());
     return 0;
 }
@@ -970,230 +1201,39 @@ int cvae_gru_rnn_backward(cvae_ctx* ctx, const cvae_net_desc* d, const void* ima
                           const void* tape, void* scratch, size_t scratch_bytes, float* dx, const cvae_net_grads* g,
                           int accumulate, void* stream) {
     CVAE_ENTER(ctx);
-    Dims m;
-    if (int rc = make_train_dims(d, &m)) return rc;
+    TrainPass p;
+    if (int rc = make_train_dims(d, &p.m)) return rc;
     if (!image || !dout || !tape || !scratch || !g) return fail(-1, "null argument");
     if (!g->conv0_w || !g->conv0_b || !g->conv1_w || !g->conv1_b || !g->w_ih || !g->w_hh || !g->b_ih || !g->b_hh || !g->out_w ||
         !g->out_b)
         return fail(-1, "missing gradient pointer");
-    if (scratch_bytes < cvae_train_scratch_bytes(ctx, d, B, T)) return fail(-2, "scratch too small");
-    hipStream_t st = (hipStream_t)stream;
-    const TDims t = make_tdims(m, T);
-    const TPrep pl = tprep_layout(m, d->has_scale_in != 0, d->has_scale_out != 0);
-    const TrainPlan pn = plan_train_pass(m, B, T);
-    const TTape tl = ttape_layout(m, B, T, pn.Bp);
-    const TScratch sl = tscratch_layout(m, T, pn.Bp);
-    const float* P = (const float*)image;
-    const float* TP = (const float*)tape;
-    float* S = (float*)scratch;
-    const int Bp = tl.Bp, M = T * Bp, acc = accumulate ? 1 : 0;
-    const SplitWs bws{S + sl.gpart, (unsigned*)(S + sl.bcnt)};     // (the counters lie in the area zeroed below)
+    open_train_pass(p, d, image, B, T, const_cast<void*>(tape), scratch, stream);
+    if (scratch_bytes < cvae_train_scratch_bytes(ctx, d, B, T)) return fail(-2, "scratch too small");      // (0 for B or T < 1, as ever)
+    const int acc = accumulate ? 1 : 0;
     const bool overlap = cx().side != nullptr && accumulate != 0;    // (fresh gradient buffers are read by the caller right away)
-    if (cx().side) {
-        // side-stream GEMMs of an earlier backward may still read this scratch (dgi / dgh / gpart2): wait for the event recorded
-        // behind them; a scratch the table no longer knows (evicted) waits for everything the side stream has been given
-        bool known = false;
-        for (int i = 0; i < 8; ++i)
-            if (cx().side_done[i].scratch == scratch && cx().side_done[i].ev) {
-                CVAE_HIP_OK(hipStreamWaitEvent(st, cx().side_done[i].ev, 0));
-                known = true;
-            }
-        if (!known && cx().side_last) CVAE_HIP_OK(hipStreamWaitEvent(st, cx().side_last, 0));
-    }
-    // everything from dyl on is backward scratch: zero it (padding frames of dc1p / dc0p, dh, dyfb, dead rows); the gate gradients
-    // dgi / dgh right in front of dyl as well, unless the reverse recurrence writes every row of them
-    const long zero_from = pn.bwd_writes_gates ? sl.dyl : sl.dgi;
-    CVAE_HIP_OK(hipMemsetAsync(S + zero_from, 0, (size_t)(sl.total - zero_from) * sizeof(float), st));
-    // (the LDS form holds scale_out^T whole: beyond ~120 outputs it no longer fits 64 KB and the plain kernel takes over)
-    if (d->has_scale_out && (size_t)(m.Co * m.Co + CVAE_BWD_DY_ROWS * m.Co) * sizeof(float) <= 64 * 1024)
-        hipLaunchKernelGGL((k_bwd_dy_sout), dim3(nblk(M, CVAE_BWD_DY_ROWS)), dim3(256),
-                           (size_t)(m.Co * m.Co + CVAE_BWD_DY_ROWS * m.Co) * sizeof(float), st, dout, (const float*)(P + pl.sout_w),
-                           S + sl.dyl, B, Bp, T, m.Co, m.Cop);
-    else
-        hipLaunchKernelGGL((k_bwd_dy), dim3(nblk((long)M * m.Cop, 256)), dim3(256), 0, st, dout, TP + tl.ybuf,
-                           d->has_scale_out ? (const float*)(P + pl.sout_w) : (const float*)nullptr,
-                           d->has_scale_out ? -1 : clamp_dim(clamp_lat_dim), clamp_floor(clamp_lat_dim), S + sl.dyl, B, Bp, T, m.Co, m.Cop);
-    const int NB = m.H / 8, nt16 = Bp / 16;
-    if (pn.bwd != BWD_STEPS) {
-        // dovl[t*Bp + b][k] = sum_c dyl[.][c] * out_1.w[c][k]: one GEMM for all steps; then the reverse recurrence (one launch, or one
-        // per two tiles per block); d loss / d y_t = dyl_t + W_ih[:, C9:]^T dgi_{t+1} is formed with the weight gradients (WgradWork)
-        gemm_nt(st, S + sl.dyl, m.Cop, m.Cop, 0, P + pl.woT, m.Cop, nullptr, S + sl.dovl, m.H, M, m.H, m.Cop, 0, bws);
-        TrainBwdParams q;
-        q.gx = S + sl.gx; q.flags = (unsigned*)(S + sl.bflags);
-        q.status = cx().status_sink ? cx().status_sink : (int*)(S + sl.bflags) + nt16 * NB;
-        q.dovl = S + sl.dovl; q.tape = TP + tl.gates; q.hrow = TP + tl.hrow; q.gmask = TP + tl.gmask; q.dgi = S + sl.dgi;
-        q.dgh = S + sl.dgh; q.dhz = S + sl.dh; q.B = B; q.Bp = Bp; q.H = m.H; q.T = T; q.ovf = (float)opt(OPT_BWD_OVERFLOW_AT);
-        q.prof = opt(OPT_TRAIN_PROF) ? (long long*)(S + sl.tprof) : nullptr;
-        q.rts = pn.bwd_rts; q.xmap = (int)((opt(OPT_TRAIN_XMAP) >> 1) & 1); q.backoff = pn.bwd_backoff;
-        q.tile_lo = 0; q.tile_n = 0;
-        if (pn.bwd != BWD_LL) {
-            const int need = pn.bwd == BWD_PAIR ? TV_PAIR : TV_EXACT, ivb = image_variants(image);
-            if (!(ivb & need))
-                return fail(-4, "the train image was prepared without the weight images of the persistent reverse recurrence "
-                                "(cvae_net_prepare_train_v variants %d, needed %d; B=%d, T=%d)", ivb, need, B, T);
-        }
-        TrainProf tprof(st, TPROF_BWD, 0.0);
-        hipError_t e = hipSuccess;
-        // the row tiles of the pass in launches of pn.bwd_per_launch tiles (0: all in one)
-        auto by_launch = [&](auto launch) {
-            const int per = pn.bwd_per_launch;
-            for (int lo = 0; lo < nt16 && e == hipSuccess; lo += per ? per : nt16) {
-                q.tile_lo = lo;
-                q.tile_n = per ? (nt16 - lo < per ? nt16 - lo : per) : 0;
-                e = launch();
-            }
-        };
-        switch (pn.bwd) {
-        case BWD_LL: {       // at most three rows (cvae_train_ll.h): it writes the live rows of dgi / dgh only
-            TrainBwdLLParams lq;
-            lq.xbuf = S + sl.llx;
-            lq.nonce = (cx().ll_train_launch.fetch_add(1u) & 0xffffu) << 16;
-            lq.backoff = pn.bwd_backoff;
-            lq.wrec_t = P + pl.wrec_t; lq.dovl = S + sl.dovl; lq.tape = TP + tl.gates; lq.hrow = TP + tl.hrow; lq.gmask = TP + tl.gmask;
-            lq.dgi = S + sl.dgi; lq.dgh = S + sl.dgh; lq.B = B; lq.Bp = Bp; lq.H = m.H; lq.T = T; lq.status = q.status;
-            const dim3 gl(m.H / 4);
-            const size_t ldsl = (size_t)(256 * 25 + 8 * 24) * sizeof(float);
-            e = B == 1 ? cvae_launch_coop(k_train_bwd_steps_ll<1>, gl, dim3(256), ldsl, st, lq)
-              : B == 2 ? cvae_launch_coop(k_train_bwd_steps_ll<2>, gl, dim3(256), ldsl, st, lq)
-                       : cvae_launch_coop(k_train_bwd_steps_ll<3>, gl, dim3(256), ldsl, st, lq);
-            break;
-        }
-        case BWD_W3: {       // exact operands, 16 units x 16-row tiles per block, zero rows dropped (cvae_train_w3.h)
-            q.wbk = P + pl.wbw3;
-            const int nl1 = m.H == 1024 ? CVAE_BWDW_NL1 : (opt(OPT_BWD_W3_L1_H64) ? 2 : 0);
-            const size_t lds = (size_t)(4 * 16 * 36) * sizeof(float) + 5120 + (size_t)4 * 6 * w3_gpw(m) * 512 + (size_t)4 * nl1 * 1024;
-            const dim3 g((m.H / 16) * pn.bwd_rts);
-            by_launch([&] {
-                return m.H == 1024 ? cvae_launch_coop(k_train_bwd_steps_w3<8, 4, CVAE_BWDW_NL1>, g, dim3(256), lds, st, q)
-                     : nl1 == 2    ? cvae_launch_coop(k_train_bwd_steps_w3<1, 2, 2>, g, dim3(256), lds, st, q)
-                                   : cvae_launch_coop(k_train_bwd_steps_w3<1, 2, 0>, g, dim3(256), lds, st, q);
-            });
-            break;
-        }
-        case BWD_X3: {       // exact operands as limb triples, 8-unit blocks (cvae_train_x3.h)
-            q.wbk = P + pl.wbk3;
-            const size_t lds = (size_t)(4 * 16 * 20) * sizeof(float) + 2560 + (size_t)4 * (m.H / 32) * 512;
-            const dim3 g(NB * pn.bwd_rts);
-            by_launch([&] {
-                return m.H == 1024 ? cvae_launch_coop(k_train_bwd_steps_x3<32>, g, dim3(256), lds, st, q)
-                                   : cvae_launch_coop(k_train_bwd_steps_x3<2>, g, dim3(256), lds, st, q);
-            });
-            break;
-        }
-        default: {           // fp16 pairs (cvae_train_bwd.h)
-            q.wbk = P + pl.wbk;
-            const size_t lds = (size_t)(4 * 16 * 20) * sizeof(float) + 2048;
-            e = m.H == 1024 ? cvae_launch_coop(k_train_bwd_steps<32>, dim3(NB * pn.bwd_rts), dim3(256), lds, st, q)
-                            : cvae_launch_coop(k_train_bwd_steps<2>, dim3(NB * pn.bwd_rts), dim3(256), lds, st, q);
-            break;
-        }
-        }
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(-3, "persistent reverse recurrence failed to launch: %s", hipGetErrorString(e));
-        }
-        tprof.end();
-    } else {         // 2T per-step launches on fp32 products
-        const bool old_gemm = opt(OPT_TRAIN_OLD_GEMM) != 0;
-        BwdStepParams bp;
-        bp.dyl = S + sl.dyl; bp.dytot = S + sl.dytot; bp.dyfb = S + sl.dyfb; bp.wo = P + pl.wo; bp.dh = S + sl.dh;
-        bp.tape = TP + tl.gates; bp.hrow = TP + tl.hrow; bp.gmask = TP + tl.gmask; bp.dgi = S + sl.dgi; bp.dgh = S + sl.dgh;
-        bp.dgic = old_gemm ? nullptr : S + sl.dgic; bp.dghc = old_gemm ? nullptr : S + sl.dghc;
-        bp.B = B; bp.Bp = Bp; bp.H = m.H; bp.Co = m.Co; bp.Cop = m.Cop;
-        bp.part = nullptr; bp.nparts = 0;
-        BwdGemmParams gq;
-        gq.wbp = P + pl.wbp; gq.part = S + sl.bpart; gq.Bp = Bp; gq.H = m.H; gq.Co = m.Co; gq.Cop = m.Cop;
-        const int NRTB = nt16 >= 4 ? 4 : (nt16 >= 2 ? 2 : 1);
-        TrainProf tprof(st, TPROF_BWD, 0.0);
-        for (int tt = T - 1; tt >= 0; --tt) {
-            bp.t = tt;
-            hipLaunchKernelGGL((k_gru_step_bwd), dim3(nblk(m.H, 256), Bp), dim3(256), m.Cop * sizeof(float), st, bp);
-            if (tt > 0 && old_gemm) {
-                // d loss / d h_{t-1} += W_hh^T dgh_t ;  d loss / d y_{t-1} = W_ih[:, C9:]^T dgi_t
-                gemm_ks(st, S + sl.dgh + (long)tt * Bp * m.H3, m.H3, P + pl.whhT, m.H3, S + sl.dh, m.H, Bp, m.H, m.H3, 1);
-                gemm_ks(st, S + sl.dgi + (long)tt * Bp * m.H3, m.H3, P + pl.wyT, m.H3, S + sl.dyfb, m.Cop, Bp, m.Co, m.H3, 0);
-            } else if (tt > 0) {
-                // both products as K-split partial sums in one launch; step tt-1 adds them up
-                gq.dgh = S + sl.dghc;      // (the chunk-major copy k_gru_step_bwd just wrote)
-                gq.dgi = S + sl.dgic;
-                const int KSr = opt(OPT_BWD_KS) >= 1 && opt(OPT_BWD_KS) <= BWD_KS_MAX ? (int)opt(OPT_BWD_KS) : BWD_KS;
-                // a block's BWD_NTN column tiles must lie on one side of the H boundary (it reads dgh OR dgi): any H / 16 with one tile
-                if (m.nch % BWD_NTN)
-                    return fail(-1, "k_bwd_step_gemm with %d column tiles per block needs hidden / 16 to be a multiple of it, got hidden %d",
-                                BWD_NTN, m.H);
-                const dim3 g(nblk((m.H + m.Cop) / 16, BWD_NTN), KSr, nblk(nt16, NRTB));
-                const size_t lds = (size_t)4 * BWD_NTN * NRTB * 16 * 20 * sizeof(float);
-                if (NRTB == 4) hipLaunchKernelGGL((k_bwd_step_gemm<4, BWD_NTN>), g, dim3(256), lds, st, gq);
-                else if (NRTB == 2) hipLaunchKernelGGL((k_bwd_step_gemm<2, BWD_NTN>), g, dim3(256), lds, st, gq);
-                else hipLaunchKernelGGL((k_bwd_step_gemm<1, BWD_NTN>), g, dim3(256), lds, st, gq);
-                bp.part = S + sl.bpart; bp.nparts = KSr;
-            }
-        }
-    }
-    // ---- parameter gradients: contractions over all (t, b) rows.  The four recurrent / projection ones and their bias sums
-    // feed nothing in this backward: with a side stream they run there.
-    WgradWork w;
-    w.m = m; w.t = t; w.tl = tl; w.sl = sl; w.TP = TP; w.S = S; w.scratch = scratch; w.g = *g;
-    w.M = M; w.Bp = Bp; w.acc = acc; w.T = T;
-    w.wyT = pn.bwd != BWD_STEPS ? P + pl.wyT : nullptr;
-    // 64 x 64 tiles beside the 8-unit blocks of a persistent reverse recurrence (several fit on a CU beside one); the 16-unit blocks
-    // leave half the chip to the side stream, and beside per-step launches (hu2048: 169 vs 176 ms) small tiles only cost
-    w.cap = pn.bwd == BWD_X3 || pn.bwd == BWD_PAIR ? 2 : 0;
+    if (int rc = wait_for_side_scratch(p)) return rc;
+    if (int rc = run_bwd_dy(p, dout, clamp_lat_dim)) return rc;
+    if (int rc = p.pn.bwd != BWD_STEPS ? run_bwd_recurrence(p) : run_bwd_steps(p)) return rc;
+    // ---- parameter gradients: contractions over all (t, b) rows.  The four recurrent / projection ones and their bias sums feed nothing
+    // in this backward: with a side stream they run there, in 64 x 64 tiles beside the 8-unit blocks of a persistent reverse recurrence
+    // (several fit on a CU beside one); the 16-unit blocks leave half the chip to the side stream, and beside per-step launches
+    // (hu2048: 169 vs 176 ms) small tiles only cost
+    const WgradWork w{p, *g, acc, p.pn.bwd != BWD_STEPS ? p.P + p.pl.wyT : nullptr, p.pn.bwd == BWD_X3 || p.pn.bwd == BWD_PAIR ? 2 : 0};
     // Where the side-stream work starts (round 5, same-run A/B on MI355X, B = 64: 24.9 ms all at once / 24.8 all behind the chain /
     // 24.5 split): from 64 rows on, the light part at once -- it barely disturbs the data-gradient chain, which the NEXT backward pass
     // waits for --, the two big contractions behind the chain, where they run under the next pass's reverse recurrence (they fit
     // beside its blocks since CVAE_BWD_RING = 5; the recurrence slows by ~0.2 ms per pass, the chain gains ~0.3).  Passes of fewer
     // than 64 rows: everything at once (B = 8: 13.8 vs 13.9 ms, one utterance 5.33 vs 5.42).
-    const bool big_behind_chain = overlap && Bp >= 64;
+    const bool big_behind_chain = overlap && p.Bp >= 64;
     if (overlap) {
-        if (int rc = launch_wgrad_side(st, w, big_behind_chain ? 1 : 3)) return rc;
+        if (int rc = launch_wgrad_side(p.st, w, big_behind_chain ? 1 : 3)) return rc;
     } else {
-        launch_wgrad(st, bws, w);
+        launch_wgrad(p.st, p.bws, w);
     }
-    auto colsum = [&](hipStream_t cs, SplitWs part, const float* A, long lda, float* out, int rows, int n) {
-        colsum_launch(cs, part, A, lda, out, rows, n, acc);
-    };
-    // ---- input side: W_ih[:, :C9]^T, conv_drop, conv1^T, conv0^T, scale_in^T: the chain that produces dx (the next backward pass
-    // of the caller's graph waits for it) first; the two convolution weight gradients and their bias sums feed nothing in this
-    // backward: with a side stream they run there, behind an event recorded after the chain
-    // (conv_drop's gradient in the epilogue; dc1's padding frames / columns stay zero from the scratch memset)
-    float* dc1 = S + sl.dc1p + (long)(m.R - m.ks) * Bp * t.C9p;
-    gemm_nt(st, S + sl.dgi, m.H3, m.H3, 0, P + pl.wixT, m.H3, nullptr, dc1, t.C9p, M, t.C9, m.H3, 0, bws,
-            EpiMask{TP + tl.cmask, B, Bp, T});
-    float* dc0 = S + sl.dc0p + (long)(m.ks - 1) * Bp * t.C3p;
-    gemm_nt(st, S + sl.dc1p + (long)m.ks * (m.ks - 1) * Bp * t.C9p, t.C9p, t.C9p, -(long)m.ks * Bp * t.C9p, P + pl.w1t,
-            (long)m.ks * t.C9p, nullptr, dc0, t.C3p, t.F0 * Bp, t.C3, m.ks * t.C9p, 0, bws);
-    if (dx) {
-        gemm_nt(st, S + sl.dc0p + (long)(m.ks - 1) * Bp * t.C3p, t.C3p, t.C3p, -(long)Bp * t.C3p, P + pl.w0t, (long)m.ks * t.C3p,
-                nullptr, S + sl.dxn, t.Cq, t.Tp * Bp, t.Cq, m.ks * t.C3p, 0, bws);
-        // (scale_in^T is folded into w0t at prepare time: this launch only gathers time-major -> [B][T][C])
-        hipLaunchKernelGGL((k_scale_in_bwd), dim3(nblk((long)B * T * m.C, 256)), dim3(256), 0, st, (const float*)(S + sl.dxn),
-                           (const float*)nullptr, dx, B, Bp, T, m.C, t.Cq, m.pad);
-    }
+    run_input_chain(p, dx);
     if (big_behind_chain)
-        if (int rc = launch_wgrad_side(st, w, 2)) return rc;
-    {
-        hipStream_t cs = st;
-        SplitWs part = bws;
-        if (overlap) {
-            CVAE_HIP_OK(hipEventRecord(cx().side_ready, st));
-            CVAE_HIP_OK(hipStreamWaitEvent(cx().side, cx().side_ready, 0));
-            cs = cx().side;
-            part = SplitWs{S + sl.gpart2, (unsigned*)(S + sl.bcnt2)};
-        }
-        gemm_tn(cs, dc1, t.C9p, TP + tl.c0, t.C3p, t.C3p, (long)m.ks * Bp * t.C3p, S + sl.tmpw, t.K1, M, t.C9, t.K1, 0, part);
-        hipLaunchKernelGGL((k_unpack_dw), dim3(nblk((long)t.C9 * t.C3 * m.ks, 256)), dim3(256), 0, cs, (const float*)(S + sl.tmpw),
-                           (long)t.K1, t.C3p, g->conv1_w, t.C9, t.C3, m.ks, acc);
-        colsum(cs, part, dc1, t.C9p, g->conv1_b, M, t.C9);
-        gemm_tn(cs, dc0, t.C3p, TP + tl.xnp, t.Cq, t.Cq, (long)Bp * t.Cq, S + sl.tmpw, t.K0, t.F0 * Bp, t.C3, t.K0, 0, part);
-        hipLaunchKernelGGL((k_unpack_dw), dim3(nblk((long)t.C3 * m.C * m.ks, 256)), dim3(256), 0, cs, (const float*)(S + sl.tmpw),
-                           (long)t.K0, t.Cq, g->conv0_w, t.C3, m.C, m.ks, acc);
-        colsum(cs, part, dc0, t.C3p, g->conv0_b, t.F0 * Bp, t.C3);
-        if (overlap) {
-            CVAE_HIP_OK(hipEventRecord(side_event_for(scratch), cx().side));     // (re-recorded: now also behind this work)
-            CVAE_HIP_OK(hipEventRecord(cx().side_last, cx().side));
-        }
-    }
+        if (int rc = launch_wgrad_side(p.st, w, 2)) return rc;
+    if (int rc = run_conv_wgrad(p, g, acc, overlap)) return rc;
     CVAE_HIP_OK(hipGetLastError());
     return 0;
 }

@@ -871,6 +871,42 @@ def test_plain_backward_accumulates_into_p_grad_on_a_side_stream(gv, dev):
     assert all(p.grad is None for p in enc.parameters()) and rel_err(x4.grad, res[False][0].cpu().numpy().astype(np.float64), "backward(inputs=[x])") <= 1e-6
 
 
+def test_philox_masks_do_not_depend_on_the_side_stream(gv, dev):
+    """A train-mode pass that draws its own dropout masks (Philox, seeded from torch's CPU generator) draws the feedback operand's
+    mask on the side stream when one is set and T*B*H >= 2^20, and both masks in one launch on its own stream otherwise
+    (draw_train_masks, csrc/cvae_train.inc).  64 rows x 256 frames at H = 64 is the smallest such shape: the same seed gives the same
+    bits of out, h_last, dx and every parameter gradient either way.  No gradient sink and no direct accumulation: both runs return
+    their gradients to autograd, so the mask branch of the forward is the only difference between them."""
+    B, T = 64, 256
+    P = synth.CycleVAEProblem(B=B, T=T, in_dim=10, out_dim=6, lat_dim=4, hidden=64, n_cyc=1, bias_scale=0.1, tag="philox_side")
+    enc = module(gv, P.enc, 10, 8, 64, True, dev)
+    assert B * T * 64 == 1 << 20 and gv._lib().get_option("masks_on_side") == 1      # (else the second run would not take the side branch)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    cot = t(synth.normal("philox_side/cot", (B, T, 8)).astype(np.float32))
+    rng, prev = torch.random.get_rng_state(), gv.set_backward_overlap(False)
+    res = {}
+    try:
+        for side in (None, torch.cuda.Stream()):
+            gv.set_side_stream(side)
+            for p in enc.parameters():
+                p.grad = None
+            torch.manual_seed(20261021)
+            x = t(P.x).requires_grad_(True)
+            out, _, hl = enc(x, t(P.y_in_enc), do=True, clamp_vae=True, lat_dim=4)
+            (out * cot).sum().backward()
+            gv.join_side_stream()
+            torch.cuda.synchronize()
+            res[side is not None] = [out.detach(), hl.detach(), x.grad] + [dict(enc.named_parameters())[k].grad for k in TRAINABLE]
+    finally:
+        gv.set_side_stream(None)
+        gv.set_backward_overlap(prev)
+        torch.random.set_rng_state(rng)
+    gv.check_status()
+    assert float(res[False][0].abs().max()) > 0 and all(bool(torch.isfinite(a).all()) for a in res[False])
+    for name, a, b in zip(["out", "h_last", "dx"] + ["d" + k for k in TRAINABLE], res[False], res[True]):
+        assert torch.equal(a, b), "%s differs with a side stream set (max|d| %.3e)" % (name, float((a - b).abs().max()))
+
+
 def test_fused_step_at_the_timed_geometry(gv, dev):
     """BASELINE configs[2] AT ITS TIMED GEOMETRY inside the suite: stage4.Stage4Step in its default form (fused glue, rec || cv
     stacked, weight-gradient GEMMs on the side stream, flat Adam) on 64 utterances x 80 frames, hu1024 / ld32 / cyc2 -- every

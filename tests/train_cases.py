@@ -266,8 +266,8 @@ class Runner(object):
     """Runs table rows on one backend (width_util.NpMem / TorchMem): options, plan, pass; keeps the train image of every (H, kind),
     the float64 reference of every problem and the result of every row for the comparisons between rows."""
 
-    def __init__(self, mem, note):
-        self.mem, self.note = mem, note
+    def __init__(self, mem, note, tape=False):
+        self.mem, self.note, self.tape = mem, note, tape      # tape: results keep the pass's tape (tools/train_pass_digests.py)
         self.nets, self.refs, self.results = {}, {}, {}
 
     def ref(self, c):
@@ -288,7 +288,7 @@ class Runner(object):
             # (every MFMA-order image is built whatever the options are: one image serves every form)
             self.nets[(c.H, c.kind)] = wu.TrainNet(mem, sd, i, o, c.H)
         net = self.nets[(c.H, c.kind)]
-        self.results[c] = got = net.run(x, y_in, h_in, cm, gm, cot, clamp, what=c.id)
+        self.results[c] = got = net.run(x, y_in, h_in, cm, gm, cot, clamp, what=c.id, tape=self.tape)
         return got
 
     def check(self, c, options, bound_out, bound_grad):

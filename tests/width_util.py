@@ -419,9 +419,10 @@ class TrainNet(object):
         A.sync()
         assert A.guards_intact(), "cvae_net_prepare_train wrote outside the train image (H = %d)" % hidden
 
-    def run(self, x, y_in, h_in, cmask, gmask, cot, clamp_lat_dim, what="", counters=False):
+    def run(self, x, y_in, h_in, cmask, gmask, cot, clamp_lat_dim, what="", counters=False, tape=False):
         """Forward + backward of sum(out * cot): dict(out, y_last [B,Co], h_last [B,H], dx, grads {state key: array}).  counters: also
-        "counters", the eight words of cvae_train_debug_counters read from the pass's scratch (option train_prof)."""
+        "counters", the eight words of cvae_train_debug_counters read from the pass's scratch (option train_prof).  tape: also "tape",
+        the whole tape as the forward left it (read behind the backward, which only reads it)."""
         mem, lib, d = self.mem, self.mem.lib, self.d
         x = np.asarray(x, np.float32)
         B, T, Cin = x.shape
@@ -458,6 +459,8 @@ class TrainNet(object):
             assert np.all(np.isfinite(a)), "%s: %s not fully written / not finite" % (what, name)
         if counters:
             res["counters"] = words
+        if tape:
+            res["tape"] = A.read(otape, _floats(tb))
         return res
 
 
