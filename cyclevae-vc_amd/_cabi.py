@@ -202,7 +202,7 @@ class _Bound(object):
 # Test queries added WITHOUT an ABI bump: a library of the same ABI version built before one of them still loads (every kernel entry
 # point is there), and calling the missing query raises CvaeError.  The shipped library must export them (__graft_entry__.build and
 # tests/test_cabi_exports.py check all of EXPORTS).
-ADDITIVE = ("cvae_plan_pass_deep_tiles", "cvae_plan_train_pass", "cvae_stream_move")
+ADDITIVE = ("cvae_plan_pass_deep_tiles", "cvae_plan_train_pass", "cvae_stream_move", "cvae_cycle_forward_m2m")
 NO_CONTEXT = ("cvae_last_error_string", "cvae_abi_version", "cvae_ctx_create", "cvae_ctx_destroy")
 _CDLLS = {}     # path -> (CDLL with argtypes declared): one load per process, any number of contexts
 
@@ -292,6 +292,9 @@ class CvaeLib(object):
                                          _fp, _fp, _fp, _fp, _fp, _fp, C.c_size_t, C.c_int, _fp]
         L.cvae_cycle_forward_carry.restype = C.c_int
         L.cvae_cycle_forward_carry.argtypes = L.cvae_cycle_forward.argtypes + [C.POINTER(CycleState), C.POINTER(CycleState)]
+        if hasattr(L, "cvae_cycle_forward_m2m"):         # (ADDITIVE, below)
+            L.cvae_cycle_forward_m2m.restype = C.c_int
+            L.cvae_cycle_forward_m2m.argtypes = L.cvae_cycle_forward_carry.argtypes + [C.c_int64, C.c_int64]
         L.cvae_workspace_status.restype = C.c_int
         L.cvae_workspace_status.argtypes = [_fp, C.POINTER(C.c_int32 * 4), _fp]
         L.cvae_train_image_bytes.restype = C.c_size_t
@@ -582,6 +585,21 @@ class CvaeLib(object):
                                                       stream or None, C.byref(si) if si else None, C.byref(so) if so else None),
                     "cvae_cycle_forward_carry")
 
+    def cycle_forward_m2m(self, de, enc_prep, dd, dec_prep, x, cvx, stdim, code_src, code_trg, ncode, y_in_enc, y_in_dec,
+                          B, T, n_cyc, lat_dim, eps, seed, out_lat, out_rec, out_cv, out_latcv, out_reccyc, ws, ws_bytes,
+                          flags=0, stream=0, state_in=None, state_out=None, cvx_cycle_stride=0, code_trg_cycle_stride=0):
+        """cycle_forward_carry with per-cycle cvx [n_cyc,B,T,stdim] / code_trg [n_cyc,B,T,ncode]: the strides are in elements, 0 = one
+        tensor for every cycle.  state_in / state_out None: the fresh form."""
+        si = CycleState(*state_in) if state_in else None
+        so = CycleState(*state_out) if state_out else None
+        self._check(self.lib.cvae_cycle_forward_m2m(C.byref(de), enc_prep, C.byref(dd), dec_prep, x, cvx, stdim, code_src,
+                                                    code_trg, ncode, y_in_enc, y_in_dec, B, T, n_cyc, lat_dim, eps or None,
+                                                    seed, out_lat or None, out_rec or None, out_cv or None,
+                                                    out_latcv or None, out_reccyc or None, ws, ws_bytes, flags,
+                                                    stream or None, C.byref(si) if si else None, C.byref(so) if so else None,
+                                                    int(cvx_cycle_stride), int(code_trg_cycle_stride)),
+                    "cvae_cycle_forward_m2m")
+
     # -- training ------------------------------------------------------------------------------------
     def train_image_bytes(self, d):
         return self.lib.cvae_train_image_bytes(C.byref(d))
@@ -807,7 +825,7 @@ class CvaeLib(object):
 EXPORTS = ("cvae_last_error_string", "cvae_abi_version", "cvae_ctx_create", "cvae_ctx_destroy", "cvae_set_status_sink", "cvae_status_latch", "cvae_set_draw_origin", "cvae_set_draw_parts",
            "cvae_set_option", "cvae_get_option", "cvae_reset_options", "cvae_selftest_limbs", "cvae_selftest_occupy", "cvae_selftest_gemm_work_bytes", "cvae_selftest_gemm", "cvae_set_side_stream", "cvae_join_side_stream", "cvae_net_prepared_bytes", "cvae_net_prepare_scratch_bytes",
            "cvae_net_prepare", "cvae_pass_workspace_bytes", "cvae_gru_rnn_forward", "cvae_gru_rnn_forward_stacked", "cvae_gru_rnn_forward_stacked_carry", "cvae_sample", "cvae_sample_laplace", "cvae_sample_laplace_backward",
-           "cvae_cycle_workspace_bytes", "cvae_cycle_forward", "cvae_cycle_forward_carry", "cvae_profile_collect", "cvae_profile_collect_launches", "cvae_train_profile_collect", "cvae_step_timing", "cvae_workspace_status",
+           "cvae_cycle_workspace_bytes", "cvae_cycle_forward", "cvae_cycle_forward_carry", "cvae_cycle_forward_m2m", "cvae_profile_collect", "cvae_profile_collect_launches", "cvae_train_profile_collect", "cvae_step_timing", "cvae_workspace_status",
            "cvae_train_image_bytes", "cvae_net_prepare_train", "cvae_net_prepare_train_v", "cvae_train_variants_needed", "cvae_plan_train_pass", "cvae_train_tape_bytes", "cvae_train_scratch_bytes",
            "cvae_gru_rnn_forward_train", "cvae_gru_rnn_backward", "cvae_adam_step", "cvae_adam_step_counted", "cvae_train_debug_counters",
            "cvae_sample_cat", "cvae_sample_cat_backward", "cvae_stage4_loss", "cvae_mcd_l1", "cvae_mcd_l1_backward", "cvae_kl_gauss",

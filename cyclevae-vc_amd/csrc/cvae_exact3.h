@@ -176,7 +176,9 @@ __global__ __launch_bounds__(256, 1) void k_gru_steps_v6(Step6Params p) {
 #define CVAE_V6_FPRE 1      // measurement: 0 reads every front-end weight in front of its MFMAs
 #endif
     constexpr bool WACC = CVAE_V6_WACC && KPW == 16 && LIMBS == 3 && !W2S;   // H = 1024, three resident limbs: every weight register is an AGPR
-    constexpr int RF = HOIST ? 1 : (W2S && KFW > 3 ? 3 : KFW);   // front-end operands: all requested ahead (they land during the publish)
+    // front-end operands: all requested ahead (they land during the publish) -- except where the registers do not reach: W2S, and the
+    // H = 1024 instances of more than 8 steps (KFW 9, 11: all ahead they took 20 / 100 B of scratch per lane), which keep a ring of 6
+    constexpr int RF = HOIST ? 1 : (W2S && KFW > 3 ? 3 : (KPW == 16 && KFW > 8 ? 6 : KFW));
     constexpr int RW = KPW < 4 ? KPW : 4;              // W2S: third weight limbs in flight
     const int tid = threadIdx.x, wave = cvae_uniform(tid >> 6), lane = tid & 63, lc = lane & 31, kh = lane >> 5;
     const int H = p.H, NB = H >> 3, nrt = p.Bp >> 5;

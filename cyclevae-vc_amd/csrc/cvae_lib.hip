@@ -246,6 +246,9 @@ struct V6Inst { int H, KFW, limbs; bool w2s; void (*fn)(Step6Params); void (*fn_
 const V6Inst g_v6_inst[] = {
     {1024, 8, 3, false, V6_PAIR(16, 8, 3)},  {1024, 6, 3, false, V6_PAIR(16, 6, 3)},
     {1024, 3, 3, false, V6_PAIR(16, 3, 3)},  {1024, 2, 3, false, V6_PAIR(16, 2, 3)},       // a one-layer front-end (dilation_size 1): encoder in_dim 54, decoder 34
+    // many-to-many decoders ([n_spk-wide code ; z], kernel_size 3, depth 2): in_dim 25..32 (KFW 5), 41..48 (7), 57..64 (9), 65..72 (11)
+    {1024, 5, 3, false, V6_PAIR(16, 5, 3)},  {1024, 7, 3, false, V6_PAIR(16, 7, 3)},
+    {1024, 9, 3, false, V6_PAIR(16, 9, 3)},  {1024, 11, 3, false, V6_PAIR(16, 11, 3)},
     {2048, 8, 3, true, V6_W2S(32, 8)},       {2048, 11, 3, true, V6_W2S(32, 11)},
     {2048, 8, 2, false, V6_PAIR(32, 8, 2)},  {2048, 11, 2, false, V6_PAIR(32, 11, 2)},
     {64, 3, 3, false, V6_PAIR(1, 3, 3)},     {64, 2, 3, false, V6_PAIR(1, 2, 3)},          {64, 1, 3, false, V6_PAIR(1, 1, 3)},
@@ -454,6 +457,7 @@ EvalPlan plan_eval_pass(const Dims& m, int Brows, int T, int flags, int cus, boo
         // (1.6K instead of 2.0K cycles at KFW 8: the blocks reach the poll earlier still; profiles/v6_hot_loop_notes.md): encoder pass
         // 424.9 (0) / 416.4 (2) / 409.9 (4) / 400.3 (8) / 398.5 (10) / 399.9 (12) / 406.3 us (16), decoder pass 478.4 (0) / 419.9 (4) /
         // 399.2 (8) / 388.9 (10) / 386.9 (12) / 384.5 us (16).  The one-layer front-ends (KFW 3, 2) keep the earlier decoder value: not swept.
+        // The many-to-many decoder widths take the value of the swept width next to them (KFW 5: 8, KFW 7 / 9 / 11: 10): not swept either.
         pn.backoff = opt(OPT_V6_BACKOFF) >= 0 ? (int)opt(OPT_V6_BACKOFF) : (m.H == 1024 ? (m.KFW > 6 ? 10 : (m.KFW == 6 ? 16 : 8)) : 0);
     } else if (exact && !unfit && !hoisted && i6h && Bp % 32 == 0 && cus >= m.H / 8 && (long)m.nch * mtot * 80 < (1L << 31)) {
         // the same recurrence behind the front-end GEMM, for a front-end too wide for the LDS limb image (KFW >= 12: find_v6h).
@@ -1284,7 +1288,10 @@ static int cycle_forward_impl(const cvae_net_desc* enc, const void* enc_prepared
                        const float* code_trg, int ncode, const float* y_in_enc, const float* y_in_dec, int B, int T,
                        int n_cyc, int lat_dim_arg, const float* eps, uint64_t seed, float* out_lat, float* out_rec,
                        float* out_cv, float* out_latcv, float* out_reccyc, void* workspace, size_t workspace_bytes,
-                       int flags, void* stream, const cvae_cycle_state* sin, const cvae_cycle_state* sout) {
+                       int flags, void* stream, const cvae_cycle_state* sin, const cvae_cycle_state* sout,
+                       long cvx_cycle_stride, long code_trg_cycle_stride) {
+    // cvx_cycle_stride / code_trg_cycle_stride (elements): cycle i reads cvx + i * stride and code_trg + i * stride -- the per-cycle
+    // converted excitation and target codes of the many-to-many recipes; 0 = one tensor for every cycle (the pointers of before)
     // lat_dim_arg: L, or L | CVAE_DRAW_LAPLACE -- the three draws of a cycle are then Laplace draws (the flag travels in the decoder
     // passes' cvae_pass_input.lat_dim) and the encoder passes clamp at the Laplace floor
     const int lat_dim = draw_dim(lat_dim_arg);
@@ -1298,6 +1305,11 @@ static int cycle_forward_impl(const cvae_net_desc* enc, const void* enc_prepared
     if (me.Co != 2 * lat_dim) return fail(-1, "encoder out_dim %d != 2*lat_dim %d", me.Co, 2 * lat_dim);
     if (md.C != ncode + lat_dim) return fail(-1, "decoder in_dim %d != ncode+lat_dim %d", md.C, ncode + lat_dim);
     if (me.C != stdim + md.Co) return fail(-1, "encoder in_dim %d != stdim+decoder out_dim %d", me.C, stdim + md.Co);
+    // a cycle stride is 0 or reaches over at least one cycle's [B, T, width] block: slices never overlap
+    if (cvx_cycle_stride < 0 || (cvx_cycle_stride > 0 && cvx_cycle_stride < (long)B * T * stdim))
+        return fail(-1, "cvx_cycle_stride %ld: must be 0 or at least B*T*stdim = %ld", cvx_cycle_stride, (long)B * T * stdim);
+    if (code_trg_cycle_stride < 0 || (code_trg_cycle_stride > 0 && code_trg_cycle_stride < (long)B * T * ncode))
+        return fail(-1, "code_trg_cycle_stride %ld: must be 0 or at least B*T*ncode = %ld", code_trg_cycle_stride, (long)B * T * ncode);
     if (workspace_bytes < cvae_cycle_workspace_bytes(tl_ctx, enc, dec, B, T, n_cyc)) return fail(-2, "workspace too small");
     hipStream_t st = (hipStream_t)stream;
     float* ws = (float*)workspace;
@@ -1342,7 +1354,7 @@ static int cycle_forward_impl(const cvae_net_desc* enc, const void* enc_prepared
             const Cell c{&in, sin ? ye(sin, i, 0) : y_in_enc, he(sin, i, 0), lat, ye(sout, i, 0), he(sout, i, 0)};
             if ((rc = run_pass(me, enc, (const float*)enc_prepared, &c, 1, B, T, enc_clamp, pws, status, flags, st, i == 0))) return rc;
         }
-        // rec = D([code_src ; z1]) and cv = D([code_trg ; z2]) share the decoder and do not depend on each other
+        // rec = D([code_src ; z1]) and cv = D([code_trg[i] ; z2]) share the decoder and do not depend on each other
         // (train...:1335-1336): one stacked pass, 2B rows
         memset(&in, 0, sizeof(in));
         in.seg0 = cvae_seg{code_src, ncode, ncode};
@@ -1350,7 +1362,7 @@ static int cycle_forward_impl(const cvae_net_desc* enc, const void* enc_prepared
         in.eps = eps ? eps + (i * 3 + 0) * neps : nullptr;
         in.seed = seed; in.draw_id = (uint64_t)(i * 3 + 0);
         in2 = in;
-        in2.seg0 = cvae_seg{code_trg, ncode, ncode};
+        in2.seg0 = cvae_seg{code_trg + (long)i * code_trg_cycle_stride, ncode, ncode};
         in2.eps = eps ? eps + (i * 3 + 1) * neps : nullptr;
         in2.draw_id = (uint64_t)(i * 3 + 1);
         {
@@ -1358,9 +1370,9 @@ static int cycle_forward_impl(const cvae_net_desc* enc, const void* enc_prepared
                                 {&in2, sin ? yd(sin, i, 1) : y_in_dec, hd(sin, i, 1), cv, yd(sout, i, 1), hd(sout, i, 1)}};
             if ((rc = run_pass(md, dec, (const float*)dec_prepared, c2, 2, B, T, -1, pws, status, flags, st))) return rc;
         }
-        // latcv = E([cvx ; cv])                                   (train...:1337)
+        // latcv = E([cvx[i] ; cv])                                (train...:1337)
         memset(&in, 0, sizeof(in));
-        in.seg0 = cvae_seg{cvx, stdim, stdim};
+        in.seg0 = cvae_seg{cvx + (long)i * cvx_cycle_stride, stdim, stdim};
         in.seg1 = cvae_seg{cv, md.Co, md.Co};
         {
             const Cell c{&in, sin ? ye(sin, i, 1) : y_in_enc, he(sin, i, 1), latcv, ye(sout, i, 1), he(sout, i, 1)};
@@ -1381,16 +1393,29 @@ static int cycle_forward_impl(const cvae_net_desc* enc, const void* enc_prepared
     return 0;
 }
 
+int cvae_cycle_forward_m2m(cvae_ctx* ctx, const cvae_net_desc* enc, const void* enc_prepared, const cvae_net_desc* dec,
+                           const void* dec_prepared, const float* x, const float* cvx, int stdim, const float* code_src,
+                           const float* code_trg, int ncode, const float* y_in_enc, const float* y_in_dec, int B, int T,
+                           int n_cyc, int lat_dim, const float* eps, uint64_t seed, float* out_lat, float* out_rec,
+                           float* out_cv, float* out_latcv, float* out_reccyc, void* workspace, size_t workspace_bytes,
+                           int flags, void* stream, const cvae_cycle_state* state_in, const cvae_cycle_state* state_out,
+                           int64_t cvx_cycle_stride, int64_t code_trg_cycle_stride) {
+    CVAE_ENTER(ctx);
+    return cycle_forward_impl(enc, enc_prepared, dec, dec_prepared, x, cvx, stdim, code_src, code_trg, ncode, y_in_enc, y_in_dec,
+                              B, T, n_cyc, lat_dim, eps, seed, out_lat, out_rec, out_cv, out_latcv, out_reccyc, workspace,
+                              workspace_bytes, flags, stream, state_in, state_out, (long)cvx_cycle_stride,
+                              (long)code_trg_cycle_stride);
+}
+
 int cvae_cycle_forward(cvae_ctx* ctx, const cvae_net_desc* enc, const void* enc_prepared, const cvae_net_desc* dec,
                        const void* dec_prepared, const float* x, const float* cvx, int stdim, const float* code_src,
                        const float* code_trg, int ncode, const float* y_in_enc, const float* y_in_dec, int B, int T,
                        int n_cyc, int lat_dim, const float* eps, uint64_t seed, float* out_lat, float* out_rec,
                        float* out_cv, float* out_latcv, float* out_reccyc, void* workspace, size_t workspace_bytes,
                        int flags, void* stream) {
-    CVAE_ENTER(ctx);
-    return cycle_forward_impl(enc, enc_prepared, dec, dec_prepared, x, cvx, stdim, code_src, code_trg, ncode, y_in_enc, y_in_dec,
-                              B, T, n_cyc, lat_dim, eps, seed, out_lat, out_rec, out_cv, out_latcv, out_reccyc, workspace,
-                              workspace_bytes, flags, stream, nullptr, nullptr);
+    return cvae_cycle_forward_m2m(ctx, enc, enc_prepared, dec, dec_prepared, x, cvx, stdim, code_src, code_trg, ncode, y_in_enc,
+                                  y_in_dec, B, T, n_cyc, lat_dim, eps, seed, out_lat, out_rec, out_cv, out_latcv, out_reccyc,
+                                  workspace, workspace_bytes, flags, stream, nullptr, nullptr, 0, 0);
 }
 
 int cvae_cycle_forward_carry(cvae_ctx* ctx, const cvae_net_desc* enc, const void* enc_prepared, const cvae_net_desc* dec,
@@ -1399,10 +1424,9 @@ int cvae_cycle_forward_carry(cvae_ctx* ctx, const cvae_net_desc* enc, const void
                              int n_cyc, int lat_dim, const float* eps, uint64_t seed, float* out_lat, float* out_rec,
                              float* out_cv, float* out_latcv, float* out_reccyc, void* workspace, size_t workspace_bytes,
                              int flags, void* stream, const cvae_cycle_state* state_in, const cvae_cycle_state* state_out) {
-    CVAE_ENTER(ctx);
-    return cycle_forward_impl(enc, enc_prepared, dec, dec_prepared, x, cvx, stdim, code_src, code_trg, ncode, y_in_enc, y_in_dec,
-                              B, T, n_cyc, lat_dim, eps, seed, out_lat, out_rec, out_cv, out_latcv, out_reccyc, workspace,
-                              workspace_bytes, flags, stream, state_in, state_out);
+    return cvae_cycle_forward_m2m(ctx, enc, enc_prepared, dec, dec_prepared, x, cvx, stdim, code_src, code_trg, ncode, y_in_enc,
+                                  y_in_dec, B, T, n_cyc, lat_dim, eps, seed, out_lat, out_rec, out_cv, out_latcv, out_reccyc,
+                                  workspace, workspace_bytes, flags, stream, state_in, state_out, 0, 0);
 }
 
 int cvae_step_timing(cvae_ctx* ctx, const cvae_net_desc* d, int B, int T, const void* workspace, double out[8], void* stream) {

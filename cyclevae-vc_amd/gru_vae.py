@@ -988,12 +988,37 @@ class TWFSEloss(nn.Module):
         return out
 
 
+def cycle_strides(x, cvx, code_src, code_trg, n_cyc):
+    """The one shape check of the chain's per-cycle inputs (CycleChain, stage4.chain_forward, Stage4Step), on shapes alone (torch
+    tensors or numpy arrays).  Returns the element strides between the cycle slices of cvx / code_trg as cvae_cycle_forward_m2m takes
+    them: B*T*width for a [n_cyc,B,T,.] tensor, 0 for a [B,T,.] tensor that serves every cycle.  ValueError for a wrong cycle count,
+    slices that do not fit x's [B,T] or code_src's width, or an empty width."""
+    B, T = x.shape[0], x.shape[1]
+    if code_src.ndim != 3 or tuple(code_src.shape[:2]) != (B, T) or code_src.shape[2] < 1:
+        raise ValueError("code_src %s does not fit x [%d,%d,.]" % (tuple(code_src.shape), B, T))
+    out = []
+    for name, t, width in (("cvx", cvx, None), ("code_trg", code_trg, code_src.shape[2])):
+        if t.ndim not in (3, 4):
+            raise ValueError("%s must be [B,T,C] or [n_cyc,B,T,C], got %s" % (name, tuple(t.shape)))
+        if t.ndim == 4 and t.shape[0] != n_cyc:
+            raise ValueError("%s has %d cycle slices, the chain runs n_cyc = %d" % (name, t.shape[0], n_cyc))
+        if tuple(t.shape[-3:-1]) != (B, T) or (width is not None and t.shape[-1] != width) or t.shape[-1] < 1:
+            raise ValueError("%s %s does not fit x [%d,%d,.]%s" % (name, tuple(t.shape), B, T,
+                                                                  "" if width is None else " and code_src's %d columns" % width))
+        out.append(B * T * t.shape[-1] if t.ndim == 4 else 0)
+    return out
+
+
 class CycleChain(object):
     """Fused n_cyc reconversion loop in eval form (the four hand-written copies of it in the reference's
     train_gru_cyclevae_gauss_batch.py:1299-1338, 1491-1510, 856-885 collapse to one C-ABI call).
     posterior: "gauss" (the recipe: sampling_vae_batch draws, encoder outputs clamped as clamp_vae does) or "laplace" (the sibling
     recipes: sampling_vae_laplace draws, eps then the uniform in (-0.4999, 0.5), and the clamp_vae_laplace floor), in the fresh, the
-    carry and the stacked-GRU form alike."""
+    carry and the stacked-GRU form alike.
+    per_cycle_inputs: code_trg and cvx may carry a leading cycle axis ([n_cyc,B,T,.], each on its own): cycle i then converts to
+    code_trg[i] and re-encodes with cvx[i], as the many-to-many recipes do (cvae_cycle_forward_m2m)."""
+
+    per_cycle_inputs = True
 
     def __init__(self, model_encoder, model_decoder, lat_dim, n_cyc=2, posterior="gauss"):
         self.enc, self.dec, self.lat_dim, self.n_cyc = model_encoder, model_decoder, lat_dim, n_cyc
@@ -1004,6 +1029,8 @@ class CycleChain(object):
     def __call__(self, x, cvx, code_src, code_trg, y_in_enc, y_in_dec, eps=None, seed=None, outputs=True, state=None,
                  return_state=False):
         """x [B,T,Cin]; cvx [B,T,stdim]; codes [B,T,ncode]; y_in_* [B,1,C]; eps None (Philox) or [n_cyc,3,B,T,L].
+        cvx [n_cyc,B,T,stdim] and / or code_trg [n_cyc,B,T,ncode]: one slice per cycle (a wrong cycle count or slices that do not fit
+        x / code_src raise ValueError before anything is enqueued); a 3-D tensor serves every cycle.
         Returns dict lat, rec, cv, latcv, reccyc, each [n_cyc,B,T,C].
         state: None (fresh window) or the dict a previous call returned with return_state=True: every pass of every cycle then
         continues from its own (y_last, h) of the previous window, as the reference's windowed loop does (train...:1299-1311).
@@ -1028,6 +1055,7 @@ class CycleChain(object):
         f = lambda t: t.to(torch.float32).contiguous()
         x, cvx, code_src, code_trg = f(x), f(cvx), f(code_src), f(code_trg)
         B, T, _ = x.shape
+        cvx_stride, trg_stride = cycle_strides(x, cvx, code_src, code_trg, self.n_cyc)
         if self.enc.hidden_layers > 1 or self.dec.hidden_layers > 1:
             return self._call_deep(x, cvx, code_src, code_trg, f(y_in_enc.reshape(B, -1)), f(y_in_dec.reshape(B, -1)),
                                    None if eps is None else f(eps), _draw_seed() if seed is None else seed, outputs)
@@ -1044,13 +1072,26 @@ class CycleChain(object):
                 out[k] = torch.empty(n, B, T, c, dtype=torch.float32, device=dev)
         p = lambda k: out[k].data_ptr() if k in out else None
         e = None if eps is None else f(eps)
-        if state is None and not return_state:
-            lib.cycle_forward(de, ie.data_ptr(), dd, idd.data_ptr(), x.data_ptr(), cvx.data_ptr(), cvx.shape[2],
-                              code_src.data_ptr(), code_trg.data_ptr(), code_src.shape[2], ye.data_ptr(), yd.data_ptr(),
-                              B, T, n, self._draw_dim, None if e is None else e.data_ptr(), _draw_seed() if seed is None else seed,
-                              p("lat"), p("rec"), p("cv"), p("latcv"), p("reccyc"), self._ws.data_ptr(), self._ws.numel(),
-                              _flags(), _stream())
-            return out
+        fresh = state is None and not return_state
+        s_in, s_out, ptrs = (None, None, lambda d_: None) if fresh else self._state_buffers(state, return_state, B, dev, f)
+        args = (de, ie.data_ptr(), dd, idd.data_ptr(), x.data_ptr(), cvx.data_ptr(), cvx.shape[-1], code_src.data_ptr(),
+                code_trg.data_ptr(), code_src.shape[2], ye.data_ptr(), yd.data_ptr(), B, T, n, self._draw_dim,
+                None if e is None else e.data_ptr(), _draw_seed() if seed is None else seed, p("lat"), p("rec"), p("cv"), p("latcv"),
+                p("reccyc"), self._ws.data_ptr(), self._ws.numel(), _flags(), _stream())
+        if hasattr(lib.lib, "cvae_cycle_forward_m2m"):
+            # the one entry point (state pointers NULL: the fresh form; strides 0: one cvx / code_trg for every cycle)
+            lib.cycle_forward_m2m(*args, ptrs(s_in), ptrs(s_out), cvx_stride, trg_stride)
+        elif cvx_stride or trg_stride:
+            raise _cabi.CvaeError("this build of the library has no cvae_cycle_forward_m2m: per-cycle cvx / code_trg need it")
+        elif fresh:       # (an older build of the same ABI: the two exports it has)
+            lib.cycle_forward(*args)
+        else:
+            lib.cycle_forward_carry(*args, ptrs(s_in), ptrs(s_out))
+        return (out, s_out) if return_state else out
+
+    def _state_buffers(self, state, return_state, B, dev, f):
+        """The carry form's state tensors: (state in, checked, or None; state out, allocated, or None; pointers of either)."""
+        n, L, Co = self.n_cyc, self.lat_dim, self.dec.out_dim
         keys = ("y_enc", "y_dec", "h_enc", "h_dec")
         shapes = {"y_enc": (n, 2, B, 2 * L), "y_dec": (n, 3, B, Co), "h_enc": (n, 2, B, self.enc.hidden_units),
                   "h_dec": (n, 3, B, self.dec.hidden_units)}
@@ -1062,12 +1103,7 @@ class CycleChain(object):
                     raise ValueError("state[%r] has shape %s, expected %s" % (k, tuple(s_in[k].shape), shapes[k]))
         s_out = {k: torch.empty(shapes[k], dtype=torch.float32, device=dev) for k in keys} if return_state else None
         ptrs = lambda d_: None if d_ is None else tuple(d_[k].data_ptr() for k in keys)
-        lib.cycle_forward_carry(de, ie.data_ptr(), dd, idd.data_ptr(), x.data_ptr(), cvx.data_ptr(), cvx.shape[2],
-                                code_src.data_ptr(), code_trg.data_ptr(), code_src.shape[2], ye.data_ptr(), yd.data_ptr(),
-                                B, T, n, self._draw_dim, None if e is None else e.data_ptr(), _draw_seed() if seed is None else seed,
-                                p("lat"), p("rec"), p("cv"), p("latcv"), p("reccyc"), self._ws.data_ptr(), self._ws.numel(),
-                                _flags(), _stream(), ptrs(s_in), ptrs(s_out))
-        return (out, s_out) if return_state else out
+        return s_in, s_out, ptrs
 
     def _call_deep(self, x, cvx, code_src, code_trg, ye, yd, eps, seed, outputs):
         """The fresh chain with a stacked encoder and / or decoder: the passes of cvae_cycle_forward (cycle_forward_impl, same inputs,
@@ -1078,7 +1114,10 @@ class CycleChain(object):
         B, T, Ce = x.shape
         n, L, Co, enc, dec = self.n_cyc, self.lat_dim, self.dec.out_dim, self.enc, self.dec
         Ld, clamp = self._draw_dim, self._clamp
-        stdim, ncode = cvx.shape[2], code_src.shape[2]
+        stdim, ncode = cvx.shape[-1], code_src.shape[2]
+        # per-cycle slices of the many-to-many recipes (3-D: the one tensor in every cycle)
+        trg = lambda i: code_trg[i] if code_trg.dim() == 4 else code_trg
+        cvx_of = lambda i: cvx[i] if cvx.dim() == 4 else cvx
         if enc.out_dim != 2 * L or dec.in_dim != ncode + L or enc.in_dim != stdim + Co or Ce != enc.in_dim:
             raise ValueError("CycleChain: encoder %d -> %d, decoder %d -> %d do not fit lat_dim %d, stdim %d, %d code columns"
                              % (enc.in_dim, enc.out_dim, dec.in_dim, Co, L, stdim, ncode))
@@ -1104,9 +1143,9 @@ class CycleChain(object):
             run(enc, de, ie, wse, pin, ye, clamp, o["lat"])
             run(dec, dd, idd, wsd, lib.pass_input((code_src.data_ptr(), ncode, ncode), lat=o["lat"].data_ptr(), lat_dim=Ld, eps=ep(0),
                                                   seed=seed, draw_id=3 * i), yd, -1, o["rec"])
-            run(dec, dd, idd, wsd, lib.pass_input((code_trg.data_ptr(), ncode, ncode), lat=o["lat"].data_ptr(), lat_dim=Ld, eps=ep(1),
+            run(dec, dd, idd, wsd, lib.pass_input((trg(i).data_ptr(), ncode, ncode), lat=o["lat"].data_ptr(), lat_dim=Ld, eps=ep(1),
                                                   seed=seed, draw_id=3 * i + 1), yd, -1, o["cv"])
-            run(enc, de, ie, wse, lib.pass_input((cvx.data_ptr(), stdim, stdim), (o["cv"].data_ptr(), Co, Co)), ye, clamp, o["latcv"])
+            run(enc, de, ie, wse, lib.pass_input((cvx_of(i).data_ptr(), stdim, stdim), (o["cv"].data_ptr(), Co, Co)), ye, clamp, o["latcv"])
             run(dec, dd, idd, wsd, lib.pass_input((code_src.data_ptr(), ncode, ncode), lat=o["latcv"].data_ptr(), lat_dim=Ld, eps=ep(2),
                                                   seed=seed, draw_id=3 * i + 2), yd, -1, o["reccyc"])
             prev = o["reccyc"]          # (read by the next cycle's first pass, rewritten by its last)

@@ -178,3 +178,38 @@ class FeatureDatasetMultEvalVAECls(FeatureDatasetMultEvalVAE):
     """Dataset for evaluation many-to-many with classifier (src/utils/dataset.py:385-492): the evaluation item plus int64 class codes."""
 
     with_class = True
+
+
+def chain_inputs(batch):
+    """The chain's arguments from one default-collated FeatureDatasetMultTrainVAE(Cls) batch (torch DataLoader): the sibling of
+    stage4.utterance_step_args for the many-to-many items, whose every cycle has a target code and a converted excitation of its own.
+
+        args = loader_m2m.chain_inputs(batch)
+        loss = step(y_in_enc=y_in_pp, y_in_dec=y_in_src, eps=None, **args)               # stage4.Stage4Step / stage4.chain_loss
+        out = chain(args["x"], args["cvx"], args["code_src"], args["code_trg"], y_in_pp, y_in_src)      # gru_vae.CycleChain
+
+    Returns {"x" [B,T,Cin] ('h_src'), "cvx" [n_cyc,B,T,stdim] ('cv_src_list', stacked in cycle order), "code_src" [B,T,n_spk]
+    ('src_code'), "code_trg" [n_cyc,B,T,n_spk] ('src_trg_code_list', stacked in cycle order), "flen_acc": the frame lengths
+    ('flen_src') as a list of ints}.  The tensors stay on the device the batch is on."""
+    need = ("h_src", "src_code", "src_trg_code_list", "cv_src_list", "flen_src")
+    missing = [k for k in need if k not in batch]
+    if missing:
+        raise ValueError("chain_inputs: the batch has no %s (a collated FeatureDatasetMultTrainVAE item has)" % ", ".join(missing))
+    x, code_src = batch["h_src"], batch["src_code"]
+    codes, cvs = list(batch["src_trg_code_list"]), list(batch["cv_src_list"])
+    if not torch.is_tensor(x) or x.dim() != 3:
+        raise ValueError("chain_inputs: 'h_src' must be a collated [B,T,C] tensor")
+    if len(codes) < 1 or len(codes) != len(cvs):
+        raise ValueError("chain_inputs: %d target codes and %d converted excitations: one of each per cycle" % (len(codes), len(cvs)))
+    B, T = x.shape[0], x.shape[1]
+    for name, t in [("src_code", code_src)] + [("src_trg_code_list[%d]" % i, c) for i, c in enumerate(codes)]:
+        if tuple(t.shape) != (B, T, code_src.shape[-1]):
+            raise ValueError("chain_inputs: %s is %s, expected %s" % (name, tuple(t.shape), (B, T, code_src.shape[-1])))
+    for i, c in enumerate(cvs):
+        if c.dim() != 3 or tuple(c.shape[:2]) != (B, T) or c.shape[2] != cvs[0].shape[2]:
+            raise ValueError("chain_inputs: cv_src_list[%d] is %s, expected [%d,%d,%d]" % (i, tuple(c.shape), B, T, cvs[0].shape[2]))
+    flens = batch["flen_src"]
+    flens = [int(v) for v in (flens.tolist() if hasattr(flens, "tolist") else flens)]
+    if len(flens) != B or not all(1 <= n <= T for n in flens):
+        raise ValueError("chain_inputs: flen_src %s does not fit %d utterances of %d padded frames" % (flens, B, T))
+    return dict(x=x, cvx=torch.stack(cvs, 0), code_src=code_src, code_trg=torch.stack(codes, 0), flen_acc=flens)

@@ -72,6 +72,15 @@ class _SplitRows(torch.autograd.Function):
         return torch.cat((da, db), 0), None
 
 
+def cycle_slices(x, cvx, code_src, code_trg, n_cyc):
+    """(cvx_i, code_trg_i): functions of the cycle number that give the cycle's [B,T,.] slice of cvx / code_trg -- slice i of a
+    [n_cyc,B,T,.] tensor, or the 3-D tensor itself -- behind the chain's one shape check (gru_vae.cycle_strides: ValueError)."""
+    import gru_vae
+    gru_vae.cycle_strides(x, cvx, code_src, code_trg, n_cyc)
+    pick = lambda t: (lambda i: t[i]) if t.ndim == 4 else (lambda i: t)
+    return pick(cvx), pick(code_trg)
+
+
 def chain_forward(run_pass, x, cvx, code_src, code_trg, y_in_enc, y_in_dec, eps, lat_dim, n_cyc=2, masks=None, carry=None,
                   stack_rec_cv=False, dec_input=None, posterior="gauss"):
     """The passes of one frame window (train...:1299-1338).  Returns (trajs, state): trajs[i] = {"lat", "rec", "cv", "latcv",
@@ -84,9 +93,13 @@ def chain_forward(run_pass, x, cvx, code_src, code_trg, y_in_enc, y_in_dec, eps,
     stack_rec_cv: the two decoder passes of :1335-1336 share weights and do not depend on each other, so they run as ONE call on
     2B rows (rows [0,B) = rec, [B,2B) = cv; run_pass is told kind "dec2").
     posterior="laplace": the draws are sampling_vae_laplace's (dec_input None = torch_dec_input of that posterior) and the encoder
-    passes are told the Laplace clamp, lat_dim | _cabi.CLAMP_LAPLACE (clamp_vae_laplace, gru_vae.py:415-417)."""
-    L, stdim = lat_dim, cvx.shape[2]
+    passes are told the Laplace clamp, lat_dim | _cabi.CLAMP_LAPLACE (clamp_vae_laplace, gru_vae.py:415-417).
+    cvx [n_cyc,B,T,stdim] and / or code_trg [n_cyc,B,T,ncode] (the many-to-many recipes' cv_src_list / src_trg_code_list, each on its
+    own): cycle i converts to code_trg[i] and re-encodes [cvx[i] ; cv_i]; a 3-D tensor serves every cycle.  ValueError for a cycle
+    axis that is not n_cyc or slices that do not fit x / code_src, before any pass runs."""
+    L, stdim = lat_dim, cvx.shape[-1]
     laplace = _check_posterior(posterior)
+    cvx_i, code_trg_i = cycle_slices(x, cvx, code_src, code_trg, n_cyc)
     if dec_input is None:
         dec_input = torch_dec_input if not laplace else (lambda *a: torch_dec_input(*a, posterior="laplace"))
     Lc = (L | _cabi.CLAMP_LAPLACE) if laplace else L
@@ -112,7 +125,7 @@ def chain_forward(run_pass, x, cvx, code_src, code_trg, y_in_enc, y_in_dec, eps,
         e_in = x if i == 0 else torch.cat((x[:, :, :stdim], prev), 2)
         lat = one("enc", "lat", i, e_in, y_in_enc, Lc, mk("enc", ie)); ie += 1
         if stack_rec_cv:
-            xin = dec_input(lat, (code_src, code_trg), (ep(i, 0), ep(i, 1)), L, (i, 0))
+            xin = dec_input(lat, (code_src, code_trg_i(i)), (ep(i, 0), ep(i, 1)), L, (i, 0))
             ma, mb = mk("dec", idc), mk("dec", idc + 1)     # (conv mask [B,T,9C], gru mask [T,B,H]) per pass
             cat = lambda a, b, d: torch.cat((a, b), d) if torch.is_tensor(a) else __import__("numpy").concatenate((a, b), d)
             m2 = None if ma is None else (cat(ma[0], mb[0], 0), cat(ma[1], mb[1], 1))
@@ -130,8 +143,8 @@ def chain_forward(run_pass, x, cvx, code_src, code_trg, y_in_enc, y_in_dec, eps,
             idc += 2
         else:
             rec = one("dec", "rec", i, dec_input(lat, (code_src,), (ep(i, 0),), L, (i, 0)), y_in_dec, -1, mk("dec", idc)); idc += 1
-            cv = one("dec", "cv", i, dec_input(lat, (code_trg,), (ep(i, 1),), L, (i, 1)), y_in_dec, -1, mk("dec", idc)); idc += 1
-        latcv = one("enc", "latcv", i, torch.cat((cvx, cv), 2), y_in_enc, Lc, mk("enc", ie)); ie += 1
+            cv = one("dec", "cv", i, dec_input(lat, (code_trg_i(i),), (ep(i, 1),), L, (i, 1)), y_in_dec, -1, mk("dec", idc)); idc += 1
+        latcv = one("enc", "latcv", i, torch.cat((cvx_i(i), cv), 2), y_in_enc, Lc, mk("enc", ie)); ie += 1
         reccyc = one("dec", "reccyc", i, dec_input(latcv, (code_src,), (ep(i, 2),), L, (i, 2)), y_in_dec, -1, mk("dec", idc)); idc += 1
         prev = reccyc
         trajs.append({"lat": lat, "rec": rec, "cv": cv, "latcv": latcv, "reccyc": reccyc})
@@ -249,7 +262,7 @@ def chain_loss(run_pass, x, cvx, code_src, code_trg, y_in_enc, y_in_dec, eps, la
     and the five trajectories per cycle."""
     trajs, state = chain_forward(run_pass, x, cvx, code_src, code_trg, y_in_enc, y_in_dec, eps, lat_dim, n_cyc, masks, carry,
                                  stack_rec_cv, posterior=posterior)
-    loss = loss_terms(trajs, x, cvx.shape[2], lat_dim, flen_acc, select_utt_idx, half_cyc, posterior, list_quirk)
+    loss = loss_terms(trajs, x, cvx.shape[-1], lat_dim, flen_acc, select_utt_idx, half_cyc, posterior, list_quirk)
     if return_state:
         return loss, state, trajs
     return loss
@@ -543,14 +556,14 @@ class Stage4Step(object):
         loss = None
         if not self.fused:
             if self.script_loss:
-                loss = script_loss_loop(trajs, x, cvx.shape[2], self.lat_dim, flen_acc, select_utt_idx, half_cyc, list_quirk=self._list_quirk)
+                loss = script_loss_loop(trajs, x, cvx.shape[-1], self.lat_dim, flen_acc, select_utt_idx, half_cyc, list_quirk=self._list_quirk)
             else:
-                loss = loss_terms(trajs, x, cvx.shape[2], self.lat_dim, flen_acc, select_utt_idx, half_cyc, self.posterior, self._list_quirk)
+                loss = loss_terms(trajs, x, cvx.shape[-1], self.lat_dim, flen_acc, select_utt_idx, half_cyc, self.posterior, self._list_quirk)
         if self.overlap_wgrad:
             for m in self.mods.values():
                 m._grad_sink = True
         if self.fused:
-            loss = self._fused_loss_backward(trajs, x, cvx.shape[2], flen_acc, select_utt_idx, half_cyc)
+            loss = self._fused_loss_backward(trajs, x, cvx.shape[-1], flen_acc, select_utt_idx, half_cyc)
         else:
             loss.backward()
         return loss, trajs, state
@@ -749,6 +762,7 @@ class Stage4Step(object):
         script's utterance branch (loss_terms; utterance_step_args sets it).  Returns the loss (0-dim tensor), with
         return_state=True (loss, state)."""
         import gru_vae
+        gru_vae.cycle_strides(x, cvx, code_src, code_trg, self.n_cyc)      # (ValueError before anything is enqueued or taken)
         self._want_state = return_state
         self._list_quirk = bool(list_quirk)
         lagged = self.fused and not self.sync and x.is_cuda

@@ -249,6 +249,85 @@ def _convert_pairs(model_encoder, model_decoder, pairs, y_in_pp, y_in_src, y_in_
     return _decode_pairs(model_decoder, enc, y_in_src, y_in_trg, lat_dim, n_smpl_dec, eps, seed, posterior=posterior)[1]
 
 
+MAX_TARGETS = 31       # conversions per convert_targets call: with the reconstruction, the 32 cells of one stacked pass
+MIN_TILE_ROWS = 4      # from this many rows on a pass runs the row-tile recurrences (fewer: the word-exchange kernels)
+
+
+def convert_targets(model_encoder, model_decoder, feat, code_src, codes_trg, y_in_pp, y_in_dec, lat_dim, n_smpl_dec=300, draw_id=0,
+                    eps=None, seed=None, posterior="gauss"):
+    """ONE source utterance to MANY target speakers (the many-to-many recipes' decode loop): the statements of
+    decode_gru-cyclevae_gauss.py:302-323 with the latent encoded and sampled ONCE,
+
+        lat = E(feat);  z = mean over n_smpl_dec draws of the posterior's sampling function (lat)       (one cvae_latent_mean)
+        rec = D([code_src ; z]),  cv[k] = D([codes_trg[k] ; z]),  k < K                                  (one stacked pass, K + 1 rows)
+
+    as `cvmcep` / `cvmcep_src` share one sampling there.  feat [T,Cin]; code_src [ncode]; codes_trg [K,ncode], 1 <= K <= 31 (one-hot or
+    not, any ncode >= 1 with decoder in_dim = ncode + lat_dim); y_in_* as the reference passes them ([1,1,C]); eps None (Philox: draw k
+    has id draw_id + k, keyed by frame and dimension as convert_pairs keys the draws of a pair's source) or [n_smpl_dec,T,lat_dim].
+    Both passes run the row-tile recurrences whatever K is: the encoder cell and, for K < 3, decoder cells are repeated up to four rows
+    (as stage5.CvgvPass does for a one-pair call), so a row's bits do not depend on K and are those of a convert_pairs call of two or
+    more pairs for the same source, code and draw id.  Single-layer networks; runs under the range policy.
+    Returns (lat [T,2L], rec [T,Co], cv [K,T,Co]) (fp32, device)."""
+    _cabi.posterior_flags(posterior, lat_dim)
+    codes_trg = torch.as_tensor(codes_trg)
+    if codes_trg.dim() != 2 or not 1 <= codes_trg.shape[0] <= MAX_TARGETS:
+        raise ValueError("convert_targets: codes_trg must be [K, ncode] with 1 <= K <= %d, got %s" % (MAX_TARGETS, tuple(codes_trg.shape)))
+    code_src = torch.as_tensor(code_src).reshape(-1)
+    if code_src.numel() != codes_trg.shape[1]:
+        raise ValueError("convert_targets: code_src has %d columns, codes_trg %d" % (code_src.numel(), codes_trg.shape[1]))
+    if model_encoder.hidden_layers > 1 or model_decoder.hidden_layers > 1:
+        raise NotImplementedError("hidden_layers=%d/%d: convert_targets is single-layer; convert stacked networks pair by pair "
+                                  "(convert_pairs)" % (model_encoder.hidden_layers, model_decoder.hidden_layers))
+    if model_decoder.in_dim != codes_trg.shape[1] + lat_dim:
+        raise ValueError("convert_targets: decoder in_dim %d != %d code columns + lat_dim %d" % (model_decoder.in_dim, codes_trg.shape[1], lat_dim))
+    if feat.dim() != 2 or feat.shape[0] < 1 or feat.shape[1] != model_encoder.in_dim:
+        raise ValueError("convert_targets: feat must be [T, %d], got %s" % (model_encoder.in_dim, tuple(feat.shape)))
+    if eps is not None and tuple(eps.shape) != (int(n_smpl_dec), feat.shape[0], lat_dim):
+        raise ValueError("convert_targets: eps must be [n_smpl_dec, T, lat_dim] = %s, got %s" % ((int(n_smpl_dec), feat.shape[0], lat_dim), tuple(eps.shape)))
+    gru_vae._need_cuda(feat, "convert_targets(feat)")
+    gru_vae.check_status()
+    if seed is None and eps is None:
+        seed = gru_vae._draw_seed()      # (a call repeated on the fp32-operand kernels draws what the first try drew)
+    return gru_vae._with_range_retry(lambda: _convert_targets(model_encoder, model_decoder, feat, code_src, codes_trg, y_in_pp, y_in_dec,
+                                                              lat_dim, int(n_smpl_dec), int(draw_id), eps, seed, posterior))
+
+
+def _convert_targets(model_encoder, model_decoder, feat, code_src, codes_trg, y_in_pp, y_in_dec, lat_dim, n, draw_id, eps, seed, posterior):
+    """convert_targets behind its checks and the range policy."""
+    lib, st = gru_vae._lib(), torch.cuda.current_stream().cuda_stream
+    f = lambda t: t.to(torch.float32).contiguous()
+    x = f(feat)
+    dev = x.device
+    T, Cin, L, Co = x.shape[0], model_encoder.in_dim, lat_dim, model_decoder.out_dim
+    K, ncode = codes_trg.shape
+    Ld, clamp = _cabi.posterior_flags(posterior, L)
+    # encoder: the one cell, four times (the rows of a tile are independent recurrences; row 0 is the result)
+    de, ie = model_encoder.prepared(dev)
+    ypp = f(y_in_pp.reshape(1, -1))
+    lat = torch.empty(MIN_TILE_ROWS, T, 2 * L, dtype=torch.float32, device=dev)
+    ws = torch.empty(gru_vae.cells_workspace_bytes(model_encoder, de, MIN_TILE_ROWS, T), dtype=torch.uint8, device=dev)
+    pin = lib.pass_input((x.data_ptr(), Cin, Cin), frames=T)
+    gru_vae.run_cells(model_encoder, de, ie, [pin] * MIN_TILE_ROWS, [ypp.data_ptr()] * MIN_TILE_ROWS, T, clamp,
+                      [lat[r].data_ptr() for r in range(MIN_TILE_ROWS)], ws, gru_vae._flags(), st)
+    # the mean of the draws, once: every decoder row reads it as a plain input segment
+    e = None if eps is None else f(eps)
+    z = torch.empty(T, L, dtype=torch.float32, device=dev)
+    lib.latent_mean([_cabi.LatMeanJob(lat[0].data_ptr(), None if e is None else e.data_ptr(), draw_id, T, 0, z.data_ptr())], Ld, n,
+                    0 if seed is None else int(seed), st)
+    # decoder: rec, cv[0..K), then repeats of the last cell up to four rows
+    codes = torch.cat((f(code_src.to(dev)).reshape(1, ncode), f(codes_trg.to(dev))), 0)
+    rows = max(K + 1, MIN_TILE_ROWS)
+    cell_of = [min(r, K) for r in range(rows)]
+    dd, idd = model_decoder.prepared(dev)
+    yd = f(y_in_dec.reshape(1, -1))
+    out = torch.empty(rows, T, Co, dtype=torch.float32, device=dev)
+    wsd = torch.empty(gru_vae.cells_workspace_bytes(model_decoder, dd, rows, T), dtype=torch.uint8, device=dev)
+    pins = [lib.pass_input((codes[c].data_ptr(), ncode, 0), (z.data_ptr(), L, L), frames=T) for c in cell_of]
+    gru_vae.run_cells(model_decoder, dd, idd, pins, [yd.data_ptr()] * rows, T, -1, [out[r].data_ptr() for r in range(rows)], wsd,
+                      gru_vae._flags(), st)
+    return lat[0], out[0], out[1:K + 1]
+
+
 def _window_edges(Tmax, window, reach):
     """Window edges of the wavefront: `window` frames each, or the caller's own list of window lengths (the last one repeats).  (A
     short first window, so that the decoder starts early, measured no better: every window costs ~0.15 ms of launches on the

@@ -515,6 +515,28 @@ int cvae_cycle_forward_carry(cvae_ctx* ctx, const cvae_net_desc* enc, const void
                              const cvae_cycle_state* state_in, const cvae_cycle_state* state_out);
 
 /*
+ * The chain of the many-to-many recipes: every cycle has its own target codes and its own converted excitation (the
+ * src_trg_code_list[i] / cv_src_list[i] of a FeatureDatasetMultTrainVAE item).  cvae_cycle_forward_carry's arguments plus two
+ * strides in ELEMENTS: cycle i reads cvx + i * cvx_cycle_stride ([B,T,stdim]) and code_trg + i * code_trg_cycle_stride
+ * ([B,T,ncode]), i.e. contiguous [n_cyc,B,T,.] tensors pass B*T*stdim and B*T*ncode:
+ *   cv_i = D([code_trg[i] ; z2]),  latcv_i = E([cvx[i] ; cv_i]);  lat_i, rec_i and rec_cyc_i as before (code_src is one tensor).
+ * A stride of 0 reads one tensor in every cycle; either stride may be 0 on its own.  state_in / state_out may be NULL (the fresh
+ * form).  cvae_cycle_forward and cvae_cycle_forward_carry ARE this call with both strides 0: same launches, same arguments, same
+ * bits.  ncode is any width >= 1 (decoder in_dim = ncode + lat_dim).  Returns -1 before anything is enqueued for a stride that
+ * is negative, or positive and shorter than one cycle's block.
+ */
+int cvae_cycle_forward_m2m(cvae_ctx* ctx, const cvae_net_desc* enc, const void* enc_prepared,
+                           const cvae_net_desc* dec, const void* dec_prepared,
+                           const float* x, const float* cvx, int stdim,
+                           const float* code_src, const float* code_trg, int ncode,
+                           const float* y_in_enc, const float* y_in_dec,
+                           int B, int T, int n_cyc, int lat_dim, const float* eps, uint64_t seed,
+                           float* out_lat, float* out_rec, float* out_cv, float* out_latcv, float* out_reccyc,
+                           void* workspace, size_t workspace_bytes, int flags, void* stream,
+                           const cvae_cycle_state* state_in, const cvae_cycle_state* state_out,
+                           int64_t cvx_cycle_stride, int64_t code_trg_cycle_stride);
+
+/*
  * Measurement aid for bench.py: with CVAE_FLAG_PROFILE every pass records a hipEvent pair on `stream` around its
  * recurrent kernel (the dominant kernel: k_gru_steps).  This call waits for the recorded pairs, returns their
  * summed elapsed time and count, and clears the list.  The events are the only thing the library ever allocates.
